@@ -22,6 +22,13 @@ rank N / world of them -- a contiguous expert range per rank, whose maps are all
 from the assignment vector INSIDE the step (one launch); `--policy expert` (expert e on rank e % world, no balancing) is kept
 for comparison.  Either way ONE all-reduce(SUM) of N + 32*world doubles and a device-side winner pick end the step.
 
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs where `--dump-outputs DIR` asks for
+them and prints the line.  Everything below -- and the other legs (`value_seed1305`, `value_exact` / `value_fast`,
+`sharded_world1`, `phase_ms`, `with_h2d`, `batched`, `training`) -- takes runs of its own and is measured with `--full` only.
+`--dump-outputs DIR`: what the caller of the timed path receives from its last step, as DIR/<name>.npy -- record.npy (the
+float64 result record, include/esac_hip.h), pose.npy (the float32 4x4 pose esac.forward writes) and scores.npy (the float64
+score vector of every hypothesis); the inputs are seeded, so two builds run with the same arguments compare output for output.
+
 `kernels`: per-stage durations measured live with HIP events on the launch stream (R back-to-back launches of one stage
 between one event pair, outside the timed region: an event pair around a single ~4 us launch reads ~4.6 us of its own)
 next to the rocprofv3 per-kernel averages and PMC counters committed under profiles/ for the same workload.
@@ -224,6 +231,25 @@ OWN_BOUND = {
 }
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, record, scores):
+    """--dump-outputs: the record and score vector of the last timed step as a caller receives them, and the pose esac.forward
+    writes from that record.  A score vector beyond half the size limit is written as a fixed, seeded sample of it
+    (scores_sample_index.npy: the hypotheses it holds, in order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    record = np.asarray(record, np.float64)
+    s = scores.detach().cpu().numpy().astype(np.float64)
+    np.save(os.path.join(out_dir, "record.npy"), record)
+    np.save(os.path.join(out_dir, "pose.npy"), record[api.RES_POSE:api.RES_POSE + 16].astype(np.float32).reshape(4, 4))
+    if s.nbytes > DUMP_LIMIT_BYTES // 2:
+        idx = np.sort(np.random.default_rng(0).choice(s.size, DUMP_LIMIT_BYTES // 32, replace=False))
+        np.save(os.path.join(out_dir, "scores_sample_index.npy"), idx.astype(np.float64))
+        s = s[idx]
+    np.save(os.path.join(out_dir, "scores.npy"), s)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` (N > 1) with no launcher around it: start the N ranks here -- torch.distributed.run, one process
     per GPU, rendezvous on 127.0.0.1 -- pass their stderr through and relay rank 0's ONE JSON line.  Never a silent one-GPU run."""
@@ -256,10 +282,15 @@ def main():
     ap.add_argument("--grid", type=str, default=None)
     ap.add_argument("--policy", choices=("range", "expert", "balanced"), default=None)
     ap.add_argument("--scaling", choices=("weak", "strong"), default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: CPU baseline + accuracy, per-stage kernels, roofline, phase times, "
+                         "the other seed / score route, the sharded leg and the h2d / batched / training figures (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (record, pose, scores)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--batch", type=int, default=64, help="frames per launch set for the extra `batched` figure (0 = skip)")
     ap.add_argument("--no-training", action="store_true", help="skip the extra `training` (esac.backward) figure")
-    ap.add_argument("--no-extras", action="store_true", help="only the contract line: no batched / training / h2d / stage legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no batched / training / h2d / sharded legs")
     ap.add_argument("--no-exact", action="store_true", help="skip the `value_exact` leg (the guaranteed routes)")
     ap.add_argument("--sharded-leg", action="store_true",
                     help="(internal) run only the `sharded_world1` leg and print its object: how the default run executes it, in a process of its own")
@@ -347,6 +378,7 @@ def main():
     # (one expert, N*H*W <= 2^21: cfg2), the fp32 ranking stream + exact re-score of the contenders elsewhere
     params = eng.make_params(E, H, W, n_total, seed=BENCH_SEED, call=0, exact_scores="auto", **kw) if world == 1 else None
     ar_timers = []
+    sharded_scores = [None]  # several ranks: the global score vector of the latest step (a view of the exchange buffer)
 
     def step(i):
         k = i % n_frames
@@ -358,8 +390,8 @@ def main():
             pk["total_experts"] = E
         if plans is not None:
             pk["expert_range"] = plans[k]
-        _, rec = D.forward_sharded(eng, d_coords[k], d_assign[k], pk, policy=policy, maps="owned" if owned else "full",
-                                   timers=ar_timers if (i - warmup) % PHASE_EVERY == 0 else None)
+        sharded_scores[0], rec = D.forward_sharded(eng, d_coords[k], d_assign[k], pk, policy=policy, maps="owned" if owned else "full",
+                                                   timers=ar_timers if (i - warmup) % PHASE_EVERY == 0 else None)
         return rec
 
     def sync():
@@ -400,7 +432,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if one_device else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    if world == 1 and not args.sharded_leg:
+    if args.dump_outputs and rank == 0 and not args.sharded_leg:
+        dump_outputs(args.dump_outputs, r, scores if world == 1 else sharded_scores[0])
+    if world == 1 and args.full and not args.sharded_leg:
         # per-phase GPU times (hipEvent brackets between the launches of a call): their own pass over the first steps of the
         # timed sequence, AFTER the timed region -- a bracketed call is ~5 us slower and reading the events costs host time
         eng.set_timing(True, period=1)
@@ -413,7 +447,7 @@ def main():
     # the same K steps under the reference's own RNG seed (thread_rand.h:103, 1305), whose 20-step window is the unluckiest of
     # 24 seeds in refinement work (BENCH_SEED above): printed next to `value`, never instead of it
     seed1305 = None
-    if world == 1 and config_name == "cfg2" and not args.sharded_leg:
+    if world == 1 and args.full and config_name == "cfg2" and not args.sharded_leg:
         params.seed = 1305
         for i in range(warmup):
             step(i)
@@ -429,7 +463,7 @@ def main():
     # ESAC_FLAG_EXACT_SCORES | ESAC_FLAG_EXACT_SAMPLING) -- what "score tensors identical" costs there; never `value`
     value_exact = value_fast = None
     auto_applies = E == 1 and n_total * H * W <= (1 << 21)
-    if world == 1 and config_name in ("cfg2", "cfg3") and not args.no_exact and not args.sharded_leg:
+    if world == 1 and args.full and config_name in ("cfg2", "cfg3") and not args.no_exact and not args.sharded_leg:
         pe = eng.make_params(E, H, W, n_total, seed=BENCH_SEED, call=0, exact_scores=not auto_applies, exact_sampling=not auto_applies, **kw)
         ke = max(10, steps // (1 if config_name == "cfg2" else 4))
         def step_other(i):
@@ -455,7 +489,7 @@ def main():
     # the multi-GPU call path on the ONE GPU of this box: the same K steps through forward_sharded(policy="range") in a one-rank RCCL
     # group -- what a rank adds to the plain call (the collective, Python glue), with the collective really executing
     sharded1 = None
-    if world == 1 and config_name == "cfg2" and not args.no_extras and not args.sharded_leg:
+    if world == 1 and args.full and config_name == "cfg2" and not args.no_extras and not args.sharded_leg:
         # in a process of its own: this leg brings up RCCL (torch.distributed's communicator and the library's), and nothing it does
         # -- not even a fault of that process -- may cost the contract line
         import subprocess
@@ -613,7 +647,7 @@ def main():
                         "fixed part (Amdahl); no scaling curve has been measured by the builder (gpurun offers one GPU)"}
             if out["expected_scaling"]["predicted_ms_per_step"]:
                 out["expected_scaling"]["predicted_value"] = n_total / (out["expected_scaling"]["predicted_ms_per_step"] * 1e-3)
-        if world == 1:
+        if world == 1 and args.full:
             out["phase_ms"] = {"sample_p3p": float(phase[0]), "score": float(phase[1]), "select_rescore": float(phase[2]),
                                "refine": float(phase[3]), "gpu_total": float(phase[4]), "event_bracket_overhead": float(phase[5]),
                                "note": "hipEvent brackets between the launches, in a pass of their own over the first steps of the timed sequence (after the timed region); each figure contains one bracket overhead"}
@@ -725,7 +759,7 @@ def main():
                 rf["hbm_nominal"] = {k: rf[k] for k in ("achieved", "peak", "unit", "frac")}
                 rf.update(bound="valu (fp32 vector; the contract's HBM figure is in hbm_nominal: algorithmic bytes are served from registers / L2)",
                           achieved=rf["valu"]["achieved"], peak=rf["valu"]["peak"], unit=rf["valu"]["unit"], frac=rf["valu"]["frac"])
-        if not args.no_extras and world == 1 and not big:
+        if args.full and not args.no_extras and world == 1 and not big:
             # the reference's calling convention: CPU tensors in (test_esac.py:187 `.cpu()`), so every call pays the H2D hop
             import esac
             f0 = frames[0]
@@ -741,7 +775,7 @@ def main():
             out["with_h2d"] = {"value": n_total * nh / th, "unit": "hypotheses/s", "ms_per_call": th / nh * 1e3,
                                "note": "esac.forward with CPU tensors (the reference's convention): + H2D of the %d-byte map and the assignment per call; never `value`"
                                        % (12 * H * W * E)}
-        if args.batch > 0 and world == 1 and not args.no_extras and not big:
+        if args.full and args.batch > 0 and world == 1 and not args.no_extras and not big:
             # extra figure (not `value`): B independent frames per launch set through esac_hip_forward_batch --
             # the single call's tail is one CU of fp64 work, so frames in flight are what fills the chip
             Bf = args.batch
@@ -760,7 +794,7 @@ def main():
             out["batched"] = {"frames_per_launch": Bf, "launches_timed": nb, "ms_per_batch": tb / nb * 1e3,
                               "value": Bf * n_total * nb / tb, "unit": "hypotheses/s",
                               "note": "esac.forward_batch: frame b == the b-th of B sequential forward calls, bit for bit"}
-        if not args.no_training and world == 1 and not args.no_extras and not big:
+        if args.full and not args.no_training and world == 1 and not args.no_extras and not big:
             # extra figure (not `value`): the training path, esac.backward = esac_hip_backward, same workload
             gts = [np.asarray(f["gt_pose"], np.float32) for f in frames]
             grads = torch.zeros_like(d_coords[0])
@@ -793,7 +827,7 @@ def main():
                         ts.append(time.time() - t0)
                 out["training"]["cpu_oracle_ms_per_call"] = float(np.median(ts)) * 1e3
                 out["training"]["cpu_threads"] = O.max_threads()
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             calls = {k: c for k, (_, _, c) in gpu_poses.items()}
             ks = sorted(calls)
             base, acc = cpu_baseline([frames[k] for k in ks], [assigns[k] for k in ks], [calls[k] for k in ks], n_total,

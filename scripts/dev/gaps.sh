@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/gaps
 mkdir -p $O
-cd /tmp && timeout 600 rocprofv3 --kernel-trace -d $O/tr -o t -- python $R/bench.py --steps 300 --warmup 40 --no-cpu-baseline --no-extras --no-exact > $O/bench.json 2> $O/err.txt
+cd /tmp && timeout 600 rocprofv3 --kernel-trace -d $O/tr -o t -- python $R/bench.py --full --steps 300 --warmup 40 --no-cpu-baseline --no-extras --no-exact > $O/bench.json 2> $O/err.txt
 python - $(find $O/tr -name "*.db" | head -1) <<'PY'
 import sqlite3, sys, numpy as np
 db = sqlite3.connect(sys.argv[1])

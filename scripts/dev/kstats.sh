@@ -6,7 +6,7 @@ CFG=$1; shift
 O=$R/gpurun_out/kstats_$CFG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/stats -o t -- python $R/bench.py --config $CFG --no-cpu-baseline --no-extras $* > $O/bench.json 2> $O/err.txt
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/stats -o t -- python $R/bench.py --full --config $CFG --no-cpu-baseline --no-extras $* > $O/bench.json 2> $O/err.txt
 cd $R
 python - $(find $O/stats -name "*.db" | head -1) $CFG <<'PY'
 import sqlite3, sys

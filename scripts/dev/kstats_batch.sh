@@ -6,7 +6,7 @@ B=${1:-256}
 O=$R/gpurun_out/kstats_batch$B
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/stats -o t -- python $R/bench.py --steps 16 --warmup 4 --no-cpu-baseline --no-training --batch $B > $O/bench.json 2> $O/err.txt
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/stats -o t -- python $R/bench.py --full --steps 16 --warmup 4 --no-cpu-baseline --no-training --batch $B > $O/bench.json 2> $O/err.txt
 cd $R
 python - $(find $O/stats -name "*.db" | head -1) <<'PY'
 import sqlite3, sys

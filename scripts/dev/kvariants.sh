@@ -14,7 +14,7 @@ for rep in 1 2; do
 for v in "$@"; do
   name=${v%%=*}
   rm -rf /tmp/kv_$name
-  (cd /tmp && ESAC_HIP_LIB=/tmp/lib_$name.so timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/kv_$name -o t -- python $R/bench.py $ARGS --no-cpu-baseline --no-extras > /dev/null 2>&1)
+  (cd /tmp && ESAC_HIP_LIB=/tmp/lib_$name.so timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/kv_$name -o t -- python $R/bench.py --full $ARGS --no-cpu-baseline --no-extras > /dev/null 2>&1)
   python - $(find /tmp/kv_$name -name "*.db" | head -1) $name "$FILT" <<'PY'
 import sqlite3, sys
 db = sqlite3.connect(sys.argv[1])

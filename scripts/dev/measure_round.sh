@@ -22,11 +22,11 @@ if [ -z "$BENCH_ONLY" ]; then
   rm -rf gpurun_out/prof_${RND}_*
 fi
 for c in $CFGS; do
-  timeout 1200 python bench.py --config $c ${ARGS[$c]} 2> $P/err_$c.txt | last > $P/${RND}_bench_$c.json
+  timeout 1200 python bench.py --full --config $c ${ARGS[$c]} 2> $P/err_$c.txt | last > $P/${RND}_bench_$c.json
 done
 if [[ " $CFGS " == *" cfg2 "* ]]; then
-  timeout 300 python bench.py --steps 20 --warmup 5 2>/dev/null | last > $P/${RND}_bench_cfg2_driver_style.json
-  for b in 16 32 256; do timeout 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-training --no-exact --batch $b 2>/dev/null | last > $P/${RND}_bench_batch$b.json; done
+  timeout 300 python bench.py --full --steps 20 --warmup 5 2>/dev/null | last > $P/${RND}_bench_cfg2_driver_style.json
+  for b in 16 32 256; do timeout 300 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-training --no-exact --batch $b 2>/dev/null | last > $P/${RND}_bench_batch$b.json; done
 fi
 for f in $P/${RND}_bench_*.json; do python - $f <<'PY'
 import json, sys

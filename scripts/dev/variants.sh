@@ -11,7 +11,7 @@ wait
 for rep in 1 2; do
 for v in "$@"; do
   name=${v%%=*}
-  ESAC_HIP_LIB=/tmp/lib_$name.so timeout 600 python bench.py $ARGS --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+  ESAC_HIP_LIB=/tmp/lib_$name.so timeout 600 python bench.py --full $ARGS --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('%-12s value %.0f ms/step %.4f' % ('$name', d['value'], d['ms_per_step']), {k: round(v,4) for k,v in d.get('phase_ms',{}).items() if k in ('sample_p3p','score','select_rescore','refine')}, [(k['stage'], round(k['avg_us'],1)) for k in d.get('kernels',[])])"
 done

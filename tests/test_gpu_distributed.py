@@ -362,11 +362,16 @@ def _run_bench(world, extra):
     return json.loads(lines[0])
 
 
-def test_bench_multi_rank_path_on_one_device():
+def test_bench_multi_rank_path_on_one_device(tmp_path):
     """bench.py launched the way the driver launches it for N > 1 (torch.distributed.run, one rank per GPU), here with
     two ranks sharing the one GPU through the ESAC_BENCH_ONE_DEVICE test hook (gloo instead of RCCL): barrier-bracketed
-    timing, max over ranks, ONE JSON line from rank 0 with the whole-job aggregate."""
-    d = _run_bench(2, ["--steps", "30", "--warmup", "4"])
+    timing, max over ranks, ONE JSON line from rank 0 with the whole-job aggregate; --dump-outputs writes the global
+    record and score vector of the last timed step."""
+    d = _run_bench(2, ["--steps", "30", "--warmup", "4", "--dump-outputs", str(tmp_path)])
+    record, pose, scores = (np.load(str(tmp_path / (n + ".npy"))) for n in ("record", "pose", "scores"))
+    assert record.shape == (api.RES_DOUBLES,) and scores.shape == (512,) and scores.dtype == np.float64 and np.isfinite(scores).all()
+    assert 0 <= int(record[api.RES_HYP]) < 512
+    assert np.array_equal(pose, record[api.RES_POSE:api.RES_POSE + 16].astype(np.float32).reshape(4, 4))
     assert d["n_gpus"] == 2 and d["steps"] == 30 and d["warmup"] == 4 and d["scaling"] == "weak"
     assert d["config"]["hypotheses_total"] == 512 and d["config"]["shard_sizes"] == [256, 256] and d["config"]["policy"] == "range"
     assert d["value"] > 0 and abs(d["value"] - 512 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]

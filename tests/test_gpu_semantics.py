@@ -276,14 +276,14 @@ def test_stage_timing_entry_point(engine):
 
 
 def test_bench_default_line_has_the_contract_fields():
-    """`python bench.py --steps 30 --warmup 5` (what the driver runs, shortened): ONE JSON line with the contract's keys,
-    the workload of BASELINE configs[1], roofline + per-stage kernels + cpu_baseline + accuracy."""
+    """`python bench.py --full --steps 30 --warmup 5` (what the driver runs, shortened, with every extra figure): ONE JSON
+    line with the contract's keys, the workload of BASELINE configs[1], roofline + per-stage kernels + cpu_baseline + accuracy."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "30", "--warmup", "5", "--batch", "4"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "30", "--warmup", "5", "--batch", "4"],
                          capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -303,6 +303,44 @@ def test_bench_default_line_has_the_contract_fields():
     assert d["accuracy"]["winner_match"] == 1.0 and d["accuracy"]["max_rot_err_rad"] <= 1e-4 and d["accuracy"]["max_trans_err_m"] <= 1e-3
     assert [k["stage"] for k in d["kernels"]] == ["sample", "score", "select_rescore", "refine"]
     assert d["value_seed1305"] > 0 and d["profile_stale"] in (True, False, None)
+
+
+def test_bench_plain_line_is_lean_and_dumps_its_last_timed_step(tmp_path):
+    """`python bench.py --steps 30 --warmup 5 --dump-outputs DIR` (no --full): the contract's line and nothing measured
+    beyond the K timed steps; DIR holds the record, pose and score vector of the LAST timed step (call warmup + steps - 1 on
+    frame (warmup + steps - 1) % 16) -- the same call made here on a context of its own gives them bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "30", "--warmup", "5", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=300, cwd=root)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 30 and d["warmup"] == 5 and d["unit"] == "hypotheses/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 256 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for k in ("cpu_baseline", "accuracy", "kernels", "roofline", "phase_ms", "value_seed1305", "value_fast", "value_exact",
+              "sharded_world1", "with_h2d", "batched", "training"):
+        assert k not in d, k
+    record, pose, scores = (np.load(str(tmp_path / (n + ".npy"))) for n in ("record", "pose", "scores"))
+    assert record.dtype == np.float64 and record.shape == (api.RES_DOUBLES,)
+    assert pose.dtype == np.float32 and np.array_equal(pose, record[api.RES_POSE:api.RES_POSE + 16].astype(np.float32).reshape(4, 4))
+    assert scores.dtype == np.float64 and scores.shape == (256,)
+    last = 5 + 30 - 1
+    f = S.make_frame(last % 16)
+    ha = S.gating_assignment(f, 256)
+    eng = api.Engine(0)
+    p = eng.make_params(1, 60, 80, 256, seed=1320, call=last, exact_scores="auto", focal=f["focal"], ppx=f["ppx"], ppy=f["ppy"],
+                        sub_sampling=f["sub"])
+    sc = torch.empty(256, dtype=torch.float64, device="cuda")
+    rec = eng.forward_device(torch.from_numpy(f["coords"]).cuda(), torch.from_numpy(ha).cuda(), p, scores_out=sc)
+    np.testing.assert_array_equal(record, rec)
+    np.testing.assert_array_equal(scores, sc.cpu().numpy())
 
 
 def _adversarial_frame(kind, E=3):
