@@ -45,7 +45,7 @@ ABI_SYMBOLS = [
     "esac_hip_pick_record", "esac_hip_time_stages", "esac_hip_shard_balanced", "esac_hip_set_wait",
     "esac_hip_set_refine_team", "esac_hip_host_turn",
     "esac_hip_comm_unique_id", "esac_hip_comm_init", "esac_hip_comm_destroy", "esac_hip_allreduce_sum", "esac_hip_comm_info",
-    "esac_hip_host_turn_mean",
+    "esac_hip_host_turn_mean", "esac_hip_backward_batch",
 ]
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
@@ -101,6 +101,8 @@ def load_library():
         for name in ("esac_hip_sample", "esac_hip_score", "esac_hip_select", "esac_hip_refine", "esac_hip_score_exact"):
             getattr(lib, name).argtypes = [vp, vp, vp, pp, vp]
         lib.esac_hip_backward.argtypes = [vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, pp, vp, vp]
+        lib.esac_hip_backward_batch.argtypes = [vp, i32, vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_float, C.c_float, C.c_float,
+                                                pp, vp, vp]
         lib.esac_hip_read.argtypes = [vp, i32, vp, C.c_size_t]
         lib.esac_hip_write_hyps.argtypes = [vp, vp, i32]
         lib.esac_hip_phase_ms.argtypes = [vp, vp]
@@ -265,6 +267,46 @@ class Engine:
             _check(rc, self.lib)
         self._keep = (sc, ha, out_gradients)
         return host
+
+    def backward_batch(self, scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params):
+        """Training path over B frames in one set of launches (esac_hip_backward_batch). scene_coords [B,E,3,H,W] (or [E,3,H,W]
+        shared by all frames), out_gradients float32 [B,E,3,H,W] on this device, contiguous, accumulated into; hyp_assign [B,N];
+        gt_poses [B,4,4]. `params` describes one frame, frame b uses call + b. Returns np.float64 [B,4] (one record per frame).
+        An out-of-range device assignment raises after every frame has run; the exception's `records` holds the [B,4] records."""
+        sc = scene_coords if scene_coords.is_cuda else scene_coords.to(self.device, non_blocking=True)
+        ha = hyp_assign if hyp_assign.is_cuda else hyp_assign.to(self.device, non_blocking=True)
+        sc, ha = sc.contiguous(), ha.contiguous()
+        B = int(ha.shape[0])
+        if not (out_gradients.is_cuda and out_gradients.is_contiguous() and out_gradients.dtype == torch.float32
+                and out_gradients.dim() == 5 and out_gradients.shape[0] == B and tuple(out_gradients.shape[1:]) == tuple(sc.shape[-4:])):
+            raise RuntimeError("esac.backward_batch: the gradient tensor must be a dense float32 device tensor [B,E,3,H,W]")
+        gt = np.ascontiguousarray(np.asarray(gt_poses, np.float32).reshape(-1))
+        if gt.size != 16 * B:
+            raise RuntimeError("esac.backward_batch: gtPoses must hold B 4x4 poses")
+        sc_stride = int(sc.stride(0)) if sc.dim() == 5 else 0
+        host = np.zeros((B, 4), np.float64)
+        rc = self.lib.esac_hip_backward_batch(
+            self.ctx, B, sc.data_ptr(), sc_stride, out_gradients.data_ptr(), int(out_gradients.stride(0)), ha.data_ptr(),
+            gt.ctypes.data, float(w_rot), float(w_trans), float(loss_cut), C.byref(params), self._stream(), host.ctypes.data)
+        self._keep = (sc, ha, out_gradients)
+        if rc != 0:
+            err = RuntimeError("esac (HIP): %s [status %d]" % (self.lib.esac_hip_last_error().decode(), rc))
+            err.records = host
+            raise err
+        return host
+
+    def read_frames(self, which, B):
+        """A training-path buffer (BUF_BWD_PROBS / _LOSSES / _REF_HYPS / _SCORE_GRADS / _SLOTS / _SLOT_INFO / _DLOSS) of all B
+        frames of the last batched backward call, frame-major: [B, ...single-frame shape]."""
+        N, H, W = self._shape
+        rows = min(N, BWD_MAX_SLOTS)
+        shapes = {BUF_BWD_PROBS: ((N,), np.float64), BUF_BWD_LOSSES: ((N,), np.float64), BUF_BWD_REF_HYPS: ((N, 6), np.float64),
+                  BUF_BWD_SCORE_GRADS: ((N,), np.float64), BUF_BWD_SLOTS: ((N,), np.int32),
+                  BUF_BWD_SLOT_INFO: ((rows, 4), np.int32), BUF_BWD_DLOSS: ((rows, 6), np.float64)}
+        shape, dt = shapes[which]
+        out = np.zeros((int(B),) + shape, dt)
+        _check(self.lib.esac_hip_read(self.ctx, which, out.ctypes.data_as(C.c_void_p), out.nbytes), self.lib)
+        return out
 
     # -- single phases (stage-wise parity tests)
     def _phase(self, fn, scene_coords, hyp_assign, params):
@@ -664,3 +706,43 @@ def backward(sceneCoordinates, outGradients, hypAssignment, gtPose, wLossRot, wL
         outGradients.copy_(grads)  # the accumulated tensor back into the caller's (CPU or strided) storage
     _state["last"] = {"backward": out}
     return float(out[0])
+
+
+def backward_batch(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLossRot, wLossTrans, lossCut, shiftX, shiftY,
+                   focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling):
+    """Batched companion of `backward` (new API): sceneCoordinates [B,E,3,H,W] (or [E,3,H,W] shared by all frames),
+    outGradients float32 [B,E,3,H,W] accumulated into in place, hypAssignment [B,N] int64, gtPoses [B,4,4] float32.  Returns
+    the list of the B expected losses.  Frame b is what the b-th of B consecutive `backward` calls would compute (the same
+    hypotheses, slots and losses; the gradient bit for bit when the single calls refine their slots with one workgroup each:
+    include/esac_hip.h).  Advances the call counter by B."""
+    if not all(isinstance(t, torch.Tensor) for t in (sceneCoordinates, outGradients, hypAssignment, gtPoses)):
+        raise RuntimeError("esac.backward_batch: every tensor argument must be a torch.Tensor")
+    if hypAssignment.dtype != torch.int64 or hypAssignment.dim() != 2 or hypAssignment.numel() == 0:
+        raise RuntimeError("esac.backward_batch: hypAssignment must be a non-empty int64 [B,N]")
+    B, N = hypAssignment.shape
+    if sceneCoordinates.dtype != torch.float32 or sceneCoordinates.dim() not in (4, 5) or sceneCoordinates.size(-3) != 3:
+        raise RuntimeError("esac.backward_batch: sceneCoordinates must be float32 [B,E,3,H,W] or [E,3,H,W]")
+    if sceneCoordinates.dim() == 5 and sceneCoordinates.size(0) != B:
+        raise RuntimeError("esac.backward_batch: batch sizes of sceneCoordinates and hypAssignment differ")
+    E, H, W = sceneCoordinates.shape[-4], sceneCoordinates.shape[-2], sceneCoordinates.shape[-1]
+    if outGradients.dtype != torch.float32 or tuple(outGradients.shape) != (B, E, 3, H, W):
+        raise RuntimeError("esac.backward_batch: outGradients must be float32 [B,E,3,H,W]")
+    if gtPoses.dtype != torch.float32 or tuple(gtPoses.shape) != (B, 4, 4):
+        raise RuntimeError("esac.backward_batch: gtPoses must be float32 [B,4,4]")
+    if not hypAssignment.is_cuda:
+        lo, hi = int(hypAssignment.min()), int(hypAssignment.max())
+        if lo < 0 or hi >= E:
+            raise RuntimeError("esac.backward_batch: hypAssignment values must lie in [0,%d), found [%d,%d]" % (E, lo, hi))
+    eng = engine(sceneCoordinates.device.index if sceneCoordinates.is_cuda else None)
+    p = eng.make_params(E, H, W, N, shiftX, shiftY, focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha,
+                        inlierBeta, maxReproj, subSampling, seed=_state["seed"], call=_state["call"],
+                        max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"])
+    _state["call"] += B
+    in_place = outGradients.is_cuda and outGradients.is_contiguous() and outGradients.device == eng.device
+    grads = outGradients if in_place else outGradients.to(eng.device).contiguous()
+    out = eng.backward_batch(sceneCoordinates, grads, hypAssignment, gtPoses.detach().cpu().numpy(), wLossRot, wLossTrans,
+                             lossCut, p)
+    if not in_place:
+        outGradients.copy_(grads)  # the accumulated tensors back into the caller's (CPU or strided) storage
+    _state["last"] = {"backward": out}
+    return [float(v) for v in out[:, 0]]

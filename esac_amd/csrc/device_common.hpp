@@ -218,6 +218,43 @@ __device__ __forceinline__ void frame_view(KArgs& a, int fr) {
 
 __device__ __forceinline__ void frame_view(KArgs& a) { frame_view(a, (int)blockIdx.y); }
 
+// The training path's buffers of frame fr of a batched call (esac_hip_backward_batch): per-hypothesis arrays are [B,N],
+// the slot workspace [B,cap] slots, the small per-slot tables [B,bwd_rows(N)], the record [B,4], the gradient tensor of
+// frame fr at out_grad + fr * grad_frame_stride.  Used together with frame_view (the sampler's and the scores' slices).
+__device__ __forceinline__ void bwd_frame_view(KArgs& a, int fr) {
+    if (fr == 0) return;
+    const size_t N = (size_t)a.N, P = (size_t)a.H * a.W, f = (size_t)fr, cap = (size_t)a.bwd.cap, rows = (size_t)bwd_rows(a.N);
+    a.bwd.sel += f * N;
+    a.bwd.n_sel += f * 4;
+    a.bwd.probs += f * N;
+    a.bwd.losses += f * N;
+    a.bwd.ref_hyps += f * N * 6;
+    a.bwd.sgrad += f * N;
+    a.bwd.dloss += f * rows * 6;
+    a.bwd.map_info += f * rows * 4;
+    a.bwd.maps += f * cap * 2 * P;
+    if (a.bwd.corr_lists) a.bwd.corr_lists = static_cast<char*>(a.bwd.corr_lists) + f * cap * (size_t)corr_entries(a.H * a.W) * 16;
+    a.bwd.grad1 += f * cap * 3 * P;
+    a.bwd.grad2 += f * cap * 3 * P;
+    a.bwd.out += f * 4;
+    a.bwd.out_grad += f * (size_t)a.bwd.grad_frame_stride;
+}
+// ground truth of frame fr into registers (the inline fields on a single call)
+__device__ __forceinline__ void bwd_load_gt(const KArgs& a, int fr, double (&gt)[16], double (&gt_pose)[6]) {
+    if (a.bwd.gt_frames) {
+        const double* g = a.bwd.gt_frames + (size_t)fr * 22;
+#pragma unroll
+        for (int k = 0; k < 16; k++) gt[k] = g[k];
+#pragma unroll
+        for (int k = 0; k < 6; k++) gt_pose[k] = g[16 + k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; k++) gt[k] = a.bwd.gt[k];
+#pragma unroll
+        for (int k = 0; k < 6; k++) gt_pose[k] = a.bwd.gt_pose[k];
+    }
+}
+
 // expert of hypothesis h.  With a single expert the answer is known without the (dependent, ~0.5 us) load every kernel
 // would otherwise start with; hypAssignment values other than 0 are meaningless there (esac.cpp:189 would return them).
 // A value outside [0,E) (the reference would index out of bounds, esac_util.h:183; only a device-resident assignment can

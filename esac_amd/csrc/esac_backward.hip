@@ -28,13 +28,26 @@ namespace esac {
 constexpr int BWD_B = 512;  // threads per slot in the gradient kernels: 8 wavefronts, 256-VGPR budget each
 
 // ================================================================= K5: softmax + ordered selection
-template <int B>
+// BATCH: esac_hip_backward_batch -- one workgroup per frame, the batch-wide overflow word, the frame's assignment check
+template <int B, bool BATCH>
 __global__ __launch_bounds__(B) void k_bwd_select(KArgs a) {
     __shared__ double s_part[2 * (B / 64)];
     __shared__ double s_tot[2];
     __shared__ double s_max[B / 64];
     __shared__ int s_wcount[B / 64];
     __shared__ int s_base;
+    if (BATCH) {
+        frame_view(a);
+        bwd_frame_view(a, (int)blockIdx.y);
+    }
+    // a batch: does this frame's assignment row hold a value outside [0,E)?  (the sampler's status word is shared by the frames;
+    // the same test as flag_bad_assignment: one expert never reads the row)
+    int bad = 0;
+    if (BATCH && a.E > 1) {
+        int mine = 0;
+        for (int h = threadIdx.x; h < a.N; h += B) mine |= (unsigned long long)a.assign[h] >= (unsigned long long)a.E;
+        bad = __syncthreads_or(mine);
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double m = -INFINITY;
     for (int i = threadIdx.x; i < a.N; i += B) {
@@ -91,8 +104,10 @@ __global__ __launch_bounds__(B) void k_bwd_select(KArgs a) {
     acc[1] = 0;
     block_sum<2, B>(acc, s_part, s_tot);
     if (threadIdx.x == 0) {
+        if (BATCH) a.bwd.n_sel[2] = bad != 0;
         a.bwd.n_sel[0] = s_base < a.bwd.cap ? s_base : a.bwd.cap;
         a.bwd.n_sel[1] = s_base;  // unclamped: > cap tells the host to grow the slot workspace and run the call again
+        if (BATCH) atomicMax(a.bwd.sel_max, s_base);  // a batch: the accumulation of every frame looks at the largest
         a.stats[0] = m;
         a.stats[1] = sum;
         a.stats[2] = acc[0];
@@ -100,16 +115,29 @@ __global__ __launch_bounds__(B) void k_bwd_select(KArgs a) {
 }
 
 // ================================================================= K6: losses, expectation, dLoss
-template <int B>
+// BATCH: esac_hip_backward_batch (one workgroup per frame, the frame's ground truth from BwdArgs::gt_frames); the single call's
+// instantiation keeps the ground truth in the kernel arguments
+template <int B, bool BATCH>
 __global__ __launch_bounds__(B) void k_bwd_loss(KArgs a) {
     __shared__ double s_part[B / 64];
     __shared__ double s_tot[1];
+    double gt[16], gt_pose[6];
+    if (BATCH) {
+        frame_view(a);
+        bwd_frame_view(a, (int)blockIdx.y);
+        bwd_load_gt(a, (int)blockIdx.y, gt, gt_pose);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; k++) gt[k] = a.bwd.gt[k];
+#pragma unroll
+        for (int k = 0; k < 6; k++) gt_pose[k] = a.bwd.gt_pose[k];
+    }
     const double wR = a.bwd.w_rot, wT = a.bwd.w_trans, cut = a.bwd.cut;
     double acc[1] = {0};
     for (int h = threadIdx.x; h < a.N; h += B) {
         const double* hp = a.bwd.ref_hyps + (size_t)h * 6;
         const double pose[6] = {hp[0], hp[1], hp[2], hp[3], hp[4], hp[5]};
-        const double l = pose_loss(pose, a.bwd.gt, wR, wT, cut);
+        const double l = pose_loss(pose, gt, wR, wT, cut);
         a.bwd.losses[h] = l;
         acc[0] += a.bwd.probs[h] * l;
     }
@@ -125,15 +153,18 @@ __global__ __launch_bounds__(B) void k_bwd_loss(KArgs a) {
         const double* hp = a.bwd.ref_hyps + (size_t)a.bwd.sel[slot] * 6;
         const double pose[6] = {hp[0], hp[1], hp[2], hp[3], hp[4], hp[5]};
         double j[6];
-        pose_dloss(pose, a.bwd.gt_pose, wR, wT, cut, j);
+        pose_dloss(pose, gt_pose, wR, wT, cut, j);
 #pragma unroll
         for (int k = 0; k < 6; k++) a.bwd.dloss[(size_t)slot * 6 + k] = j[k];
     }
+    // out-of-range hypAssignment: the sampler's status word on a single call; a batch shares that word, so each frame looks at
+    // its own assignment row (k_bwd_select looked at it: n_sel[2])
+    const bool bad = BATCH ? a.bwd.n_sel[2] != 0 : a.status[0] == (unsigned long long)a.sample_epoch;
     if (threadIdx.x == 0) {
         a.bwd.out[0] = expected;
         a.bwd.out[1] = (double)a.bwd.n_sel[1];
         a.bwd.out[2] = a.stats[2];
-        a.bwd.out[3] = (a.status[0] == (unsigned long long)a.sample_epoch) ? 1.0 : 0.0;  // out-of-range hypAssignment (k_sample)
+        a.bwd.out[3] = bad ? 1.0 : 0.0;
     }
 }
 
@@ -431,6 +462,8 @@ __global__ __launch_bounds__(B) void k_bwd_paths(KArgs a) {
     __shared__ double s_sol[18][6];
     __shared__ double s_J[72];
     __shared__ int s_bad;
+    frame_view(a);  // (a batch: grid (2 slots, frames))
+    bwd_frame_view(a, (int)blockIdx.y);
     const int slots = (int)gridDim.x >> 1;
     if ((int)blockIdx.x < slots) bwd_path1<B>(a, (int)blockIdx.x, s_part, s_tot, s_max);
     else                         bwd_path2<B>(a, (int)blockIdx.x - slots, s_part, s_tot, s_sol, s_J, s_bad);
@@ -447,12 +480,16 @@ __global__ __launch_bounds__(256) void k_bwd_accumulate(KArgs a) {
     __shared__ int s_count;
     const int P = a.H * a.W;
     const int e = blockIdx.y;
-    const int n_sel = a.bwd.n_sel[0];
+    KArgs f = a;  // frame blockIdx.z of a batch (grid (tiles, experts, frames)); `a` keeps the batch's record and pinned slots
+    frame_view(f, (int)blockIdx.z);
+    bwd_frame_view(f, (int)blockIdx.z);
+    const int n_sel = f.bwd.n_sel[0];
     // more slots than the workspace holds: nothing is accumulated, the host grows it and retries.  The slots were refined by
     // teams and one of them timed out (a member never became resident): nothing is accumulated either, the host refines the
     // slots again with one workgroup each.  (Both are the same answer in every workgroup of the launch.)
     const bool team_failed = a.bwd.team && __hip_atomic_load(a.coop_counter + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.bwd.team_tag;
-    const bool skip = a.bwd.n_sel[1] > a.bwd.cap || team_failed;
+    // A batch: ONE frame's overflow stops every frame (the host reruns all of them), so they all read the batch-wide maximum.
+    const bool skip = (a.bwd.sel_max ? a.bwd.sel_max[0] : f.bwd.n_sel[1]) > a.bwd.cap || team_failed;
     if (!skip) {
         if (threadIdx.x < 64) {
             int count = 0;
@@ -461,14 +498,14 @@ __global__ __launch_bounds__(256) void k_bwd_accumulate(KArgs a) {
                 int h = 0;
                 bool mine = false;
                 if (slot < n_sel) {
-                    h = a.bwd.sel[slot];
-                    mine = expert_of(a, h) == e;
+                    h = f.bwd.sel[slot];
+                    mine = expert_of(f, h) == e;
                 }
                 const unsigned long long bal = __ballot(mine);
                 if (mine) {
                     const int pos = count + __popcll(bal & ((1ull << threadIdx.x) - 1ull));
                     s_slot[pos] = slot;
-                    s_prob[pos] = a.bwd.probs[h];
+                    s_prob[pos] = f.bwd.probs[h];
                 }
                 count += __popcll(bal);
             }
@@ -478,7 +515,7 @@ __global__ __launch_bounds__(256) void k_bwd_accumulate(KArgs a) {
         const int n = s_count;
         const int rem = blockIdx.x * blockDim.x + threadIdx.x;  // c * P + cell
         if (n > 0 && rem < 3 * P) {
-            float* o = a.bwd.out_grad + (size_t)e * 3 * P + rem;
+            float* o = f.bwd.out_grad + (size_t)e * 3 * P + rem;
             float v = *o;
             constexpr int U = 8;
             for (int base = 0; base < n; base += U) {
@@ -487,7 +524,7 @@ __global__ __launch_bounds__(256) void k_bwd_accumulate(KArgs a) {
                 for (int u = 0; u < U; u++) {
                     const int q = base + u < n ? base + u : n - 1;  // clamped: the loads are unconditional
                     const size_t k = (size_t)s_slot[q] * 3 * P + rem;
-                    t[u] = s_prob[q] * a.bwd.grad1[k] + a.bwd.grad2[k];
+                    t[u] = s_prob[q] * f.bwd.grad1[k] + f.bwd.grad2[k];
                 }
 #pragma unroll
                 for (int u = 0; u < U; u++)
@@ -505,26 +542,35 @@ __global__ __launch_bounds__(256) void k_bwd_accumulate(KArgs a) {
     int last = 0;
     if (threadIdx.x == 0) {
         __threadfence();
-        last = atomicAdd(a.bwd.arrived, 1) == (int)(gridDim.x * gridDim.y) - 1;
+        last = atomicAdd(a.bwd.arrived, 1) == (int)(gridDim.x * gridDim.y * gridDim.z) - 1;
         if (last) a.bwd.arrived[0] = 0;  // (every workgroup has arrived: ready for the next call)
     }
     if (!__shfl(last, 0)) return;
     const int lane = threadIdx.x;
-    const double v = lane < 4 ? a.bwd.out[lane] : lane == 4 ? (team_failed ? 1.0 : 0.0) : lane == 32 ? a.epoch : 0.0;
-    pin_deliver(a.result_pin, v);
+    for (int fr = 0; fr < (int)gridDim.z; fr++) {  // one record per frame, into the frame's pinned slot
+        const double v = lane < 4 ? a.bwd.out[fr * 4 + lane] : lane == 4 ? (team_failed ? 1.0 : 0.0) : lane == 32 ? a.epoch : 0.0;
+        pin_deliver(a.result_pin + (size_t)fr * ESAC_PIN_DOUBLES, v);
+    }
 }
 
 // ---------------------------------------------------------------- launchers
 static inline int slot_grid(const KArgs& a) { return a.N < a.bwd.cap ? a.N : a.bwd.cap; }
 
-void launch_bwd_select(const KArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_bwd_select<1024>, dim3(1), dim3(1024), 0, s, a); }
-void launch_bwd_loss(const KArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_bwd_loss<BWD_B>, dim3(1), dim3(BWD_B), 0, s, a); }
+// (a.frames > 1: esac_hip_backward_batch -- frame b in grid row / layer b)
+void launch_bwd_select(const KArgs& a, hipStream_t s) {
+    if (a.bwd.gt_frames) hipLaunchKernelGGL((k_bwd_select<1024, true>), dim3(1, a.frames), dim3(1024), 0, s, a);
+    else                 hipLaunchKernelGGL((k_bwd_select<1024, false>), dim3(1), dim3(1024), 0, s, a);
+}
+void launch_bwd_loss(const KArgs& a, hipStream_t s) {
+    if (a.bwd.gt_frames) hipLaunchKernelGGL((k_bwd_loss<BWD_B, true>), dim3(1, a.frames), dim3(BWD_B), 0, s, a);
+    else                 hipLaunchKernelGGL((k_bwd_loss<BWD_B, false>), dim3(1), dim3(BWD_B), 0, s, a);
+}
 void launch_bwd_paths(const KArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_bwd_paths<BWD_B>, dim3(2 * slot_grid(a)), dim3(BWD_B), 0, s, a);
+    hipLaunchKernelGGL(k_bwd_paths<BWD_B>, dim3(2 * slot_grid(a), a.frames), dim3(BWD_B), 0, s, a);
 }
 void launch_bwd_accumulate(const KArgs& a, hipStream_t s) {
     const int per_expert = 3 * a.H * a.W;
-    hipLaunchKernelGGL(k_bwd_accumulate, dim3((unsigned)((per_expert + 255) / 256), a.E), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_bwd_accumulate, dim3((unsigned)((per_expert + 255) / 256), a.E, a.frames), dim3(256), 0, s, a);
 }
 
 }  // namespace esac

@@ -104,9 +104,18 @@ struct esac_hip_ctx {
                                           // esac_hip_set_refine_team re-arms it; ESAC_SLOT_TEAMS=0)
     long long slot_team_calls = 0, slot_team_fallbacks = 0;
     bool last_bwd_teams = false;          // the most recent esac_hip_backward refined its slots by teams
-    BwdArgs bws{};  // training-path workspace (pointers only), sized for bN hypotheses, bP cells, bcap slots
-    int bN = 0, bP = 0, bcap = 0;
+    BwdArgs bws{};  // training-path workspace (pointers only), sized for bN hypotheses, bP cells, bslots slots, brows slot-table rows
+    int bP = 0, bcap = 0;  // bcap: slots per frame the single calls have needed so far (where the next one starts)
+    long long bN = 0, bslots = 0, brows = 0;  // over all frames of a batch
+    int bB = 0;                               // frames of the per-frame records
     bool b_lists = false;
+    // batched training calls (esac_hip_backward_batch)
+    int bcap_batch = 0;                       // slots per frame the batches have needed so far
+    long long bwd_budget = 2048LL << 20;      // bytes of slot workspace a batch may use (ESAC_BWD_BATCH_BUDGET_MB): beyond it, chunks of frames
+    int last_bwd_frames = 1;                  // frames whose training-path buffers the workspace holds (the last launch set)
+    int last_bwd_batch_cap = 0;               // slots per frame of the last launch set when it was a batch's (0: a single call)
+    double* h_gt = nullptr;                   // pinned staging of the per-frame ground truth [ESAC_MAX_BATCH,22]
+    double* d_gt = nullptr;                   // ... and its device copy
     float4* sc4 = nullptr;  // packed copy of the maps for the sampler (ensure_pack_ws)
     long long sc4_cells = 0;
     // tile-stationary score workspace (ensure_tiled_ws)
@@ -235,17 +244,23 @@ extern "C" int esac_hip_create(esac_hip_ctx** out, int device) {
     if (c->team_auto_env_off || getenv("ESAC_REFINE_TEAM")) c->team_auto = false;  // (an explicit start value is an explicit size)
     if (const char* e = getenv("ESAC_SLOT_TEAMS")) c->slot_teams = atoi(e) != 0;
     if (const char* e = getenv("ESAC_SPECULATE")) c->spec_off = c->spec_env_off = atoi(e) == 0;
+    if (const char* e = getenv("ESAC_BWD_BATCH_BUDGET_MB")) {
+        const long long mb = atoll(e);
+        if (mb > 0) c->bwd_budget = mb << 20;
+    }
     *out = c;
     return 0;
 }
 
 static void free_bws(esac_hip_ctx* c) {
     void* ptrs[] = {c->bws.sel,   c->bws.n_sel, c->bws.probs,    c->bws.losses,     c->bws.ref_hyps, c->bws.sgrad, c->bws.dloss,
-                    c->bws.maps,  c->bws.map_info, c->bws.corr_lists, c->bws.grad1, c->bws.grad2,   c->bws.out, c->bws.team_gran, c->bws.arrived};
+                    c->bws.maps,  c->bws.map_info, c->bws.corr_lists, c->bws.grad1, c->bws.grad2,   c->bws.out, c->bws.team_gran, c->bws.arrived,
+                    c->bws.sel_max};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     c->bws = BwdArgs{};
-    c->bN = c->bP = c->bcap = 0;
+    c->bN = c->bslots = c->brows = 0;
+    c->bP = c->bB = 0;
     c->b_lists = false;
 }
 
@@ -254,6 +269,8 @@ extern "C" int esac_hip_destroy(esac_hip_ctx* c) {
     DeviceGuard guard(c->device);
     free_ws(c);
     free_bws(c);
+    if (c->d_gt) (void)hipFree(c->d_gt);
+    if (c->h_gt) (void)hipHostFree(c->h_gt);
     if (c->sc4) (void)hipFree(c->sc4);
     drop_comm(c);
     if (c->side) (void)hipStreamDestroy(c->side);
@@ -1013,43 +1030,47 @@ extern "C" int esac_hip_forward_batch(esac_hip_ctx* c, int B, const float* d_sc,
 }
 
 // ---------------------------------------------------------------- training path
-// `cap` = slots (hypotheses with p >= PROB_THRESH) the slab workspace must hold; it only ever grows
-static int ensure_bws(esac_hip_ctx* c, int N, int P, int cap) {
+// `cap` = slots (hypotheses with p >= PROB_THRESH) per frame the slab workspace must hold, for B frames (a batch: every buffer
+// frame-major, device_common.hpp:bwd_frame_view); it only ever grows
+static int ensure_bws(esac_hip_ctx* c, int N, int P, int cap, int B = 1) {
     const bool lists = P > ESAC_REFINE_LDS_CAP;
-    if (N <= c->bN && P <= c->bP && cap <= c->bcap && (!lists || c->b_lists)) return 0;
+    const long long NB = (long long)N * B, slots = (long long)cap * B, rows = (long long)bwd_rows(N) * B;
+    if (NB <= c->bN && P <= c->bP && slots <= c->bslots && rows <= c->brows && B <= c->bB && (!lists || c->b_lists)) return 0;
     HIP_OK(hipDeviceSynchronize());
-    const int nN = N > c->bN ? N : c->bN, nP = P > c->bP ? P : c->bP, ncap = cap > c->bcap ? cap : c->bcap;
+    const long long nN = NB > c->bN ? NB : c->bN, nslots = slots > c->bslots ? slots : c->bslots, nrows = rows > c->brows ? rows : c->brows;
+    const int nP = P > c->bP ? P : c->bP, nB = B > c->bB ? B : c->bB;
     const bool nlists = lists || c->b_lists;
     free_bws(c);
     int rc = 0;
     rc |= alloc(&c->bws.sel, (size_t)nN);
-    rc |= alloc(&c->bws.n_sel, (size_t)4);
+    rc |= alloc(&c->bws.n_sel, (size_t)4 * nB);
     rc |= alloc(&c->bws.probs, (size_t)nN);
     rc |= alloc(&c->bws.losses, (size_t)nN);
     rc |= alloc(&c->bws.ref_hyps, (size_t)nN * 6);
     rc |= alloc(&c->bws.sgrad, (size_t)nN);
-    const size_t rows = (size_t)(nN < ESAC_BWD_MAX_SLOTS ? nN : ESAC_BWD_MAX_SLOTS);  // small per-slot tables: worst case
-    rc |= alloc(&c->bws.dloss, rows * 6);
-    rc |= alloc(&c->bws.maps, (size_t)ncap * 2 * nP);
-    rc |= alloc(&c->bws.map_info, rows * 4);
+    rc |= alloc(&c->bws.dloss, (size_t)nrows * 6);  // small per-slot tables: worst case min(N, 1000) rows per frame
+    rc |= alloc(&c->bws.maps, (size_t)nslots * 2 * nP);
+    rc |= alloc(&c->bws.map_info, (size_t)nrows * 4);
     if (nlists) {
         char* cl = nullptr;
-        rc |= alloc(&cl, (size_t)ncap * ((size_t)nP + 2048) * 16);  // corr_entries(P) < P + 2048 per slot
+        rc |= alloc(&cl, (size_t)nslots * ((size_t)nP + 2048) * 16);  // corr_entries(P) < P + 2048 per slot
         c->bws.corr_lists = cl;
     }
-    rc |= alloc(&c->bws.grad1, (size_t)ncap * nP * 3);
-    rc |= alloc(&c->bws.grad2, (size_t)ncap * nP * 3);
-    rc |= alloc(&c->bws.out, (size_t)4);
+    rc |= alloc(&c->bws.grad1, (size_t)nslots * nP * 3);
+    rc |= alloc(&c->bws.grad2, (size_t)nslots * nP * 3);
+    rc |= alloc(&c->bws.out, (size_t)4 * nB);
     rc |= alloc(&c->bws.arrived, (size_t)1);
-    rc |= alloc(&c->bws.team_gran, (size_t)ncap * 2 * ESAC_REFINE_TEAM_MAX * 32 * 2);  // 16-byte granules: [slot][parity][member][value]
+    rc |= alloc(&c->bws.sel_max, (size_t)1);
+    rc |= alloc(&c->bws.team_gran, (size_t)nslots * 2 * ESAC_REFINE_TEAM_MAX * 32 * 2);  // 16-byte granules: [slot][parity][member][value]
     if (rc) {
         free_bws(c);
         return rc;
     }
-    HIP_OK(hipMemset(c->bws.n_sel, 0, 4 * sizeof(int)));
+    HIP_OK(hipMemset(c->bws.n_sel, 0, (size_t)4 * nB * sizeof(int)));
     HIP_OK(hipMemset(c->bws.arrived, 0, sizeof(int)));
-    HIP_OK(hipMemset(c->bws.team_gran, 0, (size_t)ncap * 2 * ESAC_REFINE_TEAM_MAX * 32 * 2 * sizeof(double)));
-    c->bN = nN; c->bP = nP; c->bcap = ncap; c->b_lists = nlists;
+    HIP_OK(hipMemset(c->bws.sel_max, 0, sizeof(int)));
+    HIP_OK(hipMemset(c->bws.team_gran, 0, (size_t)nslots * 2 * ESAC_REFINE_TEAM_MAX * 32 * 2 * sizeof(double)));
+    c->bN = nN; c->bP = nP; c->bslots = nslots; c->brows = nrows; c->bB = nB; c->b_lists = nlists;
     return 0;
 }
 
@@ -1107,6 +1128,19 @@ static void nearest_rotation_host(double R[9]) {
     }
 }
 
+// The loss's view of a ground-truth camera pose: gt (double of the float input) and trans2pose(gt) (esac_util.h:555-568).
+// false: singular.
+static bool gt_host(const float* h_gt_pose, double gt[16], double gt_pose[6]) {
+    double Ti[16];
+    for (int i = 0; i < 16; i++) gt[i] = (double)h_gt_pose[i];
+    if (!inv4_host(gt, Ti)) return false;
+    double Rg[9] = {Ti[0], Ti[1], Ti[2], Ti[4], Ti[5], Ti[6], Ti[8], Ti[9], Ti[10]};
+    nearest_rotation_host(Rg);
+    rodrigues_mat2vec(Rg, gt_pose);
+    gt_pose[3] = Ti[3]; gt_pose[4] = Ti[7]; gt_pose[5] = Ti[11];
+    return true;
+}
+
 extern "C" int esac_hip_backward(esac_hip_ctx* c, const float* d_sc, float* d_out_gradients, const int64_t* d_assign,
                                  const float* h_gt_pose, float w_loss_rot, float w_loss_trans, float loss_cut,
                                  const esac_hip_params* p, void* stream, double* h_out) {
@@ -1131,13 +1165,8 @@ extern "C" int esac_hip_backward(esac_hip_ctx* c, const float* d_sc, float* d_ou
         cap = c->bcap > 64 ? c->bcap : 64;
         if (cap > worst) cap = worst;
     }
-    double Ti[16], gt[16], gt_pose[6];
-    for (int i = 0; i < 16; i++) gt[i] = (double)h_gt_pose[i];
-    if (!inv4_host(gt, Ti)) return fail(-4, "esac_hip_backward: the ground-truth pose is singular");
-    double Rg[9] = {Ti[0], Ti[1], Ti[2], Ti[4], Ti[5], Ti[6], Ti[8], Ti[9], Ti[10]};
-    nearest_rotation_host(Rg);
-    rodrigues_mat2vec(Rg, gt_pose);
-    gt_pose[3] = Ti[3]; gt_pose[4] = Ti[7]; gt_pose[5] = Ti[11];
+    double gt[16], gt_pose[6];
+    if (!gt_host(h_gt_pose, gt, gt_pose)) return fail(-4, "esac_hip_backward: the ground-truth pose is singular");
     a.tstamps = nullptr;
     hipStream_t s = (hipStream_t)stream;
     c->rt32_stale = false;
@@ -1154,7 +1183,13 @@ extern "C" int esac_hip_backward(esac_hip_ctx* c, const float* d_sc, float* d_ou
     bool use_teams = h_out && c->slot_teams;
     for (int attempt = 0;; attempt++) {
         if ((rc = ensure_bws(c, p->N, P, cap))) return rc;
+        if (cap > c->bcap) c->bcap = cap;
+        c->last_bwd_frames = 1;
+        c->last_bwd_batch_cap = 0;
         a.bwd = c->bws;
+        a.bwd.sel_max = nullptr;  // (batched calls only)
+        a.bwd.gt_frames = nullptr;
+        a.bwd.grad_frame_stride = 0;
         a.bwd.cap = cap;
         a.bwd.team = 0;
         a.bwd.team_tag = 0;
@@ -1208,6 +1243,126 @@ extern "C" int esac_hip_backward(esac_hip_ctx* c, const float* d_sc, float* d_ou
     }
     if (h_out[3] != 0.0)
         return fail(-10, "hypAssignment holds a value outside [0,%d) (device-resident tensor; such hypotheses were scored against expert 0)", p->E);
+    return 0;
+}
+
+// B independent frames of the training path in one set of launches per chunk (include/esac_hip.h).  Frame b is the b-th of B
+// consecutive esac_hip_backward calls (call p->call + b); its slots are refined with one workgroup each.  The slot workspace of
+// B x cap slots is bounded by the context's budget: beyond it the frames go in chunks of consecutive frames, each with its own
+// launch set (the frames are independent, so the chunking changes no result).  An overflow of the slot workspace in ANY frame
+// of a chunk stops the accumulation of every frame of it (one batch-wide word, BwdArgs::sel_max); the host grows `cap` to the
+// largest frame's count and runs selection .. accumulation of the chunk again, so nothing is added twice.
+extern "C" int esac_hip_backward_batch(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
+                                       int64_t grad_frame_stride, const int64_t* d_assign, const float* h_gt_poses, float w_loss_rot,
+                                       float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* h_out) {
+    if (!c) return fail(-1, "null context");
+    if (!p) return fail(-1, "null params");
+    if (!d_sc || !d_out_gradients || !d_assign || !h_gt_poses)
+        return fail(-1, "esac_hip_backward_batch: null coordinate, gradient, assignment or ground-truth pointer");
+    if (!h_out) return fail(-4, "esac_hip_backward_batch: the batched call is blocking only: h_out (host double[B,4]) is required");
+    if (B < 1 || B > ESAC_MAX_BATCH) return fail(-4, "esac_hip_backward_batch: batch size %d outside [1,%d]", B, ESAC_MAX_BATCH);
+    if (p->d_hyp_index || p->hyp_offset)
+        return fail(-4, "esac_hip_backward_batch: sharded calls are not supported (the expectation needs every hypothesis)");
+    if (p->E > 65535) return fail(-4, "esac_hip_backward_batch: at most 65535 experts (one grid row per expert in the accumulation kernel)");
+    if (p->E <= 0 || p->H <= 0 || p->W <= 0 || p->N <= 0) return fail(-4, "E=%d, H=%d, W=%d, N=%d must be positive", p->E, p->H, p->W, p->N);
+    const long long slab = (long long)p->E * 3 * p->H * p->W;
+    if (sc_frame_stride < 0) return fail(-4, "esac_hip_backward_batch: negative coordinate frame stride");
+    if (B > 1 && grad_frame_stride < slab)
+        return fail(-4, "esac_hip_backward_batch: gradient frame stride %lld < E*3*H*W = %lld (frames would share gradients)",
+                    (long long)grad_frame_stride, slab);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (!c->h_gt) {
+        HIP_OK(hipHostMalloc((void**)&c->h_gt, (size_t)ESAC_MAX_BATCH * 22 * sizeof(double), hipHostMallocDefault));
+        HIP_OK(hipMalloc((void**)&c->d_gt, (size_t)ESAC_MAX_BATCH * 22 * sizeof(double)));
+    }
+    HIP_OK(hipStreamSynchronize(s));  // (the staging buffer is free: a batch that failed half-way may have left its copy queued)
+    for (int b = 0; b < B; b++) {
+        double* g = c->h_gt + (size_t)b * 22;
+        if (!gt_host(h_gt_poses + (size_t)b * 16, g, g + 16))
+            return fail(-4, "esac_hip_backward_batch: the ground-truth pose of frame %d is singular", b);
+    }
+    // validation of the parameters (make_args) before anything is launched: the caller's gradients stay untouched on an error
+    KArgs a;
+    int rc = make_args(c, d_sc, d_assign, p, &a, 1, 0);
+    if (rc) return rc;
+    HIP_OK(hipMemcpyAsync(c->d_gt, c->h_gt, (size_t)B * 22 * sizeof(double), hipMemcpyHostToDevice, s));
+    const int N = p->N, P = p->H * p->W, worst = bwd_rows(N);
+    const long long per_slot = 2LL * P + 2LL * 3 * P * (long long)sizeof(double) +
+                               (P > ESAC_REFINE_LDS_CAP ? corr_entries(P) * 16 : 0);  // inlier maps, two slabs, correspondence list
+    int cap = c->bcap_batch > 64 ? c->bcap_batch : 64;
+    if (cap > worst) cap = worst;
+    auto chunk_frames = [&](int cap_, int left) {
+        const long long f = c->bwd_budget / ((long long)cap_ * per_slot);
+        return (int)(f < 1 ? 1 : (f > left ? left : f));
+    };
+    bool any_bad = false;
+    for (int b0 = 0; b0 < B;) {
+        int nb = chunk_frames(cap, B - b0);
+        esac_hip_params pc = *p;
+        pc.call = p->call + (uint64_t)b0;
+        if ((rc = make_args(c, d_sc + (size_t)b0 * sc_frame_stride, d_assign + (size_t)b0 * N, &pc, &a, nb, sc_frame_stride))) return rc;
+        a.tstamps = nullptr;
+        c->rt32_stale = false;
+        mark_sampling(c, a);
+        launch_sample(a, s);                                    // frame b: call p->call + b
+        if ((rc = check_launch("k_sample"))) return rc;
+        launch_rescore_all(a, s, true);                         // (each frame summed as a single call sums it)
+        if ((rc = check_launch("k_rescore(all)"))) return rc;
+        for (int attempt = 0;; attempt++) {
+            if ((rc = ensure_bws(c, N, P, cap, nb))) return rc;
+            if (cap > c->bcap_batch) c->bcap_batch = cap;
+            c->last_bwd_frames = nb;
+            c->last_bwd_batch_cap = cap;
+            a.frames = nb;  // (a rerun after an overflow may take fewer frames: their samples stay where they are)
+            a.bwd = c->bws;
+            a.bwd.cap = cap;
+            a.bwd.team = 0;
+            a.bwd.team_tag = 0;
+            a.bwd.team_max_slots = 0;  // one workgroup per slot
+            a.bwd.out_grad = d_out_gradients + (size_t)b0 * grad_frame_stride;
+            a.bwd.grad_frame_stride = grad_frame_stride;
+            a.bwd.gt_frames = c->d_gt + (size_t)b0 * 22;
+            a.bwd.w_rot = (double)w_loss_rot;
+            a.bwd.w_trans = (double)w_loss_trans;
+            a.bwd.cut = (double)loss_cut;
+            HIP_OK(hipMemsetAsync(a.bwd.sel_max, 0, sizeof(int), s));
+            launch_bwd_select(a, s);
+            if ((rc = check_launch("k_bwd_select"))) return rc;
+            launch_refine_slots(a, s);
+            if ((rc = check_launch("k_refine(slots)"))) return rc;
+            launch_bwd_loss(a, s);
+            if ((rc = check_launch("k_bwd_loss"))) return rc;
+            launch_bwd_paths(a, s);
+            if ((rc = check_launch("k_bwd_paths"))) return rc;
+            KArgs acc = a;
+            acc.result_pin = c->d_pin;  // one pinned slot per frame of the chunk
+            launch_bwd_accumulate(acc, s);
+            if ((rc = check_launch("k_bwd_accumulate"))) return rc;
+            if ((rc = wait_record(c, s, nb, a.epoch, "esac_hip_backward_batch: the accumulation kernel"))) return rc;
+            __sync_synchronize();
+            int needed = 0;
+            for (int b = 0; b < nb; b++) {
+                const int n = (int)c->h_pin[(size_t)b * ESAC_PIN_DOUBLES + 1];
+                needed = n > needed ? n : needed;
+            }
+            if (needed <= cap || attempt >= 1) {  // one retry suffices: the second pass is sized by the largest true count
+                for (int b = 0; b < nb; b++)
+                    for (int k = 0; k < 4; k++) h_out[(size_t)(b0 + b) * 4 + k] = c->h_pin[(size_t)b * ESAC_PIN_DOUBLES + k];
+                break;
+            }
+            cap = needed + 31 > worst ? worst : (needed + 31) / 32 * 32;
+            const int fit = chunk_frames(cap, nb);
+            nb = fit < nb ? fit : nb;
+            c->epoch += 1.0;
+            a.epoch = c->epoch;
+        }
+        for (int b = 0; b < nb; b++) any_bad |= h_out[(size_t)(b0 + b) * 4 + 3] != 0.0;
+        b0 += nb;
+    }
+    if (any_bad)
+        return fail(-10, "hypAssignment holds a value outside [0,%d) in at least one frame (h_out[b*4+3] = 1 names them; such "
+                         "hypotheses were scored against expert 0)", p->E);
     return 0;
 }
 
@@ -1330,7 +1485,8 @@ extern "C" int esac_hip_read(esac_hip_ctx* c, int which, void* h_dst, size_t byt
         case ESAC_BUF_BWD_PATH2: {
             // [slots,3,P] doubles; the caller asks for the first k slots (k = bytes / (3 P 8))
             const size_t slab = 3 * P * sizeof(double);
-            const size_t cap = (size_t)c->bcap;  // slots the slab workspace holds (>= the slots of the last call)
+            // slots the slab workspace holds (>= the slots of the last call); after a batch, frame 0's slabs: its per-frame cap
+            const size_t cap = c->last_bwd_batch_cap > 0 ? (size_t)c->last_bwd_batch_cap : (size_t)c->bslots;
             src = which == ESAC_BUF_BWD_PATH1 ? c->bws.grad1 : c->bws.grad2;
             if (!src || slab == 0) return fail(-6, "esac_hip_read: buffer %d is empty (no backward call has run yet)", which);
             if (bytes == 0 || bytes % slab || bytes / slab > cap)
@@ -1340,6 +1496,11 @@ extern "C" int esac_hip_read(esac_hip_ctx* c, int which, void* h_dst, size_t byt
         }
         default: return fail(-5, "esac_hip_read: unknown buffer id %d", which);
     }
+    // after a batched training call the per-frame buffers above hold its (last chunk's) frames frame-major: B x the size reads them all
+    const bool per_frame = which == ESAC_BUF_BWD_PROBS || which == ESAC_BUF_BWD_LOSSES || which == ESAC_BUF_BWD_REF_HYPS ||
+                           which == ESAC_BUF_BWD_SCORE_GRADS || which == ESAC_BUF_BWD_SLOTS || which == ESAC_BUF_BWD_SLOT_INFO ||
+                           which == ESAC_BUF_BWD_DLOSS;
+    if (per_frame && c->last_bwd_frames > 1 && want > 0 && bytes == want * (size_t)c->last_bwd_frames) want = bytes;
     if (!src || want == 0) return fail(-6, "esac_hip_read: buffer %d is empty (no call has run yet)", which);
     if (bytes != want) return fail(-7, "esac_hip_read: buffer %d holds %zu bytes, caller asked for %zu", which, want, bytes);
     HIP_OK(hipDeviceSynchronize());

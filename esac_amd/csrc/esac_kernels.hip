@@ -1799,12 +1799,14 @@ constexpr int ESAC_SELECT_B = 1024;  // threads of the single-frame variant (A/B
     if (split == 1 && a.N <= grid) hipLaunchKernelGGL((k_select_rescore<ESAC_SELECT_B, false>), dim3(grid, a.frames), dim3(ESAC_SELECT_B), 0, s, a);
     else                           hipLaunchKernelGGL((k_select_rescore<1024, true>), dim3(grid, a.frames, split), dim3(1024), 0, s, a);
 }
-void launch_rescore_all(const KArgs& a, hipStream_t s) {
+void launch_rescore_all(const KArgs& a, hipStream_t s, bool per_frame_shape) {
     const int grid = a.N < 4096 ? a.N : 4096;  // bulk exact scoring: 4 wavefronts per hypothesis are enough
     // few hypotheses (a single frame of <= 256: the guaranteed route of the headline call): a cell is ~120 DEPENDENT fp64
     // operations (IEEE division, sqrt, exp), and with one wavefront per SIMD every one of them waits out its 10 cycles --
     // 16 wavefronts per hypothesis put four on every SIMD, whose chains interleave (9.8 -> 5.x us at 256 hypotheses)
-    if ((long long)a.N * a.frames <= 256) hipLaunchKernelGGL(k_rescore<1024>, dim3(grid, a.frames), dim3(1024), 0, s, a);
+    // per_frame_shape: the shape a SINGLE frame would take whatever the batch is (the two shapes sum a score's cells in different
+    // orders: esac_hip_backward_batch keeps its scores, hence its gradients, bit for bit those of single calls)
+    if ((long long)a.N * (per_frame_shape ? 1 : a.frames) <= 256) hipLaunchKernelGGL(k_rescore<1024>, dim3(grid, a.frames), dim3(1024), 0, s, a);
     else                                  hipLaunchKernelGGL(k_rescore<256>, dim3(grid, a.frames), dim3(256), 0, s, a);
 }
 

@@ -92,6 +92,11 @@ struct BwdArgs {
     unsigned long long team_tag;     // tag of the slot-team launch: the downstream kernels skip their work when it failed
     int* arrived;                    // [1] workgroups of k_bwd_accumulate that are done: the last one delivers the call's record to the
                                      // pinned slot (KArgs::result_pin) and leaves this at zero
+    // batched training calls (esac_hip_backward_batch): frame b = blockIdx.y (k_bwd_accumulate: blockIdx.z) works on its own
+    // slice of every buffer above (bwd_frame_view); null / 0 on a single call
+    const double* gt_frames;         // [B,22] per-frame gt[16] | gt_pose[6] (replaces the inline fields)
+    int* sel_max;                    // [1] the largest unclamped selection of any frame: > cap stops the accumulation of EVERY frame
+    long long grad_frame_stride;     // elements between the gradient tensors of consecutive frames
 };
 
 constexpr int ESAC_SPEC_CNT_FAN = 32, ESAC_SPEC_CNT_STRIDE = 32;  // counters of the second level; ints between two counters (128 bytes)
@@ -221,7 +226,7 @@ void launch_score_tiled(const KArgs& a, hipStream_t s);
 void launch_bucket_order(const KArgs& a, hipStream_t s);  // esac_score_tiled.hip: order[] = hypotheses sorted by expert
 int tiled_sub_tiles(int P);
 void launch_select_rescore(const KArgs& a, hipStream_t s);
-void launch_rescore_all(const KArgs& a, hipStream_t s);
+void launch_rescore_all(const KArgs& a, hipStream_t s, bool per_frame_shape = false);
 void launch_stats_exact(const KArgs& a, hipStream_t s);
 void launch_pick_record(const double* records, int world, double* pin, double epoch, double* zero, int n_zero, hipStream_t s);
 void launch_shard_balanced(const int64_t* assign, int N, int E, int world, int rank, int expert_base, int32_t* index_out,
@@ -242,5 +247,7 @@ void launch_bwd_select(const KArgs& a, hipStream_t s);
 void launch_bwd_loss(const KArgs& a, hipStream_t s);
 void launch_bwd_paths(const KArgs& a, hipStream_t s);  // path I and path II of every slot, one launch
 void launch_bwd_accumulate(const KArgs& a, hipStream_t s);
+// rows of the per-slot tables (dloss, map_info) of one frame: the worst case, so that a batch's tables are frame-major [B,rows]
+__host__ __device__ inline int bwd_rows(int N) { return N < ESAC_BWD_SLOTS_K ? N : ESAC_BWD_SLOTS_K; }
 
 }  // namespace esac

@@ -474,6 +474,7 @@ __global__ __launch_bounds__(B) void k_refine(KArgs a) {
     static_assert(B == REFINE_B, "corr_region() assumes the refinement workgroup size");
     if (threadIdx.x < 33) s_pow10[threadIdx.x] = pow10_int((int)threadIdx.x - 16);  // (visible after the barriers of the winner pick)
     frame_view(a);
+    if (SLOTS) bwd_frame_view(a, (int)blockIdx.y);  // (a batch's slots: grid (cap, frames))
     const int P = a.H * a.W;
     const Cam cam = make_cam(a);
     const PxMap pm{a.sub, a.sub / 2 - a.shift_x, a.sub / 2 - a.shift_y};
@@ -641,8 +642,8 @@ unsigned long long launch_refine(const KArgs& a, hipStream_t s) {
 void launch_refine_slots(const KArgs& a, hipStream_t s) {
     constexpr int B = REFINE_B;
     const bool global_list = a.H * a.W > LDS_CAP;
-    const bool vec = (a.W & 3) == 0 && (reinterpret_cast<uintptr_t>(a.sc) & 15) == 0;
-    const dim3 grid(a.N < a.bwd.cap ? a.N : a.bwd.cap);
+    const bool vec = (a.W & 3) == 0 && (reinterpret_cast<uintptr_t>(a.sc) & 15) == 0 && (a.frames == 1 || (a.sc_frame_stride & 3) == 0);
+    const dim3 grid(a.N < a.bwd.cap ? a.N : a.bwd.cap, a.frames);
     if (global_list) {
         if (vec) hipLaunchKernelGGL((k_refine<B, true, true, true>), grid, dim3(B), 0, s, a);
         else     hipLaunchKernelGGL((k_refine<B, true, false, true>), grid, dim3(B), 0, s, a);

@@ -289,6 +289,35 @@ int esac_hip_backward(esac_hip_ctx* ctx, const float* d_scene_coords, float* d_o
                       const int64_t* d_hyp_assign, const float* h_gt_pose, float w_loss_rot, float w_loss_trans,
                       float loss_cut, const esac_hip_params* p, void* stream, double* h_out);
 
+/*
+ * B frames of the training path in one set of launches (new, beside esac_hip_forward_batch): independent frames fill the CUs
+ * that one frame's selection, slot refinement and accumulation leave idle.  p describes ONE frame (N = hypotheses per frame).
+ * d_scene_coords   frame b at d_scene_coords + b * sc_frame_stride (elements; 0 = every frame reads the same maps), each [E,3,H,W].
+ * d_out_gradients  frame b's tensor [E,3,H,W] at d_out_gradients + b * grad_frame_stride (elements; >= E*3*H*W when B > 1: no
+ *                  two frames alias), ACCUMULATED into (`+=`); within a frame the slots are added in hypothesis order.
+ * d_hyp_assign     [B,N] int64 (device); h_gt_poses host float [B,4,4].
+ * h_out            host double[B,4], REQUIRED (blocking only; NULL: -4): frame b's record at h_out[b*4 + 0..3], the four values
+ *                  of esac_hip_backward.  An out-of-range assignment in frame b sets h_out[b*4+3] = 1 and the call returns -10
+ *                  after every frame has run.
+ * Frame b draws the Philox streams of call p->call + b, so it is the b-th of B consecutive esac_hip_backward calls: the same
+ * hypotheses, slot list, losses, entropy and record; the gradient bit for bit when the single calls refine their slots with one
+ * workgroup each (a context created with ESAC_SLOT_TEAMS=0), else to the rounding of the slot teams' LM sums.
+ * Rejected before anything is launched (the gradients stay untouched): B outside [1,ESAC_MAX_BATCH], null pointers, sharding
+ * (hyp_offset / d_hyp_index), a too small grad_frame_stride, a singular ground-truth pose in any frame, E > 65535.
+ * Slot workspace: B x cap slots (~50 H W bytes each) within a per-context budget (2 GiB; ESAC_BWD_BATCH_BUDGET_MB at context
+ * creation); beyond it the frames run in chunks of consecutive frames, each with its own launches -- the results do not depend on
+ * the chunking.  A frame selecting more slots than the workspace holds stops the accumulation of every frame of its chunk; the
+ * chunk's selection .. accumulation then runs once more with the workspace grown to the largest frame's count.
+ * esac_hip_read afterwards: the ESAC_BUF_BWD_* buffers of the hypotheses and slot tables (PROBS, LOSSES, REF_HYPS,
+ * SCORE_GRADS, SLOTS, SLOT_INFO, DLOSS) hold the last chunk's frames frame-major -- B x the single-frame size reads them all
+ * (a size that fits neither B nor one frame fails), the single-frame size reads frame 0; PATH1 / PATH2 read frame 0's slabs (at most
+ * the batch's slots per frame).
+ */
+int esac_hip_backward_batch(esac_hip_ctx* ctx, int B, const float* d_scene_coords, int64_t sc_frame_stride,
+                            float* d_out_gradients, int64_t grad_frame_stride, const int64_t* d_hyp_assign,
+                            const float* h_gt_poses, float w_loss_rot, float w_loss_trans, float loss_cut,
+                            const esac_hip_params* p, void* stream, double* h_out);
+
 /* The same phases one at a time (asynchronous on `stream`), for stage-wise parity
  * tests and for callers that interleave other work.  Order: sample, score, select, refine. */
 int esac_hip_sample(esac_hip_ctx* ctx, const float* d_scene_coords, const int64_t* d_hyp_assign,
