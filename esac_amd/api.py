@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "esac_hip_set_refine_team", "esac_hip_host_turn",
     "esac_hip_comm_unique_id", "esac_hip_comm_init", "esac_hip_comm_destroy", "esac_hip_allreduce_sum", "esac_hip_comm_info",
     "esac_hip_host_turn_mean", "esac_hip_backward_batch",
+    "esac_hip_forward_batch_cams", "esac_hip_backward_batch_cams",
 ]
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
@@ -73,6 +74,42 @@ class Params(C.Structure):
     ]
 
 
+class FrameCam(C.Structure):
+    """struct esac_hip_frame_cam (include/esac_hip.h): one frame's camera in a batch with per-frame cameras, 32 bytes."""
+    _fields_ = [
+        ("shift_x", C.c_int32), ("shift_y", C.c_int32),
+        ("focal", C.c_float), ("ppx", C.c_float), ("ppy", C.c_float),
+        ("reserved", C.c_int32 * 3),
+    ]
+
+
+CAM_DTYPE = np.dtype([("shift_x", np.int32), ("shift_y", np.int32), ("focal", np.float32), ("ppx", np.float32),
+                      ("ppy", np.float32), ("reserved", np.int32, (3,))])
+
+
+def make_cams(shift_x, shift_y, focal, ppx, ppy):
+    """A table of B esac_hip_frame_cam records (numpy structured array, CAM_DTYPE) from five length-B sequences."""
+    B = len(shift_x)
+    cams = np.zeros(B, CAM_DTYPE)
+    cams["shift_x"], cams["shift_y"] = np.asarray(shift_x, np.int64), np.asarray(shift_y, np.int64)
+    cams["focal"], cams["ppx"], cams["ppy"] = np.asarray(focal, np.float64), np.asarray(ppx, np.float64), np.asarray(ppy, np.float64)
+    return cams
+
+
+def _cams_arg(cams, B, who):
+    """`cams` of Engine.forward_batch / backward_batch as a contiguous CAM_DTYPE array of B records (kept alive by the caller)."""
+    if isinstance(cams, np.ndarray) and cams.dtype == CAM_DTYPE:
+        arr = np.ascontiguousarray(cams)
+    elif isinstance(cams, (list, tuple)) and all(isinstance(c, FrameCam) for c in cams):
+        arr = make_cams([c.shift_x for c in cams], [c.shift_y for c in cams], [c.focal for c in cams],
+                        [c.ppx for c in cams], [c.ppy for c in cams])
+    else:
+        raise RuntimeError("%s: cams must be a numpy array of dtype api.CAM_DTYPE (api.make_cams) or a list of api.FrameCam" % who)
+    if arr.ndim != 1 or arr.shape[0] != B:
+        raise RuntimeError("%s: cams must hold one record per frame (%d), found shape %s" % (who, B, tuple(arr.shape)))
+    return arr
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -98,11 +135,14 @@ def load_library():
         lib.esac_hip_destroy.argtypes = [vp]
         lib.esac_hip_forward.argtypes = [vp, vp, vp, pp, vp, vp, vp, vp]
         lib.esac_hip_forward_batch.argtypes = [vp, i32, vp, C.c_int64, vp, pp, vp, vp, vp, vp]
+        lib.esac_hip_forward_batch_cams.argtypes = [vp, i32, vp, C.c_int64, vp, pp, vp, vp, vp, vp, vp]
         for name in ("esac_hip_sample", "esac_hip_score", "esac_hip_select", "esac_hip_refine", "esac_hip_score_exact"):
             getattr(lib, name).argtypes = [vp, vp, vp, pp, vp]
         lib.esac_hip_backward.argtypes = [vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, pp, vp, vp]
         lib.esac_hip_backward_batch.argtypes = [vp, i32, vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_float, C.c_float, C.c_float,
                                                 pp, vp, vp]
+        lib.esac_hip_backward_batch_cams.argtypes = [vp, i32, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_float, C.c_float,
+                                                     C.c_float, pp, vp, vp]
         lib.esac_hip_read.argtypes = [vp, i32, vp, C.c_size_t]
         lib.esac_hip_write_hyps.argtypes = [vp, vp, i32]
         lib.esac_hip_phase_ms.argtypes = [vp, vp]
@@ -232,19 +272,25 @@ class Engine:
         self._keep = (sc, ha)  # keep inputs alive until the (possibly asynchronous) kernels have run
         return self._host_np.copy() if want_host else None
 
-    def forward_batch(self, scene_coords, hyp_assign, params, scores_out=None, result_out=None, want_host=True):
+    def forward_batch(self, scene_coords, hyp_assign, params, scores_out=None, result_out=None, want_host=True, cams=None):
         """B frames per launch set. scene_coords [B,E,3,H,W] (or [E,3,H,W] shared by all frames), hyp_assign [B,N];
-        `params` describes one frame, frame b uses call + b. Returns np.float64 [B,32] (or None)."""
+        `params` describes one frame, frame b uses call + b. Returns np.float64 [B,32] (or None).
+        cams: None (every frame uses the shift, focal length and principal point of `params`) or B records (make_cams):
+        frame b uses cams[b] and the five fields of `params` are ignored (esac_hip_forward_batch_cams)."""
         sc = scene_coords if scene_coords.is_cuda else scene_coords.to(self.device, non_blocking=True)
         ha = hyp_assign if hyp_assign.is_cuda else hyp_assign.to(self.device, non_blocking=True)
         sc, ha = sc.contiguous(), ha.contiguous()
         B = int(ha.shape[0])
         stride = int(sc.stride(0)) if sc.dim() == 5 else 0
         host = np.zeros((B, RES_DOUBLES), np.float64) if want_host else None
-        self._call(self.lib.esac_hip_forward_batch, B, sc.data_ptr(), stride, ha.data_ptr(), C.byref(params), self._stream(),
-                   scores_out.data_ptr() if scores_out is not None else None,
-                   result_out.data_ptr() if result_out is not None else None,
-                   host.ctypes.data if want_host else None)
+        outs = (scores_out.data_ptr() if scores_out is not None else None,
+                result_out.data_ptr() if result_out is not None else None, host.ctypes.data if want_host else None)
+        if cams is None:
+            self._call(self.lib.esac_hip_forward_batch, B, sc.data_ptr(), stride, ha.data_ptr(), C.byref(params), self._stream(), *outs)
+        else:
+            cams = _cams_arg(cams, B, "esac.forward_batch")  # (the library copies the table before it returns)
+            self._call(self.lib.esac_hip_forward_batch_cams, B, sc.data_ptr(), stride, ha.data_ptr(), C.byref(params),
+                       cams.ctypes.data, self._stream(), *outs)
         self._keep = (sc, ha)
         return host
 
@@ -268,11 +314,12 @@ class Engine:
         self._keep = (sc, ha, out_gradients)
         return host
 
-    def backward_batch(self, scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params):
+    def backward_batch(self, scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, cams=None):
         """Training path over B frames in one set of launches (esac_hip_backward_batch). scene_coords [B,E,3,H,W] (or [E,3,H,W]
         shared by all frames), out_gradients float32 [B,E,3,H,W] on this device, contiguous, accumulated into; hyp_assign [B,N];
         gt_poses [B,4,4]. `params` describes one frame, frame b uses call + b. Returns np.float64 [B,4] (one record per frame).
-        An out-of-range device assignment raises after every frame has run; the exception's `records` holds the [B,4] records."""
+        An out-of-range device assignment raises after every frame has run; the exception's `records` holds the [B,4] records.
+        cams: None or B per-frame camera records (make_cams), as in forward_batch (esac_hip_backward_batch_cams)."""
         sc = scene_coords if scene_coords.is_cuda else scene_coords.to(self.device, non_blocking=True)
         ha = hyp_assign if hyp_assign.is_cuda else hyp_assign.to(self.device, non_blocking=True)
         sc, ha = sc.contiguous(), ha.contiguous()
@@ -285,9 +332,16 @@ class Engine:
             raise RuntimeError("esac.backward_batch: gtPoses must hold B 4x4 poses")
         sc_stride = int(sc.stride(0)) if sc.dim() == 5 else 0
         host = np.zeros((B, 4), np.float64)
-        rc = self.lib.esac_hip_backward_batch(
-            self.ctx, B, sc.data_ptr(), sc_stride, out_gradients.data_ptr(), int(out_gradients.stride(0)), ha.data_ptr(),
-            gt.ctypes.data, float(w_rot), float(w_trans), float(loss_cut), C.byref(params), self._stream(), host.ctypes.data)
+        if cams is None:
+            rc = self.lib.esac_hip_backward_batch(
+                self.ctx, B, sc.data_ptr(), sc_stride, out_gradients.data_ptr(), int(out_gradients.stride(0)), ha.data_ptr(),
+                gt.ctypes.data, float(w_rot), float(w_trans), float(loss_cut), C.byref(params), self._stream(), host.ctypes.data)
+        else:
+            cams = _cams_arg(cams, B, "esac.backward_batch")
+            rc = self.lib.esac_hip_backward_batch_cams(
+                self.ctx, B, sc.data_ptr(), sc_stride, out_gradients.data_ptr(), int(out_gradients.stride(0)), ha.data_ptr(),
+                gt.ctypes.data, cams.ctypes.data, float(w_rot), float(w_trans), float(loss_cut), C.byref(params), self._stream(),
+                host.ctypes.data)
         self._keep = (sc, ha, out_gradients)
         if rc != 0:
             err = RuntimeError("esac (HIP): %s [status %d]" % (self.lib.esac_hip_last_error().decode(), rc))
@@ -303,6 +357,16 @@ class Engine:
         shapes = {BUF_BWD_PROBS: ((N,), np.float64), BUF_BWD_LOSSES: ((N,), np.float64), BUF_BWD_REF_HYPS: ((N, 6), np.float64),
                   BUF_BWD_SCORE_GRADS: ((N,), np.float64), BUF_BWD_SLOTS: ((N,), np.int32),
                   BUF_BWD_SLOT_INFO: ((rows, 4), np.int32), BUF_BWD_DLOSS: ((rows, 6), np.float64)}
+        shape, dt = shapes[which]
+        out = np.zeros((int(B),) + shape, dt)
+        _check(self.lib.esac_hip_read(self.ctx, which, out.ctypes.data_as(C.c_void_p), out.nbytes), self.lib)
+        return out
+
+    def read_forward_frames(self, which, B):
+        """BUF_HYPS / _SAMPLE_XY / _TRIES / _SCORES / _INLIER_COUNTS of all B frames of the last batched call, frame-major."""
+        N, H, W = self._shape
+        shapes = {BUF_HYPS: ((N, 6), np.float64), BUF_SAMPLE_XY: ((N, 4, 2), np.int32), BUF_TRIES: ((N,), np.int32),
+                  BUF_SCORES: ((N,), np.float64), BUF_INLIER_COUNTS: ((MAX_REF_STEPS + 1,), np.int32)}
         shape, dt = shapes[which]
         out = np.zeros((int(B),) + shape, dt)
         _check(self.lib.esac_hip_read(self.ctx, which, out.ctypes.data_as(C.c_void_p), out.nbytes), self.lib)
@@ -642,12 +706,61 @@ def forward(sceneCoordinates, hypAssignment, outPose, shiftX, shiftY, focalLengt
     return int(res[RES_EXPERT])
 
 
+_CAM_ARGS = ("shiftX", "shiftY", "focalLength", "ppointX", "ppointY")
+
+
+def _per_frame_cams(who, B, shiftX, shiftY, focalLength, ppointX, ppointY):
+    """The five camera arguments of a batched call: each a scalar (one value for the batch) or a length-B sequence / 1-D tensor /
+    numpy array (one value per frame).  Returns (scalars, cams): all five scalars -> (the five values, None), today's call;
+    otherwise scalars are broadcast and cams is the table of B records (frame 0's values stand in the parameter block).
+    Raises RuntimeError naming the argument; touches no device."""
+    cols, per_frame = [], False
+    for name, v in zip(_CAM_ARGS, (shiftX, shiftY, focalLength, ppointX, ppointY)):
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        if isinstance(v, (list, tuple)):
+            try:
+                v = np.asarray(v, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise RuntimeError("%s: %s must be a number or a sequence of B numbers" % (who, name))
+        if isinstance(v, np.ndarray) and v.ndim > 0:
+            if v.ndim != 1 or v.shape[0] != B:
+                raise RuntimeError("%s: %s must be a scalar or hold one value per frame (%d), found shape %s"
+                                   % (who, name, B, tuple(v.shape)))
+            if v.dtype.kind not in "iuf":
+                raise RuntimeError("%s: %s must be numeric, found dtype %s" % (who, name, v.dtype))
+            per_frame = True
+            col = v.astype(np.float64)
+        else:
+            try:
+                col = np.full(B, float(v), np.float64)
+            except (TypeError, ValueError):
+                raise RuntimeError("%s: %s must be a number or a sequence of B numbers" % (who, name))
+        cols.append(col)
+    if not per_frame:
+        return (shiftX, shiftY, focalLength, ppointX, ppointY), None
+    for name, col in zip(_CAM_ARGS, cols):
+        if not np.all(np.isfinite(col)):
+            raise RuntimeError("%s: %s holds a non-finite value (frame %d)" % (who, name, int(np.flatnonzero(~np.isfinite(col))[0])))
+    for name, col in zip(_CAM_ARGS[:2], cols[:2]):
+        bad = np.flatnonzero((col != np.round(col)) | (np.abs(col) > 2**31 - 1))
+        if bad.size:
+            raise RuntimeError("%s: %s must hold integers within int32 (frame %d: %r)" % (who, name, int(bad[0]), float(col[bad[0]])))
+    bad = np.flatnonzero(~(cols[2] > 0))
+    if bad.size:
+        raise RuntimeError("%s: focalLength must be positive (frame %d: %r)" % (who, int(bad[0]), float(cols[2][bad[0]])))
+    cams = make_cams(cols[0], cols[1], cols[2], cols[3], cols[4])
+    return (int(cols[0][0]), int(cols[1][0]), float(cols[2][0]), float(cols[3][0]), float(cols[4][0])), cams
+
+
 def forward_batch(sceneCoordinates, hypAssignment, outPoses, shiftX, shiftY, focalLength, ppointX, ppointY,
                   inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling):
     """Batched companion of `forward` (new API): sceneCoordinates [B,E,3,H,W] (or [E,3,H,W] shared),
     hypAssignment [B,N] int64, outPoses [B,4,4] float32 written in place; returns the list of winning experts.
     Frame b is what the b-th of B consecutive `forward` calls would compute (discrete outputs identical; poses to the rounding of
-    the LM sums, bit for bit when the single calls refine with teams of 8 like a batch does: include/esac_hip.h)."""
+    the LM sums, bit for bit when the single calls refine with teams of 8 like a batch does: include/esac_hip.h).
+    Each of shiftX, shiftY, focalLength, ppointX, ppointY is a scalar (the whole batch) or a length-B sequence / 1-D tensor /
+    numpy array (frame b uses element b; test sets whose images differ in focal length)."""
     if hypAssignment.dim() != 2 or hypAssignment.dtype != torch.int64:
         raise RuntimeError("esac.forward_batch: hypAssignment must be int64 [B,N]")
     if sceneCoordinates.dtype != torch.float32 or sceneCoordinates.dim() not in (4, 5) or sceneCoordinates.size(-3) != 3:
@@ -657,6 +770,8 @@ def forward_batch(sceneCoordinates, hypAssignment, outPoses, shiftX, shiftY, foc
         raise RuntimeError("esac.forward_batch: outPoses must be float32 [B,4,4]")
     if sceneCoordinates.dim() == 5 and sceneCoordinates.size(0) != B:
         raise RuntimeError("esac.forward_batch: batch sizes of sceneCoordinates and hypAssignment differ")
+    (shiftX, shiftY, focalLength, ppointX, ppointY), cams = _per_frame_cams("esac.forward_batch", B, shiftX, shiftY, focalLength,
+                                                                            ppointX, ppointY)
     eng = engine(sceneCoordinates.device.index if sceneCoordinates.is_cuda else None)
     E, H, W = sceneCoordinates.shape[-4], sceneCoordinates.shape[-2], sceneCoordinates.shape[-1]
     p = eng.make_params(E, H, W, N, shiftX, shiftY, focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha,
@@ -664,7 +779,7 @@ def forward_batch(sceneCoordinates, hypAssignment, outPoses, shiftX, shiftY, foc
                         max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"])
     _state["call"] += B
     scores = torch.empty(B, N, dtype=torch.float64, device=eng.device)
-    res = eng.forward_batch(sceneCoordinates, hypAssignment, p, scores_out=scores)
+    res = eng.forward_batch(sceneCoordinates, hypAssignment, p, scores_out=scores, cams=cams)
     outPoses.copy_(torch.from_numpy(res[:, RES_POSE:RES_POSE + 16].astype(np.float32).reshape(B, 4, 4)))
     _state["last"] = {"scores": scores, "result": res}
     return [int(v) for v in res[:, RES_EXPERT]]
@@ -714,7 +829,9 @@ def backward_batch(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLoss
     outGradients float32 [B,E,3,H,W] accumulated into in place, hypAssignment [B,N] int64, gtPoses [B,4,4] float32.  Returns
     the list of the B expected losses.  Frame b is what the b-th of B consecutive `backward` calls would compute (the same
     hypotheses, slots and losses; the gradient bit for bit when the single calls refine their slots with one workgroup each:
-    include/esac_hip.h).  Advances the call counter by B."""
+    include/esac_hip.h).  Advances the call counter by B.
+    Each of shiftX, shiftY, focalLength, ppointX, ppointY is a scalar (the whole batch) or a length-B sequence / 1-D tensor /
+    numpy array: frame b uses element b (a training mini-batch: one random shift and one focal length per image)."""
     if not all(isinstance(t, torch.Tensor) for t in (sceneCoordinates, outGradients, hypAssignment, gtPoses)):
         raise RuntimeError("esac.backward_batch: every tensor argument must be a torch.Tensor")
     if hypAssignment.dtype != torch.int64 or hypAssignment.dim() != 2 or hypAssignment.numel() == 0:
@@ -733,6 +850,8 @@ def backward_batch(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLoss
         lo, hi = int(hypAssignment.min()), int(hypAssignment.max())
         if lo < 0 or hi >= E:
             raise RuntimeError("esac.backward_batch: hypAssignment values must lie in [0,%d), found [%d,%d]" % (E, lo, hi))
+    (shiftX, shiftY, focalLength, ppointX, ppointY), cams = _per_frame_cams("esac.backward_batch", B, shiftX, shiftY, focalLength,
+                                                                             ppointX, ppointY)
     eng = engine(sceneCoordinates.device.index if sceneCoordinates.is_cuda else None)
     p = eng.make_params(E, H, W, N, shiftX, shiftY, focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha,
                         inlierBeta, maxReproj, subSampling, seed=_state["seed"], call=_state["call"],
@@ -741,7 +860,7 @@ def backward_batch(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLoss
     in_place = outGradients.is_cuda and outGradients.is_contiguous() and outGradients.device == eng.device
     grads = outGradients if in_place else outGradients.to(eng.device).contiguous()
     out = eng.backward_batch(sceneCoordinates, grads, hypAssignment, gtPoses.detach().cpu().numpy(), wLossRot, wLossTrans,
-                             lossCut, p)
+                             lossCut, p, cams=cams)
     if not in_place:
         outGradients.copy_(grads)  # the accumulated tensors back into the caller's (CPU or strided) storage
     _state["last"] = {"backward": out}

@@ -184,8 +184,20 @@ __device__ __forceinline__ void block_sum28(double (&v)[NV], double* s_part, dou
 // Batched calls (esac_hip_forward_batch): workgroups with blockIdx.y = b serve frame b.  Every per-call
 // buffer is laid out frame-major, so a frame's view is the same KArgs with offset pointers; frame b draws
 // the RNG streams of call + b, which makes a batch bit-identical to B sequential calls.
+// A batch with per-frame cameras (KArgs::cams): the frame's shift, focal length and principal point replace the inline fields
+// here, so every kernel reads the five values AFTER its frame's view is applied.  Frame 0 returns early: the host puts record 0
+// into the inline fields (make_args), which also serves the kernels and launch paths that never take a frame's view.
+__device__ __forceinline__ void frame_cam(KArgs& a, int fr) {
+    const FrameCam c = a.cams[fr];
+    a.shift_x = c.shift_x;
+    a.shift_y = c.shift_y;
+    a.focal = c.focal;
+    a.ppx = c.ppx;
+    a.ppy = c.ppy;
+}
 __device__ __forceinline__ void frame_view(KArgs& a, int fr) {
     if (fr == 0) return;
+    if (a.cams) frame_cam(a, fr);
     const size_t N = (size_t)a.N, P = (size_t)a.H * a.W, f = (size_t)fr;
     a.sc += f * a.sc_frame_stride;
     a.assign += f * N;

@@ -9,6 +9,7 @@
 #include <sched.h>
 #include <time.h>
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -74,6 +75,7 @@ struct esac_hip_ctx {
     int capN = 0, capP = 0, capB = 0;  // capN / capP count elements over ALL frames of a batch
     KArgs ws{};  // only the workspace pointers are kept here
     int lastN = 0, lastH = 0, lastW = 0;
+    int lastB = 1;  // frames of the most recent launch set (esac_hip_read: B x the single-frame size reads the per-frame forward buffers of all of them)
     bool timing = false;
     int timing_period = 1;       // record the phase events / device-side stamps on every timing_period-th forward call
     long long timing_calls = 0;  // forward calls since timing was enabled
@@ -116,6 +118,11 @@ struct esac_hip_ctx {
     int last_bwd_batch_cap = 0;               // slots per frame of the last launch set when it was a batch's (0: a single call)
     double* h_gt = nullptr;                   // pinned staging of the per-frame ground truth [ESAC_MAX_BATCH,22]
     double* d_gt = nullptr;                   // ... and its device copy
+    // per-frame cameras of a batch (esac_hip_forward_batch_cams / esac_hip_backward_batch_cams)
+    FrameCam* h_cams = nullptr;               // pinned staging [ESAC_MAX_BATCH]: the caller's array is free when the call returns
+    FrameCam* d_cams = nullptr;               // ... and the table the kernels read (KArgs::cams)
+    hipEvent_t cams_ev = nullptr;             // recorded behind the most recent upload: the staging is rewritten only after it
+    bool cams_queued = false;
     float4* sc4 = nullptr;  // packed copy of the maps for the sampler (ensure_pack_ws)
     long long sc4_cells = 0;
     // tile-stationary score workspace (ensure_tiled_ws)
@@ -270,6 +277,9 @@ extern "C" int esac_hip_destroy(esac_hip_ctx* c) {
     free_ws(c);
     free_bws(c);
     if (c->d_gt) (void)hipFree(c->d_gt);
+    if (c->d_cams) (void)hipFree(c->d_cams);
+    if (c->h_cams) (void)hipHostFree(c->h_cams);
+    if (c->cams_ev) (void)hipEventDestroy(c->cams_ev);
     if (c->h_gt) (void)hipHostFree(c->h_gt);
     if (c->sc4) (void)hipFree(c->sc4);
     drop_comm(c);
@@ -435,9 +445,30 @@ static int ensure_tiled_ws(esac_hip_ctx* c, int N, int P, int E) {
     return 0;
 }
 
+// One camera's checks (cam_frame >= 0: a record of a per-frame table, the error names the frame)
+static int check_cam(const esac_hip_params* p, int shift_x, int shift_y, float focal, int cam_frame) {
+    char where[32] = "";
+    if (cam_frame >= 0) snprintf(where, sizeof(where), " in frame %d", cam_frame);
+    {   // pixel centres col*sub + sub/2 - shift (esac_util.h:64-66) are formed in int32 on the device
+        const int64_t lim = 0x7fffffffLL, half = p->sub_sampling / 2;
+        const int64_t xs[4] = {half - shift_x, (int64_t)(p->W - 1) * p->sub_sampling + half - shift_x,
+                               half - shift_y, (int64_t)(p->H - 1) * p->sub_sampling + half - shift_y};
+        for (int64_t v : xs)
+            if (v > lim || v < -lim) return fail(-4, "pixel positions overflow int32 (subSampling=%d, shift=(%d,%d))%s", p->sub_sampling, shift_x, shift_y, where);
+    }
+    if (!(focal > 0)) return fail(-4, "focal length must be positive%s", where);
+    return 0;
+}
+static esac_hip_params with_cam(const esac_hip_params& p, const esac_hip_frame_cam& cam) {
+    esac_hip_params q = p;
+    q.shift_x = cam.shift_x; q.shift_y = cam.shift_y;
+    q.focal = cam.focal; q.ppx = cam.ppx; q.ppy = cam.ppy;
+    return q;
+}
+
 // Validation: what the reference leaves to accessor<>() / OpenCV asserts.
 static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign, const esac_hip_params* p, KArgs* out,
-                     int B = 1, long long sc_frame_stride = 0) {
+                     int B = 1, long long sc_frame_stride = 0, int cam_frame = -1) {
     if (!c) return fail(-1, "null context");
     if (!p) return fail(-1, "null params");
     if (!d_sc || !d_assign) return fail(-1, "null scene-coordinate or assignment pointer");
@@ -447,14 +478,7 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
     if ((int64_t)p->H * p->W > (int64_t)1 << 28 || p->H > 65535 || p->W > 65535)
         return fail(-4, "grid %dx%d too large (at most 65535 rows / columns, 2^28 cells)", p->H, p->W);
     if (p->sub_sampling <= 0) return fail(-4, "subSampling=%d must be positive", p->sub_sampling);
-    {   // pixel centres col*sub + sub/2 - shift (esac_util.h:64-66) are formed in int32 on the device
-        const int64_t lim = 0x7fffffffLL, half = p->sub_sampling / 2;
-        const int64_t xs[4] = {half - p->shift_x, (int64_t)(p->W - 1) * p->sub_sampling + half - p->shift_x,
-                               half - p->shift_y, (int64_t)(p->H - 1) * p->sub_sampling + half - p->shift_y};
-        for (int64_t v : xs)
-            if (v > lim || v < -lim) return fail(-4, "pixel positions overflow int32 (subSampling=%d, shift=(%d,%d))", p->sub_sampling, p->shift_x, p->shift_y);
-    }
-    if (!(p->focal > 0)) return fail(-4, "focal length must be positive");
+    if (int rc_cam = check_cam(p, p->shift_x, p->shift_y, p->focal, cam_frame)) return rc_cam;
     const int P = p->H * p->W;
     if (B < 1 || B > ESAC_MAX_BATCH) return fail(-4, "batch size %d outside [1,%d]", B, ESAC_MAX_BATCH);
     int rc = ensure_ws(c, p->N, P, B);
@@ -473,6 +497,7 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
     }
     a.frames = B;
     a.sc_frame_stride = sc_frame_stride;
+    a.cams = nullptr;  // (the _cams entry points set it after stage_cams)
     a.sc = d_sc;
     a.assign = d_assign;
     a.E = p->E; a.H = p->H; a.W = p->W; a.N = p->N;
@@ -508,7 +533,33 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
     // side of tau under fp32, which moves a score by alpha / (H*W); on small grids that exceeds alpha * 1e-3
     a.margin = p->rescore_margin > 0 ? p->rescore_margin : fabsf(p->inlier_alpha) * (ESAC_DEFAULT_MARGIN + 2.0f / (float)P);
     c->lastN = p->N; c->lastH = p->H; c->lastW = p->W;
+    c->lastB = B;
     *out = a;
+    return 0;
+}
+
+// Per-frame cameras of a batch: every record checked like a single call's camera (p: the call's parameters, already validated by
+// make_args with record 0), then staged in pinned memory of the context's own and uploaded on `s` -- once per call; chunks and
+// re-runs offset the device pointer.  The staging is rewritten only after the previous upload has left it (an asynchronous
+// forward batch may still have its copy queued); the device table is rewritten in stream order behind its last readers.
+static int stage_cams(esac_hip_ctx* c, const esac_hip_params* p, const esac_hip_frame_cam* h_cams, int B, hipStream_t s) {
+    static_assert(sizeof(esac_hip_frame_cam) == sizeof(FrameCam) && offsetof(esac_hip_frame_cam, focal) == offsetof(FrameCam, focal) &&
+                  offsetof(esac_hip_frame_cam, ppy) == offsetof(FrameCam, ppy), "esac_hip_frame_cam is the device record");
+    for (int b = 0; b < B; b++)
+        if (int rc = check_cam(p, h_cams[b].shift_x, h_cams[b].shift_y, h_cams[b].focal, b)) return rc;
+    if (!c->h_cams) {
+        HIP_OK(hipHostMalloc((void**)&c->h_cams, (size_t)ESAC_MAX_BATCH * sizeof(FrameCam), hipHostMallocDefault));
+        HIP_OK(hipMalloc((void**)&c->d_cams, (size_t)ESAC_MAX_BATCH * sizeof(FrameCam)));
+        HIP_OK(hipEventCreateWithFlags(&c->cams_ev, hipEventDisableTiming));
+    }
+    if (c->cams_queued) {
+        HIP_OK(hipEventSynchronize(c->cams_ev));
+        c->cams_queued = false;
+    }
+    memcpy(c->h_cams, h_cams, (size_t)B * sizeof(FrameCam));
+    HIP_OK(hipMemcpyAsync(c->d_cams, c->h_cams, (size_t)B * sizeof(FrameCam), hipMemcpyHostToDevice, s));
+    HIP_OK(hipEventRecord(c->cams_ev, s));
+    c->cams_queued = true;
     return 0;
 }
 
@@ -632,13 +683,22 @@ static int wait_record(esac_hip_ctx* c, hipStream_t s, int B, double want, const
 
 static int forward_impl(esac_hip_ctx* c, const float* d_sc, long long sc_frame_stride, const int64_t* d_assign,
                         const esac_hip_params* p, int B, void* stream, double* d_scores_out, double* d_result_out,
-                        double* h_result_out) {
+                        double* h_result_out, const esac_hip_frame_cam* h_cams = nullptr) {
     if (!c) return fail(-1, "null context");
     const double t_entry = now_ns();
     DeviceGuard guard(c->device);
     KArgs a;
-    int rc = make_args(c, d_sc, d_assign, p, &a, B, sc_frame_stride);
+    esac_hip_params p0;
+    if (h_cams && p) {  // the inline fields carry record 0 (device_common.hpp:frame_view)
+        p0 = with_cam(*p, h_cams[0]);
+        p = &p0;
+    }
+    int rc = make_args(c, d_sc, d_assign, p, &a, B, sc_frame_stride, h_cams ? 0 : -1);
     if (rc) return rc;
+    if (h_cams && B > 1) {  // (one frame: record 0 is the whole table)
+        if ((rc = stage_cams(c, p, h_cams, B, (hipStream_t)stream))) return rc;
+        a.cams = c->d_cams;
+    }
     if (c->team_latched_off && ++c->solo_since_latch > ESAC_TEAM_REARM_CALLS) {  // (blocking or not: every forward call counts)
         c->team_latched_off = false;               // try a team again; one more time-out latches at once
         c->team_strikes = ESAC_TEAM_STRIKES - 1;
@@ -1026,7 +1086,14 @@ extern "C" int esac_hip_forward(esac_hip_ctx* c, const float* d_sc, const int64_
 extern "C" int esac_hip_forward_batch(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride,
                                       const int64_t* d_assign, const esac_hip_params* p, void* stream,
                                       double* d_scores_out, double* d_result_out, double* h_result_out) {
-    return forward_impl(c, d_sc, (long long)sc_frame_stride, d_assign, p, B, stream, d_scores_out, d_result_out, h_result_out);
+    return esac_hip_forward_batch_cams(c, B, d_sc, sc_frame_stride, d_assign, p, nullptr, stream, d_scores_out, d_result_out, h_result_out);
+}
+
+extern "C" int esac_hip_forward_batch_cams(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride,
+                                           const int64_t* d_assign, const esac_hip_params* p, const esac_hip_frame_cam* h_cams,
+                                           void* stream, double* d_scores_out, double* d_result_out, double* h_result_out) {
+    if (h_cams && (B < 1 || B > ESAC_MAX_BATCH)) return fail(-4, "batch size %d outside [1,%d]", B, ESAC_MAX_BATCH);  // (before h_cams[0] is read)
+    return forward_impl(c, d_sc, (long long)sc_frame_stride, d_assign, p, B, stream, d_scores_out, d_result_out, h_result_out, h_cams);
 }
 
 // ---------------------------------------------------------------- training path
@@ -1255,6 +1322,16 @@ extern "C" int esac_hip_backward(esac_hip_ctx* c, const float* d_sc, float* d_ou
 extern "C" int esac_hip_backward_batch(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
                                        int64_t grad_frame_stride, const int64_t* d_assign, const float* h_gt_poses, float w_loss_rot,
                                        float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* h_out) {
+    return esac_hip_backward_batch_cams(c, B, d_sc, sc_frame_stride, d_out_gradients, grad_frame_stride, d_assign, h_gt_poses, nullptr,
+                                        w_loss_rot, w_loss_trans, loss_cut, p, stream, h_out);
+}
+
+// ... with a camera per frame (h_cams: host, B records; NULL: the five fields of p for every frame).  Record b0 of a chunk goes
+// into the chunk's inline fields, the table pointer is offset by the chunk's first frame like gt_frames and the call counter.
+extern "C" int esac_hip_backward_batch_cams(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
+                                            int64_t grad_frame_stride, const int64_t* d_assign, const float* h_gt_poses,
+                                            const esac_hip_frame_cam* h_cams, float w_loss_rot, float w_loss_trans, float loss_cut,
+                                            const esac_hip_params* p, void* stream, double* h_out) {
     if (!c) return fail(-1, "null context");
     if (!p) return fail(-1, "null params");
     if (!d_sc || !d_out_gradients || !d_assign || !h_gt_poses)
@@ -1284,8 +1361,14 @@ extern "C" int esac_hip_backward_batch(esac_hip_ctx* c, int B, const float* d_sc
     }
     // validation of the parameters (make_args) before anything is launched: the caller's gradients stay untouched on an error
     KArgs a;
-    int rc = make_args(c, d_sc, d_assign, p, &a, 1, 0);
-    if (rc) return rc;
+    int rc;
+    if (h_cams) {
+        const esac_hip_params p0 = with_cam(*p, h_cams[0]);
+        if ((rc = make_args(c, d_sc, d_assign, &p0, &a, 1, 0, 0))) return rc;
+        if ((rc = stage_cams(c, &p0, h_cams, B, s))) return rc;  // (checks every record before the first launch)
+    } else if ((rc = make_args(c, d_sc, d_assign, p, &a, 1, 0))) {
+        return rc;
+    }
     HIP_OK(hipMemcpyAsync(c->d_gt, c->h_gt, (size_t)B * 22 * sizeof(double), hipMemcpyHostToDevice, s));
     const int N = p->N, P = p->H * p->W, worst = bwd_rows(N);
     const long long per_slot = 2LL * P + 2LL * 3 * P * (long long)sizeof(double) +
@@ -1299,9 +1382,10 @@ extern "C" int esac_hip_backward_batch(esac_hip_ctx* c, int B, const float* d_sc
     bool any_bad = false;
     for (int b0 = 0; b0 < B;) {
         int nb = chunk_frames(cap, B - b0);
-        esac_hip_params pc = *p;
+        esac_hip_params pc = h_cams ? with_cam(*p, h_cams[b0]) : *p;
         pc.call = p->call + (uint64_t)b0;
         if ((rc = make_args(c, d_sc + (size_t)b0 * sc_frame_stride, d_assign + (size_t)b0 * N, &pc, &a, nb, sc_frame_stride))) return rc;
+        if (h_cams) a.cams = c->d_cams + b0;
         a.tstamps = nullptr;
         c->rt32_stale = false;
         mark_sampling(c, a);
@@ -1501,6 +1585,10 @@ extern "C" int esac_hip_read(esac_hip_ctx* c, int which, void* h_dst, size_t byt
                            which == ESAC_BUF_BWD_SCORE_GRADS || which == ESAC_BUF_BWD_SLOTS || which == ESAC_BUF_BWD_SLOT_INFO ||
                            which == ESAC_BUF_BWD_DLOSS;
     if (per_frame && c->last_bwd_frames > 1 && want > 0 && bytes == want * (size_t)c->last_bwd_frames) want = bytes;
+    // ... and after a batched call the sampler's and the refinement's per-frame buffers hold its frames frame-major
+    const bool fwd_per_frame = which == ESAC_BUF_HYPS || which == ESAC_BUF_SAMPLE_XY || which == ESAC_BUF_TRIES || which == ESAC_BUF_SCORES ||
+                               which == ESAC_BUF_INLIER_COUNTS;
+    if (fwd_per_frame && c->lastB > 1 && want > 0 && bytes == want * (size_t)c->lastB) want = bytes;
     if (!src || want == 0) return fail(-6, "esac_hip_read: buffer %d is empty (no call has run yet)", which);
     if (bytes != want) return fail(-7, "esac_hip_read: buffer %d holds %zu bytes, caller asked for %zu", which, want, bytes);
     HIP_OK(hipDeviceSynchronize());

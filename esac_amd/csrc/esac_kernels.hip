@@ -72,9 +72,10 @@ __device__ __forceinline__ bool cannot_pass(double reproj2, double tau) {
 // the 4 cells of try t of hypothesis gh, their scene points and pixel positions.  With the planar [E,3,H,W] layout a
 // cell is three 4-byte reads from three cache lines; when the maps are too large for the caches (KArgs::sc4, see
 // k_pack_cells) the sampler reads one 16-byte (x, y, z, -) record per cell instead.
+// (shift_x, shift_y: the frame's -- a.shift_x, a.shift_y wherever the frame's view has been applied)
 __device__ __forceinline__ void gather_sample(const KArgs& a, const float* __restrict__ map, int P, const Philox& rng, uint32_t gh,
                                               uint32_t t, int (&cx)[4], int (&cy)[4], V3 (&Pt)[4], float (&Pf)[4][3],
-                                              double (&mu)[4], double (&mv)[4]) {
+                                              double (&mu)[4], double (&mv)[4], int shift_x, int shift_y) {
     draw_cells(rng, gh, t, a.W, a.H, cx, cy);
     const float4* __restrict__ map4 = a.sc4 ? a.sc4 + (size_t)(map - a.sc) / 3 : nullptr;  // (map - sc) / 3 = expert * P
 #pragma unroll
@@ -89,9 +90,14 @@ __device__ __forceinline__ void gather_sample(const KArgs& a, const float* __res
             Pf[j][2] = map[2 * P + idx];
         }
         Pt[j] = V3{(double)Pf[j][0], (double)Pf[j][1], (double)Pf[j][2]};
-        mu[j] = (double)cell_px(a, cx[j]);
-        mv[j] = (double)cell_py(a, cy[j]);
+        mu[j] = (double)(float)(cx[j] * a.sub + a.sub / 2 - shift_x);  // cell_px / cell_py
+        mv[j] = (double)(float)(cy[j] * a.sub + a.sub / 2 - shift_y);
     }
+}
+__device__ __forceinline__ void gather_sample(const KArgs& a, const float* __restrict__ map, int P, const Philox& rng, uint32_t gh,
+                                              uint32_t t, int (&cx)[4], int (&cy)[4], V3 (&Pt)[4], float (&Pf)[4][3],
+                                              double (&mu)[4], double (&mv)[4]) {
+    gather_sample(a, map, P, rng, gh, t, cx, cy, Pt, Pf, mu, mv, a.shift_x, a.shift_y);
 }
 
 // planar [E,3,H,W] -> [E,H*W] records (x, y, z, 0): one coalesced pass (12 B read, 16 B written per cell), paid once per
@@ -587,13 +593,22 @@ __global__ __launch_bounds__(64) void k_sample_decide(KArgs a0) {
         const int P = a0.H * a0.W;
         const float* __restrict__ map = sc + (size_t)e * 3 * P;
         const Philox rng(a0.seed, a0.call + (uint64_t)fr);
-        const Cam cam = make_cam(a0);
+        // ... and its camera: the one kernel in which the frame differs from lane to lane, so a batch with per-frame cameras
+        // reads the record per lane here (a 32-byte load per listed try; nothing when the table is null)
+        Cam cam = make_cam(a0);
+        int shift_x = a0.shift_x, shift_y = a0.shift_y;
+        if (a0.cams) {
+            const FrameCam fc = a0.cams[fr];
+            cam = Cam{(double)fc.focal, (double)fc.focal, (double)fc.ppx, (double)fc.ppy};
+            shift_x = fc.shift_x;
+            shift_y = fc.shift_y;
+        }
         const uint32_t gh = (uint32_t)global_hyp(a0, h);
         int cx[4], cy[4];
         V3 Pt[4];
         float Pf[4][3];
         double mu[4], mv[4], Rp[9], Tp[3], reproj2 = 0;
-        gather_sample(a0, map, P, rng, gh, (uint32_t)t, cx, cy, Pt, Pf, mu, mv);
+        gather_sample(a0, map, P, rng, gh, (uint32_t)t, cx, cy, Pt, Pf, mu, mv, shift_x, shift_y);
         bool solved;
         if (quad) {  // the four lanes of this entry replay p3p_4pt's scan over the candidates (k_sample: same rule, same NaN behaviour)
             const int lane = threadIdx.x, root = lane & 3, quad0 = lane & ~3;

@@ -101,6 +101,15 @@ struct BwdArgs {
 
 constexpr int ESAC_SPEC_CNT_FAN = 32, ESAC_SPEC_CNT_STRIDE = 32;  // counters of the second level; ints between two counters (128 bytes)
 constexpr int ESAC_SPEC_CNT_INTS = ESAC_SPEC_CNT_STRIDE * (1 + ESAC_SPEC_CNT_FAN);
+// One frame's camera in a batch with per-frame cameras (= esac_hip_frame_cam, include/esac_hip.h): 32 bytes, so that a frame's
+// record is one aligned scalar load (s_load_dwordx8) at an address that depends on the workgroup's frame only.
+struct FrameCam {
+    int shift_x, shift_y;
+    float focal, ppx, ppy;
+    int pad_[3];
+};
+static_assert(sizeof(FrameCam) == 32, "one aligned 32-byte record per frame");
+
 struct KArgs {
     // inputs (device)
     const float* sc;        // [E,3,H,W]
@@ -204,6 +213,8 @@ struct KArgs {
     // batched calls: frame b = blockIdx.y works on its own slice of every buffer (device_common.hpp:frame_view)
     int frames;                 // B >= 1
     long long sc_frame_stride;  // elements between the coordinate tensors of consecutive frames
+    const FrameCam* cams;       // per-frame cameras [B] (esac_hip_*_batch_cams), or null: every frame uses the inline shift_x .. ppy.
+                                // When set, the inline fields hold record 0 (frame_view resolves the others)
     BwdArgs bwd;                // training path only
 };
 

@@ -215,3 +215,91 @@ def train_step(image, gt_pose, gating, experts, focal_length, hypotheses=256, th
         torch.autograd.backward(tensors, grads)
     return dict(loss=loss, e_hyps=e_hyps, e_hist=e_hist, prediction=prediction, prediction_gradients=prediction_gradients,
                 gating_log_probs=gating_log_probs, pad=(pad_x, pad_y))
+
+
+def train_batch(images, gt_poses, gating, experts, focal_lengths, hypotheses=256, threshold=10.0, inlier_alpha=100.0,
+                inlier_beta=0.5, max_reprojection=100.0, subsample=8, weight_rot=1.0, weight_trans=100.0, loss_cut=100.0,
+                max_experts=-1, expert_selection=False, shifts=None, e_hyps=None, generator=None):
+    """The mini-batch form of `train_step`: B images through ONE `esac.backward_batch` with a shift and a focal length per
+    image (train_esac.py:112 reads the focal length per image, :125 draws a new shift for every image), up to and including
+    one `torch.autograd.backward`.
+
+    images [B,3,H,W]; gt_poses [B,4,4]; focal_lengths: B numbers (or one for all).  gating(images) -> log-probabilities [B,E];
+    experts[e](images) -> [B,3,H/s,W/s].  Every image is padded by its own shift (`shifts`: B pairs, or drawn per image within
+    +-subsample/2 -- from `generator` when one is given, else from Python's `random` like `random_shift`), the gating runs once
+    on the batch, the hypothesis assignment is drawn per frame on the device (or given: `e_hyps` [B,N]), and every expert that
+    is active in at least one frame runs once on the batch: the rows of frames in which it is inactive are never read by the
+    kernels and receive a zero gradient.  Only the B x E activity flags and the B losses reach the host.
+    Returns dict(losses (list of B floats), e_hyps [B,N], e_hist [B,E], prediction [B,E,3,h,w], prediction_gradients,
+    gating_log_probs [B,E], pads (list of B pairs))."""
+    dev = images.device
+    B, E = int(images.size(0)), len(experts)
+    pp_x = float(images.size(3) / 2)
+    pp_y = float(images.size(2) / 2)
+    pred_w = math.ceil(images.size(3) / subsample)
+    pred_h = math.ceil(images.size(2) / subsample)
+    focals = [float(f) for f in (focal_lengths.tolist() if isinstance(focal_lengths, (torch.Tensor, np.ndarray)) and
+                                 getattr(focal_lengths, "ndim", 0) > 0 else
+                                 focal_lengths if isinstance(focal_lengths, (list, tuple)) else [focal_lengths] * B)]
+    if len(focals) != B:
+        raise RuntimeError("train_batch: focal_lengths must hold one value per image (%d), found %d" % (B, len(focals)))
+    if shifts is None:
+        m = int(subsample / 2)
+        if generator is not None:
+            drawn = torch.randint(-m, m + 1, (B, 2), generator=generator, device=generator.device).cpu().tolist()
+            pads = [(int(x), int(y)) for x, y in drawn]
+        else:
+            import random
+            pads = [(random.randint(-m, m), random.randint(-m, m)) for _ in range(B)]
+    else:
+        pads = [(int(s[0]), int(s[1])) for s in shifts]
+        if len(pads) != B:
+            raise RuntimeError("train_batch: shifts must hold one pair per image (%d), found %d" % (B, len(pads)))
+    images = torch.cat([torch.nn.functional.pad(images[b:b + 1], (px, -px, py, -py)) for b, (px, py) in enumerate(pads)])
+    gating_log_probs = gating(images)  # [B,E]
+    expert = None
+    with torch.no_grad():
+        if e_hyps is not None:
+            e_hyps = torch.as_tensor(e_hyps, dtype=torch.int64).to(dev)
+            if e_hyps.dim() != 2 or e_hyps.size(0) != B:
+                raise RuntimeError("train_batch: e_hyps must be [B,N]")
+            if expert_selection:
+                expert = e_hyps[:, :1]
+        else:
+            gating_probs = torch.exp(gating_log_probs).clone()
+            for b in range(B):
+                clamp_probs(gating_probs[b], max_experts)
+            if expert_selection:
+                expert = torch.multinomial(gating_probs, 1, replacement=True, generator=generator)  # [B,1]
+                e_hyps = expert.expand((B, hypotheses))
+            else:
+                e_hyps = torch.multinomial(gating_probs, hypotheses, replacement=True, generator=generator)  # one row of draws per frame
+        e_hist = torch.zeros((B, E), device=dev).scatter_add_(1, e_hyps, torch.ones(e_hyps.shape, device=dev))
+        active = (e_hist > 0).cpu()  # [B,E] flags: all that reaches the host before the call
+        active_any = active.any(dim=0).tolist()
+    outputs = [experts[e](images) if on else torch.zeros((B, 3, pred_h, pred_w), device=dev) for e, on in enumerate(active_any)]
+    prediction = torch.stack(outputs, dim=1)  # [B,E,3,h,w]
+    prediction_gradients = torch.zeros_like(prediction)
+    losses = api.backward_batch(prediction.detach(), prediction_gradients, e_hyps.contiguous(),
+                                torch.as_tensor(np.asarray(gt_poses, np.float32) if not isinstance(gt_poses, torch.Tensor) else gt_poses,
+                                                dtype=torch.float32).cpu(),
+                                weight_rot, weight_trans, loss_cut, [p[0] for p in pads], [p[1] for p in pads], focals, pp_x, pp_y,
+                                threshold, inlier_alpha, inlier_beta, max_reprojection, subsample)
+    # gating gradients, per frame: REINFORCE-style, loss per drawn hypothesis (train_esac.py:171-177)
+    loss_t = torch.tensor(losses, device=dev, dtype=torch.float32)
+    if expert_selection:
+        gating_grads = torch.zeros_like(gating_log_probs)
+        gating_grads.scatter_(1, expert, loss_t.unsqueeze(1).to(gating_log_probs.dtype))
+    else:
+        gating_grads = (loss_t.unsqueeze(1) * e_hist).to(gating_log_probs.dtype)
+    tensors, grads = [], []
+    if prediction.requires_grad:
+        tensors.append(prediction)
+        grads.append(prediction_gradients)
+    if gating_log_probs.requires_grad:
+        tensors.append(gating_log_probs)
+        grads.append(gating_grads)
+    if tensors:
+        torch.autograd.backward(tensors, grads)
+    return dict(losses=losses, e_hyps=e_hyps, e_hist=e_hist, prediction=prediction, prediction_gradients=prediction_gradients,
+                gating_log_probs=gating_log_probs, pads=pads)

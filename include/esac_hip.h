@@ -67,6 +67,15 @@ typedef struct esac_hip_params {
                                  its first map so that the record carries what esac.cpp:189 returns; 0 otherwise */
 } esac_hip_params;
 
+/* One frame's camera in a batch whose frames differ in shift, focal length or principal point (esac_hip_forward_batch_cams,
+ * esac_hip_backward_batch_cams): the five per-image values of esac_hip_params, padded to 32 bytes (one aligned record per frame
+ * on the device).  The padding is ignored. */
+typedef struct esac_hip_frame_cam {
+    int32_t shift_x, shift_y; /* esac.cpp:67-68: the image's random shift (training) or 0 */
+    float focal, ppx, ppy;    /* esac.cpp:69-71 */
+    int32_t reserved[3];
+} esac_hip_frame_cam;
+
 /* esac_hip_forward / _batch: score EVERY hypothesis in the reference's mixed float/double arithmetic
  * (esac_util.h:235-260, 292-360) instead of ranking with the fp32 stream and re-scoring only the contenders.
  * The score vector, ESAC_RES_PROB and ESAC_RES_ENTROPY are then the reference's own values (softMax / entropy,
@@ -220,6 +229,20 @@ int esac_hip_forward_batch(esac_hip_ctx* ctx, int B, const float* d_scene_coords
                            double* d_scores_out, double* d_result_out, double* h_result_out);
 
 /*
+ * esac_hip_forward_batch with a camera per frame: h_cams = HOST array of B records, frame b is computed with h_cams[b]'s
+ * shift_x, shift_y, focal, ppx, ppy and the five fields of p are ignored; everything else in p stays one value per batch.
+ * Frame b then equals esac_hip_forward with p's five fields replaced by h_cams[b] and call p->call + b (same routes, same
+ * bits as described above).  h_cams == NULL is esac_hip_forward_batch exactly.
+ * Every record is checked like a single call's camera (focal > 0, pixel positions within int32) before anything is launched;
+ * the error (-4) names the first offending frame.  The table is copied into pinned memory the context owns and uploaded on
+ * `stream` into a context-owned device buffer that only grows: the caller's array may be reused as soon as the call returns,
+ * also for an asynchronous call (h_result_out == NULL).
+ */
+int esac_hip_forward_batch_cams(esac_hip_ctx* ctx, int B, const float* d_scene_coords, int64_t sc_frame_stride,
+                                const int64_t* d_hyp_assign, const esac_hip_params* p, const esac_hip_frame_cam* h_cams,
+                                void* stream, double* d_scores_out, double* d_result_out, double* h_result_out);
+
+/*
  * Multi-GPU exchange (new; the reference has no multi-device path): d_records = `world` result records of
  * ESAC_RES_DOUBLES doubles each (device), e.g. the tail of the all-reduced buffer [N scores | world records] with
  * all-zero records for ranks without hypotheses (ESAC_RES_VALID marks real ones).  Picks the global winner -- highest
@@ -318,6 +341,19 @@ int esac_hip_backward_batch(esac_hip_ctx* ctx, int B, const float* d_scene_coord
                             const float* h_gt_poses, float w_loss_rot, float w_loss_trans, float loss_cut,
                             const esac_hip_params* p, void* stream, double* h_out);
 
+/*
+ * esac_hip_backward_batch with a camera per frame (the training loop draws a new random shift for every image and reads the
+ * focal length per image): h_cams = HOST array of B records as in esac_hip_forward_batch_cams, the five fields of p are ignored.
+ * Frame b is the esac_hip_backward call with h_cams[b]'s camera and call p->call + b, bit for bit under the conditions above.
+ * Chunks of a batch beyond the workspace budget and the re-run after a slot overflow keep frame b with record b.  A bad record
+ * (focal <= 0, pixel positions beyond int32) is rejected with -4 naming the frame before anything is launched: the gradients
+ * stay untouched.  h_cams == NULL is esac_hip_backward_batch exactly.
+ */
+int esac_hip_backward_batch_cams(esac_hip_ctx* ctx, int B, const float* d_scene_coords, int64_t sc_frame_stride,
+                                 float* d_out_gradients, int64_t grad_frame_stride, const int64_t* d_hyp_assign,
+                                 const float* h_gt_poses, const esac_hip_frame_cam* h_cams, float w_loss_rot,
+                                 float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* h_out);
+
 /* The same phases one at a time (asynchronous on `stream`), for stage-wise parity
  * tests and for callers that interleave other work.  Order: sample, score, select, refine. */
 int esac_hip_sample(esac_hip_ctx* ctx, const float* d_scene_coords, const int64_t* d_hyp_assign,
@@ -342,7 +378,9 @@ int esac_hip_score_exact(esac_hip_ctx* ctx, const float* d_scene_coords, const i
  * Out-of-range values never cause an out-of-bounds read: such hypotheses are evaluated against expert 0. */
 int esac_hip_check(esac_hip_ctx* ctx);
 
-/* Stage buffer access (synchronous). `bytes` must match the buffer size for (which, N, H, W). */
+/* Stage buffer access (synchronous). `bytes` must match the buffer size for (which, N, H, W).  After a batched call of B frames
+ * the per-frame buffers ESAC_BUF_HYPS, _SAMPLE_XY, _TRIES, _SCORES and _INLIER_COUNTS also accept B x that size and then return
+ * every frame's, frame-major (the single-frame size reads frame 0). */
 int esac_hip_read(esac_hip_ctx* ctx, int which, void* h_dst, size_t bytes);
 int esac_hip_write_hyps(esac_hip_ctx* ctx, const double* h_hyps, int N);
 
