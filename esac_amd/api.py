@@ -53,6 +53,7 @@ ABI_VERSION = 6
 FLAG_EXACT_SCORES, FLAG_SCORE_TILED, FLAG_SCORE_STREAM, FLAG_PACK_MAPS, FLAG_EXACT_SAMPLING, FLAG_SCORES_BY_INDEX = 1, 2, 4, 8, 16, 32
 FLAG_AUTO_EXACT = 64
 FLAG_REFINE_SOLO = 128
+FLAG_STRICT_REFERENCE = 256  # the reference's rule in P3P alignment, NaN scores and the LM trial test (include/esac_hip.h)
 WAIT_SPIN, WAIT_YIELD, WAIT_BLOCK = 0, 1, 2
 DEBUG_ERROR_IMAGE, DEBUG_COOP_STALL, DEBUG_TEAM_SPREAD, DEBUG_NO_SPECULATION, DEBUG_SPEC_SECOND_BEST, DEBUG_SPEC_LOSE_CHAIN = 1, 2, 4, 8, 16, 32
 
@@ -225,7 +226,10 @@ class Engine:
     def make_params(self, E, H, W, N, shift_x=0, shift_y=0, focal=525.0, ppx=320.0, ppy=240.0, inlier_thresh=10.0,
                     inlier_alpha=100.0, inlier_beta=0.5, max_reproj=100.0, sub_sampling=8, seed=1305, call=0,
                     max_tries=0, max_ref_steps=-1, hyp_offset=0, rescore_margin=0.0, exact_scores=False, score_shape="auto", pack_maps=False,
-                    exact_sampling=False, scores_by_index=False, expert_base=0, refine_solo=False):
+                    exact_sampling=False, scores_by_index=False, expert_base=0, refine_solo=False, strict_reference=False):
+        if strict_reference and (exact_scores == "auto" or score_shape != "auto"):
+            # (what the C ABI answers with -4: strict mode scores every hypothesis in reference arithmetic)
+            raise ValueError("strict_reference cannot be combined with exact_scores='auto' or score_shape=%r" % (score_shape,))
         p = Params()
         p.E, p.H, p.W, p.N = int(E), int(H), int(W), int(N)
         p.shift_x, p.shift_y = int(shift_x), int(shift_y)
@@ -241,6 +245,8 @@ class Engine:
             {"auto": 0, "tiled": FLAG_SCORE_TILED, "stream": FLAG_SCORE_STREAM}[score_shape] | \
             (FLAG_PACK_MAPS if pack_maps else 0) | (FLAG_EXACT_SAMPLING if exact_sampling else 0) | (FLAG_SCORES_BY_INDEX if scores_by_index else 0) | \
             (FLAG_REFINE_SOLO if refine_solo else 0)
+        if strict_reference:  # implies the two guaranteed routes
+            p.flags |= FLAG_STRICT_REFERENCE | FLAG_EXACT_SCORES | FLAG_EXACT_SAMPLING
         p.expert_base = int(expert_base)
         self._shape = (int(N), int(H), int(W))
         return p
@@ -570,7 +576,7 @@ class Engine:
 # The reference keeps a static RNG whose state advances from call to call
 # (thread_rand.cpp:4-5); here that state is (seed, call counter).
 _state = {"seed": 1305, "call": 0, "engines": {}, "last": None, "max_tries": 0, "max_ref_steps": -1, "fwd_cache": {},
-          "exact_scores": None, "exact_sampling": False}
+          "exact_scores": None, "exact_sampling": False, "strict_reference": False}
 
 
 def set_seed(seed, call=0):
@@ -601,6 +607,19 @@ def set_exact_sampling(on):
     (ESAC_FLAG_EXACT_SAMPLING), the reference's loop try by try (esac_util.h:152-223).  The accepted try is the same either
     way; this is the guaranteed route (several times slower on wrong-expert hypotheses)."""
     _state["exact_sampling"] = bool(on)
+
+
+def set_strict_reference(on):
+    """True: forward() and forward_batch() follow the reference where the default knowingly differs (ESAC_FLAG_STRICT_REFERENCE):
+    Horn / Jacobi alignment in the P3P, NaN scores from non-finite scene coordinates (hypothesis 0 is then refined), the plain
+    CvLevMarq trial test.  Implies exact scores and exact sampling; a verification route, several times slower.  backward() and
+    backward_batch() raise ValueError while it is on: the training path has no strict mode."""
+    _state["strict_reference"] = bool(on)
+
+
+def _no_strict_training(who):
+    if _state["strict_reference"]:
+        raise ValueError("%s: the training path has no strict mode (esac.set_strict_reference(False) first)" % who)
 
 
 def engine(device=None):
@@ -693,6 +712,8 @@ def forward(sceneCoordinates, hypAssignment, outPose, shiftX, shiftY, focalLengt
     p.max_tries, p.max_ref_steps = int(_state["max_tries"]), int(_state["max_ref_steps"])
     p.flags = (FLAG_AUTO_EXACT if _state["exact_scores"] is None else FLAG_EXACT_SCORES if _state["exact_scores"] else 0) | \
         (FLAG_EXACT_SAMPLING if _state["exact_sampling"] else 0)
+    if _state["strict_reference"]:  # (never with FLAG_AUTO_EXACT: strict mode IS the exact routes)
+        p.flags = FLAG_STRICT_REFERENCE | FLAG_EXACT_SCORES | FLAG_EXACT_SAMPLING
     p.seed, p.call = _state["seed"] & (2**64 - 1), _state["call"] & (2**64 - 1)
     eng._shape = (int(N), int(H), int(W))
     _state["call"] += 1
@@ -776,7 +797,8 @@ def forward_batch(sceneCoordinates, hypAssignment, outPoses, shiftX, shiftY, foc
     E, H, W = sceneCoordinates.shape[-4], sceneCoordinates.shape[-2], sceneCoordinates.shape[-1]
     p = eng.make_params(E, H, W, N, shiftX, shiftY, focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha,
                         inlierBeta, maxReproj, subSampling, seed=_state["seed"], call=_state["call"],
-                        max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"])
+                        max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"],
+                        strict_reference=_state["strict_reference"])
     _state["call"] += B
     scores = torch.empty(B, N, dtype=torch.float64, device=eng.device)
     res = eng.forward_batch(sceneCoordinates, hypAssignment, p, scores_out=scores, cams=cams)
@@ -793,6 +815,7 @@ def backward(sceneCoordinates, outGradients, hypAssignment, gtPose, wLossRot, wL
 
     Tensors may live on the CPU (as train_esac.py:152-155 passes them) or on the GPU; with device tensors nothing
     but the ground-truth pose and the loss value crosses PCIe."""
+    _no_strict_training("esac.backward")
     if sceneCoordinates.dtype != torch.float32 or sceneCoordinates.dim() != 4 or sceneCoordinates.size(1) != 3:
         raise RuntimeError("esac.backward: sceneCoordinates must be float32 [E,3,H,W]")
     if outGradients.dtype != torch.float32 or tuple(outGradients.shape) != tuple(sceneCoordinates.shape):
@@ -832,6 +855,7 @@ def backward_batch(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLoss
     include/esac_hip.h).  Advances the call counter by B.
     Each of shiftX, shiftY, focalLength, ppointX, ppointY is a scalar (the whole batch) or a length-B sequence / 1-D tensor /
     numpy array: frame b uses element b (a training mini-batch: one random shift and one focal length per image)."""
+    _no_strict_training("esac.backward_batch")
     if not all(isinstance(t, torch.Tensor) for t in (sceneCoordinates, outGradients, hypAssignment, gtPoses)):
         raise RuntimeError("esac.backward_batch: every tensor argument must be a torch.Tensor")
     if hypAssignment.dtype != torch.int64 or hypAssignment.dim() != 2 or hypAssignment.numel() == 0:

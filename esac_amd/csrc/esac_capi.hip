@@ -34,7 +34,8 @@ static_assert(ESAC_RES_SCORE == ESAC_RES_SCORE_K && ESAC_RES_HYP == ESAC_RES_HYP
                   ESAC_RES_CONTENDERS == ESAC_RES_CONTENDERS_K && ESAC_RES_LM_ITERS == ESAC_RES_LM_ITERS_K &&
                   ESAC_MAX_REF_STEPS == ESAC_MAX_REF_STEPS_K && ESAC_BWD_MAX_SLOTS == ESAC_BWD_SLOTS_K &&
                   ESAC_FLAG_EXACT_SCORES == ESAC_FLAG_EXACT_SCORES_K && ESAC_FLAG_EXACT_SAMPLING == ESAC_FLAG_EXACT_SAMPLING_K &&
-                  ESAC_FLAG_SCORES_BY_INDEX == ESAC_FLAG_SCORES_BY_INDEX_K && ESAC_REFINE_TEAM_MAX == ESAC_REFINE_TEAM_MAX_K &&
+                  ESAC_FLAG_SCORES_BY_INDEX == ESAC_FLAG_SCORES_BY_INDEX_K && ESAC_FLAG_STRICT_REFERENCE == ESAC_FLAG_STRICT_REFERENCE_K &&
+                  ESAC_REFINE_TEAM_MAX == ESAC_REFINE_TEAM_MAX_K &&
                   ESAC_REFINE_TEAM_DEFAULT == ESAC_REFINE_TEAM_DEFAULT_K &&
                   (ESAC_FLAG_AUTO_EXACT & (ESAC_FLAG_EXACT_SCORES | ESAC_FLAG_EXACT_SAMPLING | ESAC_FLAG_SCORES_BY_INDEX)) == 0,
               "result layout drifted between include/esac_hip.h and esac_kernels.hpp");
@@ -478,6 +479,9 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
     if ((int64_t)p->H * p->W > (int64_t)1 << 28 || p->H > 65535 || p->W > 65535)
         return fail(-4, "grid %dx%d too large (at most 65535 rows / columns, 2^28 cells)", p->H, p->W);
     if (p->sub_sampling <= 0) return fail(-4, "subSampling=%d must be positive", p->sub_sampling);
+    if ((p->flags & ESAC_FLAG_STRICT_REFERENCE) && (p->flags & (ESAC_FLAG_SCORE_TILED | ESAC_FLAG_SCORE_STREAM | ESAC_FLAG_AUTO_EXACT)))
+        return fail(-4, "ESAC_FLAG_STRICT_REFERENCE cannot be combined with ESAC_FLAG_SCORE_TILED, ESAC_FLAG_SCORE_STREAM or ESAC_FLAG_AUTO_EXACT "
+                        "(flags=%d): strict mode scores every hypothesis in reference arithmetic", p->flags);
     if (int rc_cam = check_cam(p, p->shift_x, p->shift_y, p->focal, cam_frame)) return rc_cam;
     const int P = p->H * p->W;
     if (B < 1 || B > ESAC_MAX_BATCH) return fail(-4, "batch size %d outside [1,%d]", B, ESAC_MAX_BATCH);
@@ -523,6 +527,7 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
     a.spec_flag = nullptr;  // (forward_impl hands the flags to the kernels of a speculative call only)
     a.samp_cap = (int)(((long long)c->capN * ESAC_SAMPLE_LIST_PER_HYP) > 0x7fffffffLL ? 0x7fffffff : (long long)c->capN * ESAC_SAMPLE_LIST_PER_HYP);
     a.flags = p->flags;
+    if (a.flags & ESAC_FLAG_STRICT_REFERENCE) a.flags |= ESAC_FLAG_EXACT_SCORES | ESAC_FLAG_EXACT_SAMPLING;  // (implied)
     c->epoch += 1.0;  // every call gets its own epoch: result hand-off word and the tag of the status word
     a.epoch = c->epoch;
     a.sample_epoch = c->sample_epoch;  // launches that sample call mark_sampling() and overwrite this
@@ -1213,6 +1218,8 @@ extern "C" int esac_hip_backward(esac_hip_ctx* c, const float* d_sc, float* d_ou
                                  const esac_hip_params* p, void* stream, double* h_out) {
     if (!d_out_gradients || !h_gt_pose) return fail(-1, "esac_hip_backward: null gradient tensor or ground-truth pose");
     if (!c) return fail(-1, "null context");
+    if (p && (p->flags & ESAC_FLAG_STRICT_REFERENCE))
+        return fail(-4, "esac_hip_backward: the training path has no strict mode (ESAC_FLAG_STRICT_REFERENCE is a forward flag)");
     DeviceGuard guard(c->device);
     KArgs a;
     int rc = make_args(c, d_sc, d_assign, p, &a);
@@ -1336,6 +1343,8 @@ extern "C" int esac_hip_backward_batch_cams(esac_hip_ctx* c, int B, const float*
     if (!p) return fail(-1, "null params");
     if (!d_sc || !d_out_gradients || !d_assign || !h_gt_poses)
         return fail(-1, "esac_hip_backward_batch: null coordinate, gradient, assignment or ground-truth pointer");
+    if (p->flags & ESAC_FLAG_STRICT_REFERENCE)
+        return fail(-4, "esac_hip_backward_batch: the training path has no strict mode (ESAC_FLAG_STRICT_REFERENCE is a forward flag)");
     if (!h_out) return fail(-4, "esac_hip_backward_batch: the batched call is blocking only: h_out (host double[B,4]) is required");
     if (B < 1 || B > ESAC_MAX_BATCH) return fail(-4, "esac_hip_backward_batch: batch size %d outside [1,%d]", B, ESAC_MAX_BATCH);
     if (p->d_hyp_index || p->hyp_offset)

@@ -184,48 +184,7 @@ constexpr int ESAC_FIRST_WIDE_MAX = 8192;  // up to this many hypotheses: one pa
 // one only for wavefronts with a hypothesis still open); TRIES = 32: two hypotheses, 32 tries in one pass -- with a few
 // thousand hypotheses (config 4: 4096) the 16-try shape is 1024 wavefronts, half of what the chip holds, twice in a row
 // (47 us; one pass of 32: 30 us).
-template <int TRIES>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sample_first(KArgs a) {
-    constexpr int HPW = 64 / TRIES;  // hypotheses per wavefront
-    frame_view(a);
-    const int lane = threadIdx.x, grp = lane / TRIES, t = a.first_try + (lane & (TRIES - 1));
-    const int h = blockIdx.x * HPW + grp;
-    const int hc = h < a.N ? h : a.N - 1;
-    const bool mine_pending = h < a.N && (a.first_try == 0 || a.tries[hc] == SAMPLE_PENDING);
-    if (!__any(mine_pending)) return;  // all hypotheses of this wavefront are done
-    const bool active = mine_pending && t < a.max_tries;
-    if (a.first_try == 0 && h < a.N && (lane & (TRIES - 1)) == 0) flag_bad_assignment(a, h);
-    const int e = expert_of(a, hc);
-    const int P = a.H * a.W;
-    const float* __restrict__ map = a.sc + (size_t)e * 3 * P;
-    const Philox rng(a.seed, a.call);
-    const Cam cam = make_cam(a);
-    int cx[4] = {0, 0, 0, 0}, cy[4] = {0, 0, 0, 0};
-    double rvec[3] = {0, 0, 0}, T[3] = {0, 0, 0};
-    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    bool accepted = false;
-    if (active) {
-        V3 Pt[4];
-        float Pf[4][3];
-        double mu[4], mv[4], Rp[9], Tp[3];
-        gather_sample(a, map, P, rng, (uint32_t)global_hyp(a, hc), (uint32_t)t, cx, cy, Pt, Pf, mu, mv);
-        double reproj2 = 0;
-        if (p3p_4pt(Pt, mu, mv, cam, Rp, Tp, &reproj2) && (t == a.max_tries - 1 || !cannot_pass(reproj2, (double)a.tau)))
-            accepted = accept_sample(Rp, Tp, Pf, mu, mv, cam, (double)a.tau, rvec, T, R);
-    }
-    const unsigned long long m = __ballot(accepted);
-    const unsigned mine = (unsigned)(m >> (TRIES * grp)) & (TRIES == 32 ? 0xffffffffu : 0xffffu);
-    if (mine_pending) {
-        if (mine) {
-            const int first = __ffs((int)mine) - 1;
-            if ((lane & (TRIES - 1)) == first) store_hypothesis(a, h, map, rvec, T, R, cx, cy, a.first_try + first);
-        } else if (a.max_tries <= a.first_try + TRIES) {
-            if (t == a.max_tries - 1) store_hypothesis(a, h, map, rvec, T, R, cx, cy, -1);  // budget exhausted: last state remains
-        } else if ((lane & (TRIES - 1)) == 0) {
-            a.tries[h] = SAMPLE_PENDING;  // k_pending_list gathers what the last pass leaves pending
-        }
-    }
-}
+// (the kernel itself: sample_kernels.inc.hpp, k_sample_first<TRIES> -- included below, once per alignment)
 
 // The hypotheses the first passes left pending, as a list for the screened chain (k_sample_prescreen): a ballot prefix per
 // wavefront, a block scan, ONE global atomic per 1024 hypotheses.  (Appending from k_sample_first itself -- 15,000 single-
@@ -291,130 +250,28 @@ __global__ __launch_bounds__(1024) void k_pending_list(KArgs a) {
 // second 128-try one.  The chip holds no more than this: the fp64 solver with its decision path needs ~445 registers,
 // one wavefront per SIMD, and 256 hypotheses x 4 wavefronts fill the 1024 SIMDs.
 // A hypothesis that needs hundreds of tries (wrong expert) continues with one try per lane, the throughput shape.
-template <int SAMPLE_B, int LPT>
-__global__ __launch_bounds__(SAMPLE_B) void k_sample(KArgs a) {
-    static_assert(LPT == 1 || LPT == 2 || LPT == 4, "lanes per try");
-    constexpr int CPLN = 4 / LPT;  // candidates per lane in the shared rounds
-    __shared__ int s_first[2][SAMPLE_B / 64];
-    __shared__ double s_pose[CPLN > 1 ? SAMPLE_B * 12 : 1];  // [value][lane]: the best candidate's pose so far, per lane
-    frame_view(a);
-    const int h = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int e = expert_of(a, h);
-    const int P = a.H * a.W;
-    const float* __restrict__ map = a.sc + (size_t)e * 3 * P;
-    const Philox rng(a.seed, a.call);
-    const Cam cam = make_cam(a);
-    const uint32_t gh = (uint32_t)global_hyp(a, h);
-    const double tau = (double)a.tau;
-    if (a.first_try > 0 && a.tries[h] != SAMPLE_PENDING) return;  // phase 2 of the throughput shape: done in phase 1
-    if (a.first_try == 0 && threadIdx.x == 0) flag_bad_assignment(a, h);
-    if (a.handover != 0x7fffffff && threadIdx.x == 0 && expert_stats_on(a)) atomicAdd(expert_stats(a, e), 1);  // (see expert_stats)
-
-    int parity = 0;
-    for (int base = a.first_try, TRIES = 0; base < a.max_tries; base += TRIES, parity ^= 1) {
-        const bool quad = LPT > 1 && base < SAMPLE_B;  // workgroup-uniform: the first SAMPLE_B tries go LPT lanes a try
-        TRIES = quad ? SAMPLE_B / LPT : SAMPLE_B;
-        const int t = base + (quad ? (int)threadIdx.x / LPT : (int)threadIdx.x);
-        const int sub = threadIdx.x & (LPT - 1);  // shared rounds only: this lane evaluates roots sub, sub + LPT, ...
-        bool holder = !quad;                      // the lane that carries the try's final state (pose or zero pose)
-        const bool active = t < a.max_tries;
-        int cx[4] = {0, 0, 0, 0}, cy[4] = {0, 0, 0, 0};
-        double rvec[3] = {0, 0, 0}, T[3] = {0, 0, 0};
-        double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        bool accepted = false;
-        if (active) {
-            V3 Pt[4];
-            float Pf[4][3];
-            double mu[4], mv[4];
-            gather_sample(a, map, P, rng, gh, (uint32_t)t, cx, cy, Pt, Pf, mu, mv);
-            double Rp[9], Tp[3], reproj2 = 0;
-            bool solved;
-            if (LPT > 1 && quad) {
-                P3PSetup S;
-                const bool ok = p3p_setup(Pt, mu, mv, cam, S);
-                // Step k: the lanes evaluate roots k * LPT .. k * LPT + LPT - 1 (this lane: root k * LPT + sub), exchange
-                // (valid, error) and continue the reference's sequential scan over the candidates (same `>` rule, same NaN
-                // behaviour) -- every lane carries the scan's state, and the lane whose candidate has just become the best
-                // keeps its pose: after the last step the winner's lane holds the winner's pose.
-                const int lane0 = lane & ~(LPT - 1);
-                bool have = false;
-                double min_reproj = 0;
-                int win = -1;
-#pragma nounroll
-                for (int k = 0; k < CPLN; k++) {
-                    const int root = k * LPT + sub;
-                    const double x = root == 0 ? S.x[0] : root == 1 ? S.x[1] : root == 2 ? S.x[2] : S.x[3];
-                    double R1[9], T1[3], rp = 0;
-                    const bool vk = ok && root < S.n && p3p_candidate(S, x, Pt, mu[3], mv[3], cam, R1, T1, rp);
-#pragma unroll
-                    for (int j = 0; j < LPT; j++) {
-                        const bool vi = __shfl((int)vk, lane0 + j) != 0;
-                        const double ri = __shfl(rp, lane0 + j);
-                        if (vi && (!have || min_reproj > ri)) {
-                            have = true;
-                            min_reproj = ri;
-                            win = k * LPT + j;
-                        }
-                    }
-                    if (win == root) {  // (more than one step: the pose waits in LDS, not in 24 registers across the next solve)
-#pragma unroll
-                        for (int q = 0; q < 9; q++) {
-                            if (CPLN > 1) s_pose[q * SAMPLE_B + threadIdx.x] = R1[q];
-                            else Rp[q] = R1[q];
-                        }
-#pragma unroll
-                        for (int q = 0; q < 3; q++) {
-                            if (CPLN > 1) s_pose[(9 + q) * SAMPLE_B + threadIdx.x] = T1[q];
-                            else Tp[q] = T1[q];
-                        }
-                    }
-                }
-                solved = have && (win & (LPT - 1)) == sub;
-                if (CPLN > 1 && solved) {
-#pragma unroll
-                    for (int q = 0; q < 9; q++) Rp[q] = s_pose[q * SAMPLE_B + threadIdx.x];
-#pragma unroll
-                    for (int q = 0; q < 3; q++) Tp[q] = s_pose[(9 + q) * SAMPLE_B + threadIdx.x];
-                }
-                holder = solved || (!have && sub == 0);
-                reproj2 = min_reproj;
-            } else {
-                solved = p3p_4pt(Pt, mu, mv, cam, Rp, Tp, &reproj2);
-            }
-            if (solved && (t == a.max_tries - 1 || !cannot_pass(reproj2, tau)))
-                accepted = accept_sample(Rp, Tp, Pf, mu, mv, cam, tau, rvec, T, R);
-            // a failed solve leaves the zero pose (safeSolvePnP, esac_util.h:107-111)
-        }
-        // lowest accepted try of the round = the try the reference's sequential loop stops at
-        const unsigned long long m = __ballot(accepted);
-        if (lane == 0) {
-            const int first_lane = __ffsll((long long)m) - 1;
-            s_first[parity][wave] = m ? base + (quad ? wave * (64 / LPT) + first_lane / LPT : wave * 64 + first_lane) : 0x7fffffff;
-        }
-        __syncthreads();
-        int first = s_first[parity][0];
-#pragma unroll
-        for (int w = 1; w < SAMPLE_B / 64; w++) first = min(first, s_first[parity][w]);
-        const bool last_round = base + TRIES >= a.max_tries;
-        int writer = -1, tries_val = -1;
-        if (first != 0x7fffffff) {
-            writer = first;
-            tries_val = first;
-        } else if (last_round) {
-            writer = a.max_tries - 1;  // budget exhausted: state of the last try remains
-        }
-        if (writer >= 0) {
-            if (t == writer && holder) store_hypothesis(a, h, map, rvec, T, R, cx, cy, tries_val);
-            if (a.spec_flag && threadIdx.x == 0) a.spec_flag[h] = 0;  // settled by this pass
-            return;
-        }
-        if (base + TRIES >= a.handover) {  // a straggler (wrong expert): the spread, screened search takes over from here
-            if (threadIdx.x < 64) mark_pending(a, h, e, threadIdx.x == 0);
-            return;
-        }
-    }
-}
+// (the kernel itself: sample_kernels.inc.hpp, k_sample<SAMPLE_B, LPT>)
+#define ESAC_K_SAMPLE_FIRST k_sample_first
+#define ESAC_K_SAMPLE k_sample
+#define ESAC_SAMPLE_ALIGN AlignTriad
+#define ESAC_SAMPLE_FIRST_ATTR __attribute__((amdgpu_waves_per_eu(2, 2)))
+#include "sample_kernels.inc.hpp"
+#undef ESAC_K_SAMPLE_FIRST
+#undef ESAC_K_SAMPLE
+#undef ESAC_SAMPLE_ALIGN
+#undef ESAC_SAMPLE_FIRST_ATTR
+// ESAC_FLAG_STRICT_REFERENCE: the same two kernels around the reference's own alignment (Horn / Jacobi: align_horn).  The first
+// pass at one wavefront per SIMD: the eigen-solve's two 4x4s on top of the solver's state do not fit 256 registers.  The strict
+// route never hands over (launch_sample): it has no screened chain.
+#define ESAC_K_SAMPLE_FIRST k_sample_first_strict
+#define ESAC_K_SAMPLE k_sample_strict
+#define ESAC_SAMPLE_ALIGN AlignHorn
+#define ESAC_SAMPLE_FIRST_ATTR
+#include "sample_kernels.inc.hpp"
+#undef ESAC_K_SAMPLE_FIRST
+#undef ESAC_K_SAMPLE
+#undef ESAC_SAMPLE_ALIGN
+#undef ESAC_SAMPLE_FIRST_ATTR
 
 // ---- throughput shape, tries >= first_try: screened sampling -----------------------------------------------------------
 // A hypothesis of a wrong expert needs ~10^3 tries (its 4 points only pass tau by luck), and half of the fp64 work of a
@@ -1417,8 +1274,10 @@ void launch_spec_join(const KArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_spec
 
 // ================================================================= K3b: exact score of EVERY hypothesis
 // (training path esac.cpp:295-316, esac_hip_score_exact)
-template <int B>
-__global__ __launch_bounds__(B) void k_rescore(KArgs a) {
+// STRICT (ESAC_FLAG_STRICT_REFERENCE): std::min's own argument order -- a NaN error (non-finite scene coordinate) stays NaN and
+// with it the hypothesis' score, as in the reference (oracle: repro_errs); otherwise such a cell is an outlier at maxReproj
+template <int B, bool STRICT>
+__device__ __forceinline__ void rescore_body(KArgs& a) {
     __shared__ double s_part[B / 64];
     __shared__ double s_tot[1];
     frame_view(a);
@@ -1438,7 +1297,8 @@ __global__ __launch_bounds__(B) void k_rescore(KArgs a) {
         for (int i = threadIdx.x; i < P; i += B) {
             const int row = i / a.W, col = i - row * a.W;
             float err = project_exact_err(R, t, cam, mx[i], mx[P + i], mx[2 * P + i], cell_px(a, col), cell_py(a, row));
-            err = err < a.max_reproj ? err : a.max_reproj;  // std::min(l, maxReproj), esac_util.h:358
+            if (STRICT) err = a.max_reproj < err ? a.max_reproj : err;  // std::min(l, maxReproj) = (maxReproj < l) ? maxReproj : l
+            else        err = err < a.max_reproj ? err : a.max_reproj;  // std::min(l, maxReproj), esac_util.h:358
             acc[0] += soft_inlier_exact(err, a.tau, a.beta);
         }
         block_sum<1, B>(acc, s_part, s_tot);
@@ -1452,6 +1312,15 @@ __global__ __launch_bounds__(B) void k_rescore(KArgs a) {
         }
         __syncthreads();
     }
+}
+
+template <int B>
+__global__ __launch_bounds__(B) void k_rescore(KArgs a) {
+    rescore_body<B, false>(a);
+}
+template <int B>
+__global__ __launch_bounds__(B) void k_rescore_strict(KArgs a) {
+    rescore_body<B, true>(a);
 }
 
 // softMax / entropy (esac_util.h:461-497) over the EXACT scores of all N hypotheses (ESAC_FLAG_EXACT_SCORES: k_rescore
@@ -1468,6 +1337,60 @@ __global__ __launch_bounds__(B) void k_stats_exact(KArgs a) {
     for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
     if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = m;
     __syncthreads();
+    m = s_max[0];
+#pragma unroll
+    for (int k = 1; k < B / 64; k++) m = fmax(m, s_max[k]);
+    double acc[2] = {0, 0};
+    for (int i = threadIdx.x; i < a.N; i += B) {
+        const double d = a.scores[i] - m;
+        const double ex = exp(d);
+        acc[0] += ex;
+        acc[1] += ex * d;
+    }
+    block_sum<2, B>(acc, s_part, s_tot);
+    if (threadIdx.x == 0) {
+        a.n_contenders[0] = a.N;
+        a.stats[0] = m;
+        a.stats[1] = acc[0];
+        a.stats[2] = log2(acc[0]) - acc[1] / (acc[0] * 0.6931471805599453);  // -sum p log2 p, p = exp(d) / S
+    }
+}
+
+// ESAC_FLAG_STRICT_REFERENCE: the same statistics, and the reference's behaviour when a score is NaN (k_rescore_strict lets a
+// non-finite coordinate through).  softMax (esac_util.h:461-481) then divides by a NaN sum: EVERY probability is NaN, whichever
+// hypothesis the NaN came from; entropy (`dist > 0` is false) is 0; draw (`prob < EPS` and `prob > maxProb` are false) keeps
+// index 0.  Here: stats = (NaN, NaN, 0), which makes the record's probability NaN, and hypothesis 0 is left as the only
+// contender (exact_flag), so that the refinement's argmax -- which never picks a NaN -- returns it.
+template <int B>
+__global__ __launch_bounds__(B) void k_stats_strict(KArgs a) {
+    __shared__ double s_part[2 * (B / 64)];
+    __shared__ double s_tot[2];
+    __shared__ double s_max[B / 64];
+    __shared__ int s_nan;
+    frame_view(a);
+    if (threadIdx.x == 0) s_nan = 0;
+    __syncthreads();
+    double m = -INFINITY;
+    bool nan = false;
+    for (int i = threadIdx.x; i < a.N; i += B) {
+        const double sc = a.scores[i];
+        nan |= sc != sc;
+        m = fmax(m, sc);
+    }
+    if (nan) s_nan = 1;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (s_nan) {  // (workgroup-uniform)
+        for (int i = threadIdx.x; i < a.N; i += B) a.exact_flag[i] = i == 0 ? 1 : 0;
+        if (threadIdx.x == 0) {
+            a.n_contenders[0] = a.N;
+            a.stats[0] = a.stats[1] = __builtin_nan("");
+            a.stats[2] = 0.0;
+        }
+        return;
+    }
     m = s_max[0];
 #pragma unroll
     for (int k = 1; k < B / 64; k++) m = fmax(m, s_max[k]);
@@ -1650,6 +1573,10 @@ void launch_shard_balanced(const int64_t* assign, int N, int E, int world, int r
 
 // ---------------------------------------------------------------- launchers
 void launch_stats_exact(const KArgs& a, hipStream_t s) {
+    if (a.flags & ESAC_FLAG_STRICT_REFERENCE_K) {
+        hipLaunchKernelGGL(k_stats_strict<256>, dim3(1, a.frames), dim3(256), 0, s, a);
+        return;
+    }
     hipLaunchKernelGGL(k_stats_exact<256>, dim3(1, a.frames), dim3(256), 0, s, a);
 }
 // the chain that finishes hypotheses left SAMPLE_PENDING at try b.first_try (see k_sample_prescreen); `waves` wavefronts
@@ -1679,7 +1606,9 @@ void launch_sample(const KArgs& a, hipStream_t s) {
     // ESAC_FLAG_EXACT_SAMPLING: no screen anywhere -- every try is solved and decided by the fp64 route (k_sample walks a
     // straggler's whole budget itself, one try per lane; the throughput shape finishes with k_sample<64> instead of the
     // screened chain)
-    const bool exact = (a.flags & ESAC_FLAG_EXACT_SAMPLING_K) != 0;
+    // ESAC_FLAG_STRICT_REFERENCE (implies the exact route): the same launches, the kernels with the reference's alignment
+    const bool strict = (a.flags & ESAC_FLAG_STRICT_REFERENCE_K) != 0;
+    const bool exact = strict || (a.flags & ESAC_FLAG_EXACT_SAMPLING_K) != 0;
     const bool handover = a.E > 1 && a.max_tries > 1024 && !exact;
 constexpr int ESAC_LATENCY_MAX = 1024;
 constexpr int ESAC_HANDOVER = 32;  // (64: k_sample<128> 41 us + screened search 29 us at config 3; 32: 30 + 31 us)
@@ -1707,14 +1636,14 @@ constexpr int ESAC_CHAIN_PER_HYP = 8;
         // tries: 29.9 again).  Without a hand-over (one expert, ESAC_FLAG_EXACT_SAMPLING) a straggler walks its whole budget in this
         // kernel, one try per lane: two wavefronts per hypothesis halve that tail (config 3 on the guaranteed routes: 0.56 ms
         // against 0.89 with one)
-        if (total <= 256)                    hipLaunchKernelGGL((k_sample<256, 2>), dim3(a.N, a.frames), dim3(256), 0, s, b);
-        else if (total <= 512 || !handover)  hipLaunchKernelGGL((k_sample<128, 4>), dim3(a.N, a.frames), dim3(128), 0, s, b);
+        if (total <= 256)                    hipLaunchKernelGGL((strict ? k_sample_strict<256, 2> : k_sample<256, 2>), dim3(a.N, a.frames), dim3(256), 0, s, b);
+        else if (total <= 512 || !handover)  hipLaunchKernelGGL((strict ? k_sample_strict<128, 4> : k_sample<128, 4>), dim3(a.N, a.frames), dim3(128), 0, s, b);
         else                                 hipLaunchKernelGGL((k_sample<64, 2>), dim3(a.N, a.frames), dim3(64), 0, s, b);
     } else if (total <= 4096 && !handover) {
-        hipLaunchKernelGGL((k_sample<128, 1>), dim3(a.N, a.frames), dim3(128), 0, s, b);
+        hipLaunchKernelGGL((strict ? k_sample_strict<128, 1> : k_sample<128, 1>), dim3(a.N, a.frames), dim3(128), 0, s, b);
     } else {  // throughput: passes of 16 tries with four hypotheses per wavefront, then the unaccepted rest by the screened chain
         if (total <= ESAC_FIRST_WIDE_MAX) {
-            hipLaunchKernelGGL(k_sample_first<32>, dim3((a.N + 1) / 2, a.frames), dim3(64), 0, s, b);
+            hipLaunchKernelGGL((strict ? k_sample_first_strict<32> : k_sample_first<32>), dim3((a.N + 1) / 2, a.frames), dim3(64), 0, s, b);
             b.first_try += 32;
         } else if (a.E > 1 && !exact) {
             // tens of thousands of hypotheses over many experts (config 5: 16384 over 50, Dirichlet gating): nearly all of them
@@ -1722,13 +1651,13 @@ constexpr int ESAC_CHAIN_PER_HYP = 8;
             // from try 0 (a hypothesis of the right expert costs it one screened round and a handful of fp64 decisions)
         } else {
             for (int pass = 0; pass < FIRST_PHASE_TRIES / 16 && b.first_try < a.max_tries; pass++) {
-                hipLaunchKernelGGL(k_sample_first<16>, dim3((a.N + 3) / 4, a.frames), dim3(64), 0, s, b);
+                hipLaunchKernelGGL((strict ? k_sample_first_strict<16> : k_sample_first<16>), dim3((a.N + 3) / 4, a.frames), dim3(64), 0, s, b);
                 b.first_try += 16;
             }
         }
         if (b.first_try < a.max_tries) {
             if (exact) {
-                hipLaunchKernelGGL((k_sample<64, 1>), dim3(a.N, a.frames), dim3(64), 0, s, b);  // every try solved in full
+                hipLaunchKernelGGL((strict ? k_sample_strict<64, 1> : k_sample<64, 1>), dim3(a.N, a.frames), dim3(64), 0, s, b);  // every try solved in full
             } else {
                 hipLaunchKernelGGL(k_pending_list, dim3((a.N + 1023) / 1024, a.frames), dim3(1024), 0, s, b);
                 // (the list stays in hypothesis order: expert-major and dealt to the XCDs, the full-resolution workload's
@@ -1749,7 +1678,7 @@ constexpr int ESAC_CHAIN_PER_HYP = 8;
 // ESAC_FIRST_WIDE_MAX hypotheses (beyond that the chain takes every hypothesis from try 0: nothing is settled early).
 constexpr int ESAC_SPLIT_LATENCY_MAX = 1024, ESAC_SPLIT_HANDOVER = 32;  // = launch_sample's ESAC_LATENCY_MAX / ESAC_HANDOVER
 bool sample_can_split(const KArgs& a) {
-    return a.frames == 1 && a.E > 1 && a.max_tries > 1024 && !(a.flags & ESAC_FLAG_EXACT_SAMPLING_K) && a.N <= ESAC_FIRST_WIDE_MAX &&
+    return a.frames == 1 && a.E > 1 && a.max_tries > 1024 && !(a.flags & (ESAC_FLAG_EXACT_SAMPLING_K | ESAC_FLAG_STRICT_REFERENCE_K)) && a.N <= ESAC_FIRST_WIDE_MAX &&
            a.first_try == 0;
 }
 // The first pass on `s` -- its last kernel completes `fork` (the kernel's own completion signal: hipExtLaunchKernelGGL; an event
@@ -1821,8 +1750,11 @@ void launch_rescore_all(const KArgs& a, hipStream_t s, bool per_frame_shape) {
     // 16 wavefronts per hypothesis put four on every SIMD, whose chains interleave (9.8 -> 5.x us at 256 hypotheses)
     // per_frame_shape: the shape a SINGLE frame would take whatever the batch is (the two shapes sum a score's cells in different
     // orders: esac_hip_backward_batch keeps its scores, hence its gradients, bit for bit those of single calls)
-    if ((long long)a.N * (per_frame_shape ? 1 : a.frames) <= 256) hipLaunchKernelGGL(k_rescore<1024>, dim3(grid, a.frames), dim3(1024), 0, s, a);
-    else                                  hipLaunchKernelGGL(k_rescore<256>, dim3(grid, a.frames), dim3(256), 0, s, a);
+    const bool strict = (a.flags & ESAC_FLAG_STRICT_REFERENCE_K) != 0;
+    if ((long long)a.N * (per_frame_shape ? 1 : a.frames) <= 256)
+        hipLaunchKernelGGL((strict ? k_rescore_strict<1024> : k_rescore<1024>), dim3(grid, a.frames), dim3(1024), 0, s, a);
+    else
+        hipLaunchKernelGGL((strict ? k_rescore_strict<256> : k_rescore<256>), dim3(grid, a.frames), dim3(256), 0, s, a);
 }
 
 }  // namespace esac

@@ -366,7 +366,7 @@ __device__ __forceinline__ double lm_pass(ListPtr list, int n, const double para
 // with the pass inlined at several sites the code grew to 170 KB and every phase ran from cold code).
 template <int B, int MODE, typename ListPtr>
 __device__ __forceinline__ int lm_refit(ListPtr list, int n, double pose[6], const Cam& cam, const PxMap& pm, double* s_part,
-                                        double* s_tot, const double* s_pow10, long long* g_cyc, Coop* co = nullptr) {
+                                        double* s_tot, const double* s_pow10, long long* g_cyc, bool strict, Coop* co = nullptr) {
     CYC_DECL;
     double param[6], prev[6];
 #pragma unroll
@@ -397,7 +397,7 @@ __device__ __forceinline__ int lm_refit(ListPtr list, int n, double pose[6], con
                 pn += prev[k] * prev[k];
             }
             const bool would_end = iters + 1 >= 20 || relative_step_below_eps(dn, pn);
-            if (trial_rejected(err2, prev_err2, would_end) && ++lambda_lg10 <= 16) {
+            if (trial_rejected(err2, prev_err2, would_end, strict) && ++lambda_lg10 <= 16) {
                 accept = false;  // state CHECK_ERR failed: retry from `prev` with a larger lambda
             } else {
                 lambda_lg10 = lambda_lg10 - 1 > -16 ? lambda_lg10 - 1 : -16;
@@ -544,7 +544,7 @@ __global__ __launch_bounds__(B) void k_refine(KArgs a) {
         if (!SLOTS && writer && threadIdx.x == 0) a.inlier_counts[rstep] = n_inl;
         if ((unsigned)n_inl <= best_inliers) break;  // converged (esac_util.h:417-419)
         best_inliers = (unsigned)n_inl;
-        lm_total += lm_refit<B, MODE>(my_list, n_wave, pose, cam, pm, s_part, s_tot, s_pow10, g_cyc, SHARED ? &co : nullptr);
+        lm_total += lm_refit<B, MODE>(my_list, n_wave, pose, cam, pm, s_part, s_tot, s_pow10, g_cyc, (a.flags & ESAC_FLAG_STRICT_REFERENCE_K) != 0, SHARED ? &co : nullptr);
         accepted++;
         last_inliers = n_inl;
         map_buf = cur;  // inlierMap = this step's set (esac_util.h:440)

@@ -701,7 +701,7 @@ __global__ __launch_bounds__(REFINE_B) void k_refine_team(KArgs a) {
         if (co.dead) break;  // an exchange timed out: the sums are garbage, the call reports it
         CYC_BEGIN();
         bool fresh = true;  // normal equations from this pass (else: state CHECK_ERR failed, retry from `prev` with a larger lambda)
-        if (in_refit && trial_rejected(sums[0], prev_err2, ends_refit) && ++lambda_lg10 <= 16) {
+        if (in_refit && trial_rejected(sums[0], prev_err2, ends_refit, (a.flags & ESAC_FLAG_STRICT_REFERENCE_K) != 0) && ++lambda_lg10 <= 16) {
             fresh = false;
         } else {
             if (in_refit) {
@@ -835,7 +835,8 @@ bool refine_folds_select(const KArgs& a) {
 // ESAC_FLAG_EXACT_SCORES: the scores are final when the refinement starts; their softmax statistics and argmax are a few
 // reductions over <= 256 values -- in the team kernel's prologue instead of a launch of their own (k_stats_exact)
 bool refine_folds_exact_stats(const KArgs& a) {
-    return refine_team_members(a) > 0 && a.N <= REFINE_B && (a.flags & ESAC_FLAG_EXACT_SCORES_K) != 0;
+    // (not under ESAC_FLAG_STRICT_REFERENCE: the reference's behaviour on NaN scores lives in k_stats_strict alone)
+    return refine_team_members(a) > 0 && a.N <= REFINE_B && (a.flags & ESAC_FLAG_EXACT_SCORES_K) != 0 && !(a.flags & ESAC_FLAG_STRICT_REFERENCE_K);
 }
 
 unsigned long long launch_refine_team(const KArgs& a, hipStream_t s) {

@@ -374,6 +374,127 @@ ESAC_HD void align_triangles(V3 P0, V3 P1, V3 P2, V3 Q0, V3 Q1, V3 Q2, double R[
     T[0] = Qc.x - RPc.x; T[1] = Qc.y - RPc.y; T[2] = Qc.z - RPc.z;
 }
 
+// ---- the same alignment as the CPU library computes it (ESAC_FLAG_STRICT_REFERENCE): Horn's unit-quaternion method with a
+// cyclic Jacobi eigen-solve of the symmetric 4x4 -- operation by operation the oracle's align3 + jacobi_4x4 (Numerical Recipes
+// `jacobi`), so that a host build reproduces its doubles and the device differs from it by libm's last bits only.  On congruent,
+// well-spread triangles this is the optimum align_triangles reaches; on collinear base points (the optimum is a one-parameter
+// family: which member comes out is the eigen-solve's business) and on slivers it is the member the reference takes.
+// One lane, no run-time indices: the (i, j) order of a sweep is fixed, so its six rotations are six instantiations and the two
+// 4x4s, D, B and Z are scalars after unrolling; the sweep loop is a loop (sum == 0 ends it after ~6 sweeps; 50 is the bound).
+template <int G, int H>
+ESAC_HD void jacobi_rotate_pair(double (&M)[16], double s, double tau) {
+    const double g = M[G], h = M[H];
+    M[G] = g - s * (h + g * tau);
+    M[H] = h + s * (g - h * tau);
+}
+// row / column K of the upper triangle under the rotation (I, J): the elements (K, I) and (K, J), wherever they are stored
+template <int I, int J, int K>
+ESAC_HD void jacobi_rotate_row(double (&A)[16], double s, double tau) {
+    if constexpr (K != I && K != J) jacobi_rotate_pair<(K < I ? K * 4 + I : I * 4 + K), (K < J ? K * 4 + J : J * 4 + K)>(A, s, tau);
+}
+template <int I, int J>
+ESAC_HD void jacobi_rotate_4x4(double (&A)[16], double (&U)[16], double (&D)[4], double (&Z)[4], int iter, double tresh) {
+    const double Aij = A[I * 4 + J];
+    const double eps_machine = 100.0 * fabs(Aij);
+    if (iter > 3 && fabs(D[I]) + eps_machine == fabs(D[I]) && fabs(D[J]) + eps_machine == fabs(D[J])) {
+        A[I * 4 + J] = 0.0;
+    } else if (fabs(Aij) > tresh) {
+        double hh = D[J] - D[I], t;
+        if (fabs(hh) + eps_machine == fabs(hh)) {
+            t = Aij / hh;
+        } else {
+            const double theta = 0.5 * hh / Aij;
+            t = 1.0 / (fabs(theta) + sqrt(1.0 + theta * theta));
+            if (theta < 0.0) t = -t;
+        }
+        hh = t * Aij;
+        Z[I] -= hh; Z[J] += hh;
+        D[I] -= hh; D[J] += hh;
+        A[I * 4 + J] = 0.0;
+        const double c = 1.0 / sqrt(1 + t * t);
+        const double s = t * c;
+        const double tau = s / (1.0 + c);
+        jacobi_rotate_row<I, J, 0>(A, s, tau);
+        jacobi_rotate_row<I, J, 1>(A, s, tau);
+        jacobi_rotate_row<I, J, 2>(A, s, tau);
+        jacobi_rotate_row<I, J, 3>(A, s, tau);
+        jacobi_rotate_pair<0 * 4 + I, 0 * 4 + J>(U, s, tau);
+        jacobi_rotate_pair<1 * 4 + I, 1 * 4 + J>(U, s, tau);
+        jacobi_rotate_pair<2 * 4 + I, 2 * 4 + J>(U, s, tau);
+        jacobi_rotate_pair<3 * 4 + I, 3 * 4 + J>(U, s, tau);
+    }
+}
+
+ESAC_HD void align_horn(V3 P0, V3 P1, V3 P2, V3 Q0, V3 Q1, V3 Q2, double R[9], double T[3]) {
+    // centroids (C_start: scene points, C_end: camera-frame points) and the cross-covariance s[r][c] = mean(P.r * Q.c) - ...
+    const double Cex = (Q0.x + Q1.x + Q2.x) / 3, Cey = (Q0.y + Q1.y + Q2.y) / 3, Cez = (Q0.z + Q1.z + Q2.z) / 3;
+    const double Csx = (P0.x + P1.x + P2.x) / 3, Csy = (P0.y + P1.y + P2.y) / 3, Csz = (P0.z + P1.z + P2.z) / 3;
+    const double s0 = (P0.x * Q0.x + P1.x * Q1.x + P2.x * Q2.x) / 3 - Cex * Csx;
+    const double s1 = (P0.x * Q0.y + P1.x * Q1.y + P2.x * Q2.y) / 3 - Cey * Csx;
+    const double s2 = (P0.x * Q0.z + P1.x * Q1.z + P2.x * Q2.z) / 3 - Cez * Csx;
+    const double s3 = (P0.y * Q0.x + P1.y * Q1.x + P2.y * Q2.x) / 3 - Cex * Csy;
+    const double s4 = (P0.y * Q0.y + P1.y * Q1.y + P2.y * Q2.y) / 3 - Cey * Csy;
+    const double s5 = (P0.y * Q0.z + P1.y * Q1.z + P2.y * Q2.z) / 3 - Cez * Csy;
+    const double s6 = (P0.z * Q0.x + P1.z * Q1.x + P2.z * Q2.x) / 3 - Cex * Csz;
+    const double s7 = (P0.z * Q0.y + P1.z * Q1.y + P2.z * Q2.y) / 3 - Cey * Csz;
+    const double s8 = (P0.z * Q0.z + P1.z * Q1.z + P2.z * Q2.z) / 3 - Cez * Csz;
+    double A[16], U[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    A[0] = s0 + s4 + s8;
+    A[5] = s0 - s4 - s8;
+    A[10] = s4 - s8 - s0;
+    A[15] = s8 - s0 - s4;
+    A[4] = A[1] = s5 - s7;
+    A[8] = A[2] = s6 - s2;
+    A[12] = A[3] = s1 - s3;
+    A[9] = A[6] = s3 + s1;
+    A[13] = A[7] = s6 + s2;
+    A[14] = A[11] = s7 + s5;
+    double B[4] = {A[0], A[5], A[10], A[15]}, D[4] = {A[0], A[5], A[10], A[15]}, Z[4] = {0, 0, 0, 0};
+#pragma nounroll
+    for (int iter = 0; iter < 50; iter++) {
+        const double sum = fabs(A[1]) + fabs(A[2]) + fabs(A[3]) + fabs(A[6]) + fabs(A[7]) + fabs(A[11]);
+        if (sum == 0.0) break;
+        const double tresh = (iter < 3) ? 0.2 * sum / 16. : 0.0;
+        jacobi_rotate_4x4<0, 1>(A, U, D, Z, iter, tresh);
+        jacobi_rotate_4x4<0, 2>(A, U, D, Z, iter, tresh);
+        jacobi_rotate_4x4<0, 3>(A, U, D, Z, iter, tresh);
+        jacobi_rotate_4x4<1, 2>(A, U, D, Z, iter, tresh);
+        jacobi_rotate_4x4<1, 3>(A, U, D, Z, iter, tresh);
+        jacobi_rotate_4x4<2, 3>(A, U, D, Z, iter, tresh);
+        B[0] += Z[0]; B[1] += Z[1]; B[2] += Z[2]; B[3] += Z[3];
+        D[0] = B[0]; D[1] = B[1]; D[2] = B[2]; D[3] = B[3];
+        Z[0] = Z[1] = Z[2] = Z[3] = 0;
+    }
+    // eigenvector of the largest eigenvalue, the first one on ties.  (The index is chosen first and the four components are
+    // selected from values: chosen through pointers into U, the matrix would live in scratch.)
+    int i_ev = 0;
+    double ev_max = D[0];
+    if (D[1] > ev_max) { ev_max = D[1]; i_ev = 1; }
+    if (D[2] > ev_max) { ev_max = D[2]; i_ev = 2; }
+    if (D[3] > ev_max) { ev_max = D[3]; i_ev = 3; }
+    const double q0 = i_ev == 0 ? U[0] : i_ev == 1 ? U[1] : i_ev == 2 ? U[2] : U[3];
+    const double q1 = i_ev == 0 ? U[4] : i_ev == 1 ? U[5] : i_ev == 2 ? U[6] : U[7];
+    const double q2 = i_ev == 0 ? U[8] : i_ev == 1 ? U[9] : i_ev == 2 ? U[10] : U[11];
+    const double q3 = i_ev == 0 ? U[12] : i_ev == 1 ? U[13] : i_ev == 2 ? U[14] : U[15];
+    const double q02 = q0 * q0, q12 = q1 * q1, q22 = q2 * q2, q32 = q3 * q3;
+    const double q0_1 = q0 * q1, q0_2 = q0 * q2, q0_3 = q0 * q3;
+    const double q1_2 = q1 * q2, q1_3 = q1 * q3, q2_3 = q2 * q3;
+    R[0] = q02 + q12 - q22 - q32; R[1] = 2. * (q1_2 - q0_3);    R[2] = 2. * (q1_3 + q0_2);
+    R[3] = 2. * (q1_2 + q0_3);    R[4] = q02 + q22 - q12 - q32; R[5] = 2. * (q2_3 - q0_1);
+    R[6] = 2. * (q1_3 - q0_2);    R[7] = 2. * (q2_3 + q0_1);    R[8] = q02 + q32 - q12 - q22;
+    T[0] = Cex - (R[0] * Csx + R[1] * Csy + R[2] * Csz);
+    T[1] = Cey - (R[3] * Csx + R[4] * Csy + R[5] * Csz);
+    T[2] = Cez - (R[6] * Csx + R[7] * Csy + R[8] * Csz);
+}
+
+// which alignment p3p_candidate / p3p_4pt use (a type, so that the choice is made at compile time)
+struct AlignTriad {
+    static ESAC_HD void run(V3 P0, V3 P1, V3 P2, V3 Q0, V3 Q1, V3 Q2, double R[9], double T[3]) { align_triangles(P0, P1, P2, Q0, Q1, Q2, R, T); }
+};
+struct AlignHorn {
+    static ESAC_HD void run(V3 P0, V3 P1, V3 P2, V3 Q0, V3 Q1, V3 Q2, double R[9], double T[3]) { align_horn(P0, P1, P2, Q0, Q1, Q2, R, T); }
+};
+
 // 4-point P3P (Gao, Hou, Tang, Cheng, PAMI 2003; main branch): up to four poses
 // from points 0..2, the one with the smallest reprojection error of point 3 wins.
 // Split in two so that the (up to four) candidates can be evaluated by different lanes: p3p_setup = everything up to
@@ -474,7 +595,8 @@ ESAC_HD bool p3p_candidate_lengths(const P3PSetup& S, double x, double& X, doubl
     return true;
 }
 
-// candidate of root x: false when it is not a valid solution
+// candidate of root x: false when it is not a valid solution.  Align: AlignTriad (default) or AlignHorn
+template <class Align = AlignTriad>
 ESAC_HD bool p3p_candidate(const P3PSetup& S, double x, const V3 P[4], const double mu3_px, const double mv3_px,
                            const Cam& cam, double R[9], double T[3], double& reproj) {
     double X, Y, Z;
@@ -482,7 +604,7 @@ ESAC_HD bool p3p_candidate(const P3PSetup& S, double x, const V3 P[4], const dou
     const V3 Q0 = {X * S.mu[0], X * S.mv[0], X * S.mk[0]};
     const V3 Q1 = {Y * S.mu[1], Y * S.mv[1], Y * S.mk[1]};
     const V3 Q2 = {Z * S.mu[2], Z * S.mv[2], Z * S.mk[2]};
-    align_triangles(P[0], P[1], P[2], Q0, Q1, Q2, R, T);
+    Align::run(P[0], P[1], P[2], Q0, Q1, Q2, R, T);
     const double X3p = R[0] * P[3].x + R[1] * P[3].y + R[2] * P[3].z + T[0];
     const double Y3p = R[3] * P[3].x + R[4] * P[3].y + R[5] * P[3].z + T[1];
     const double Z3p = R[6] * P[3].x + R[7] * P[3].y + R[8] * P[3].z + T[2];
@@ -493,6 +615,7 @@ ESAC_HD bool p3p_candidate(const P3PSetup& S, double x, const V3 P[4], const dou
 }
 
 // obj: 4 scene points, img: 4 pixel positions.  Returns false when there is no solution.
+template <class Align = AlignTriad>
 ESAC_HD bool p3p_4pt(const V3 P[4], const double mu_px[4], const double mv_px[4], const Cam& cam,
                                         double Rbest[9], double Tbest[3], double* best_reproj = nullptr) {
     P3PSetup S;
@@ -505,7 +628,7 @@ ESAC_HD bool p3p_4pt(const V3 P[4], const double mu_px[4], const double mv_px[4]
     for (int i = 0; i < S.n; i++) {
         const double x = (i == 0) ? S.x[0] : (i == 1) ? S.x[1] : (i == 2) ? S.x[2] : S.x[3];
         double R[9], T[3], reproj;
-        if (!p3p_candidate(S, x, P, mu_px[3], mv_px[3], cam, R, T, reproj)) continue;
+        if (!p3p_candidate<Align>(S, x, P, mu_px[3], mv_px[3], cam, R, T, reproj)) continue;
         if (!have || min_reproj > reproj) {
             have = true;
             min_reproj = reproj;

@@ -152,10 +152,12 @@ __device__ __forceinline__ double pow10_int(int k) {
 // the trial, with the same iteration count (rejected trials do not count) and the re-fit over either way.  Inside the band
 // (err <= prev (1 + 8 eps)) such a trial is therefore ACCEPTED; a clear increase is rejected as ever, and trials that do
 // not end their re-fit keep the reference's comparison (an acceptance there would change lambda's course).
-__device__ __forceinline__ bool trial_rejected(double err2, double prev2, bool ends_refit) {
+// strict (ESAC_FLAG_STRICT_REFERENCE, a word of the call's flags): no such exception -- every trial is the reference's comparison
+// alone, sqrt(err2) > sqrt(prev2), and a converged trial inside the band goes up the lambda ladder when the roots say so.
+__device__ __forceinline__ bool trial_rejected(double err2, double prev2, bool ends_refit, bool strict) {
     if (!(err2 > prev2)) return false;
     if (err2 > prev2 * (1.0 + 8.0 * DBL_EPSILON)) return true;
-    if (ends_refit) return false;
+    if (ends_refit && !strict) return false;
     asm volatile("; norms a few ulp apart");  // (keeps the two square roots BEHIND the branch: as plain arithmetic they are
                                               // if-converted and run on every pass, ~45 instructions)
     return sqrt(err2) > sqrt(prev2);

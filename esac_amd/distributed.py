@@ -343,6 +343,9 @@ def forward_sharded_once(engine, scene_coords, hyp_assign_full, params_kw, group
     ha_full = hyp_assign_full
     n_total = int(ha_full.shape[0])
     params_kw = dict(params_kw)
+    if params_kw.get("strict_reference"):
+        # (the reference's rule on NaN scores looks at EVERY hypothesis' score: a shard cannot apply it)
+        raise ValueError("forward_sharded: the sharded forward has no strict mode (strict_reference)")
     total_experts = params_kw.pop("total_experts", None)
     E, _, H, W = scene_coords.shape
     dev = engine.device

@@ -67,8 +67,9 @@ def pose_file_line(name, out_pose):
 @torch.no_grad()
 def localize(image, gating, experts, focal_length, hypotheses=256, threshold=10.0, inlier_alpha=100.0,
              inlier_beta=0.5, max_reprojection=100.0, subsample=8, expert_selection=False, oracle_expert=None,
-             generator=None):
+             generator=None, strict_reference=False):
     """One iteration of the reference test loop (test_esac.py:145-207) for `image` [1,3,H,W] on the GPU.
+    strict_reference: this call follows the reference where the default knowingly differs (esac.set_strict_reference).
 
     gating(image) -> log-probabilities [1,E]; experts[e](image) -> scene coordinates [1,3,H/s,W/s].
     Returns dict(pose [4,4] float32 cpu, expert, active_experts, gating_probs (device), time_s, prediction, hyp_assignment
@@ -96,8 +97,13 @@ def localize(image, gating, experts, focal_length, hypotheses=256, threshold=10.
         if on:
             prediction[e] = experts[e](image)[0]
     out_pose = torch.zeros(4, 4)
-    winning_expert = api.forward(prediction, e_hyps, out_pose, 0, 0, float(focal_length), pp_x, pp_y, threshold,
-                                 inlier_alpha, inlier_beta, max_reprojection, subsample)
+    strict_before = api._state["strict_reference"]
+    api.set_strict_reference(strict_before or strict_reference)
+    try:
+        winning_expert = api.forward(prediction, e_hyps, out_pose, 0, 0, float(focal_length), pp_x, pp_y, threshold,
+                                     inlier_alpha, inlier_beta, max_reprojection, subsample)
+    finally:
+        api.set_strict_reference(strict_before)
     return dict(pose=out_pose, expert=winning_expert, active_experts=int(sum(active)), gating_probs=gating_probs,
                 time_s=time.time() - start, prediction=prediction, hyp_assignment=e_hyps)
 

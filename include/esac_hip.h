@@ -96,7 +96,9 @@ typedef struct esac_hip_frame_cam {
  * loop, esac_util.h:152-223, try by try).  The default route screens the tries of long searches (wrong-expert hypotheses)
  * with a one-sided fp32 test first and decides only what the screen cannot rule out; the accepted
  * try is the same either way -- this flag is the guaranteed route, several times slower on such hypotheses, like
- * ESAC_FLAG_EXACT_SCORES for the scores. */
+ * ESAC_FLAG_EXACT_SCORES for the scores.  The P3P of either route aligns the two triangles with orthonormal triads and Newton
+ * steps, not with the reference's eigen-solve: on collinear base points and ill-conditioned slivers the two can accept different
+ * tries.  ESAC_FLAG_STRICT_REFERENCE is the route with the reference's alignment. */
 #define ESAC_FLAG_EXACT_SAMPLING 16
 /* d_scores_out is indexed by GLOBAL hypothesis index (d_hyp_index[i], or hyp_offset + i) instead of by local position:
  * a multi-GPU shard writes its scores straight into its slots of the exchange buffer. */
@@ -114,6 +116,28 @@ typedef struct esac_hip_frame_cam {
  * needs no co-residency of several workgroups.  What a blocking call falls back to by itself after a team time-out; a caller of
  * ASYNCHRONOUS calls (the multi-GPU exchange: esac_hip_pick_record returned -12) sets it to run the frame again. */
 #define ESAC_FLAG_REFINE_SOLO 128
+/* The reference, as written, in the three places where the default knowingly differs -- for validating a
+ * port, chasing a disagreement with the CPU code or regenerating published numbers on the device:
+ *   - P3P alignment: Horn's unit-quaternion method with a cyclic Jacobi eigen-solve of the 4x4 (operation by operation the
+ *     oracle's restatement) instead of triads + Newton steps, so collinear base points and ill-conditioned minimal sets give the
+ *     reference's pose and the sampling loop accepts the reference's try;
+ *   - non-finite scene coordinates: std::min(l, maxReproj) lets a NaN error through (esac_util.h:358), every score of that
+ *     expert's hypotheses is NaN, softMax makes every probability NaN, the entropy is 0 and draw keeps hypothesis 0, which is
+ *     refined (default: such a cell is an outlier at maxReproj);
+ *   - LM: a trial is rejected iff sqrt(err2) > sqrt(prev2), also a converged one whose two norms are a few ulp apart (default:
+ *     accepted inside 8 eps when it ends its re-fit).
+ * Implies ESAC_FLAG_EXACT_SCORES | ESAC_FLAG_EXACT_SAMPLING and the serial route: every try solved in fp64 without the fp32
+ * screen, every hypothesis scored in reference arithmetic, no speculative straggler chain, the selection in a launch of its own.
+ * It costs what those two flags cost plus the eigen-solve in every candidate of every try: measured on an MI355X, 1.45 times
+ * the call with the two exact flags at 1 expert / 256 hypotheses (0.137 against 0.094 ms), 4.2 times at 10 experts / 1024
+ * hypotheses (2.23 against 0.54 ms); it is a verification route, not a fast one.
+ * It does NOT pin OpenCV's own internals: the oracle restates the published algorithms (Gao P3P, Horn, Numerical Recipes'
+ * jacobi, CvLevMarq), and libm's last bits (pow, acos, cos) differ between host and device, so a try that rounding decides may
+ * still differ.
+ * Honoured by esac_hip_forward, esac_hip_forward_batch and esac_hip_forward_batch_cams.  Combined with ESAC_FLAG_SCORE_TILED,
+ * ESAC_FLAG_SCORE_STREAM or ESAC_FLAG_AUTO_EXACT it is an argument error (-4); esac_hip_backward* return -4 with it: the
+ * training path has no strict mode. */
+#define ESAC_FLAG_STRICT_REFERENCE 256
 
 #define ESAC_DEFAULT_MARGIN 1e-3f
 
