@@ -54,6 +54,7 @@ FLAG_EXACT_SCORES, FLAG_SCORE_TILED, FLAG_SCORE_STREAM, FLAG_PACK_MAPS, FLAG_EXA
 FLAG_AUTO_EXACT = 64
 FLAG_REFINE_SOLO = 128
 FLAG_STRICT_REFERENCE = 256  # the reference's rule in P3P alignment, NaN scores and the LM trial test (include/esac_hip.h)
+FLAG_STRICT_TRAINING = 512  # the training path's strict mode: esac_hip_backward* only (include/esac_hip.h)
 WAIT_SPIN, WAIT_YIELD, WAIT_BLOCK = 0, 1, 2
 DEBUG_ERROR_IMAGE, DEBUG_COOP_STALL, DEBUG_TEAM_SPREAD, DEBUG_NO_SPECULATION, DEBUG_SPEC_SECOND_BEST, DEBUG_SPEC_LOSE_CHAIN = 1, 2, 4, 8, 16, 32
 
@@ -226,7 +227,11 @@ class Engine:
     def make_params(self, E, H, W, N, shift_x=0, shift_y=0, focal=525.0, ppx=320.0, ppy=240.0, inlier_thresh=10.0,
                     inlier_alpha=100.0, inlier_beta=0.5, max_reproj=100.0, sub_sampling=8, seed=1305, call=0,
                     max_tries=0, max_ref_steps=-1, hyp_offset=0, rescore_margin=0.0, exact_scores=False, score_shape="auto", pack_maps=False,
-                    exact_sampling=False, scores_by_index=False, expert_base=0, refine_solo=False, strict_reference=False):
+                    exact_sampling=False, scores_by_index=False, expert_base=0, refine_solo=False, strict_reference=False,
+                    strict_training=False):
+        if strict_training and (strict_reference or exact_scores == "auto" or score_shape != "auto"):
+            # strict_training is the training path's flag (esac_hip_backward*), strict_reference the forward path's: never both
+            raise ValueError("strict_training cannot be combined with strict_reference, exact_scores='auto' or score_shape=%r" % (score_shape,))
         if strict_reference and (exact_scores == "auto" or score_shape != "auto"):
             # (what the C ABI answers with -4: strict mode scores every hypothesis in reference arithmetic)
             raise ValueError("strict_reference cannot be combined with exact_scores='auto' or score_shape=%r" % (score_shape,))
@@ -247,6 +252,8 @@ class Engine:
             (FLAG_REFINE_SOLO if refine_solo else 0)
         if strict_reference:  # implies the two guaranteed routes
             p.flags |= FLAG_STRICT_REFERENCE | FLAG_EXACT_SCORES | FLAG_EXACT_SAMPLING
+        if strict_training:  # (the library implies the two routes itself; set here so that the flag word says what runs)
+            p.flags |= FLAG_STRICT_TRAINING | FLAG_EXACT_SCORES | FLAG_EXACT_SAMPLING
         p.expert_base = int(expert_base)
         self._shape = (int(N), int(H), int(W))
         return p
@@ -576,7 +583,7 @@ class Engine:
 # The reference keeps a static RNG whose state advances from call to call
 # (thread_rand.cpp:4-5); here that state is (seed, call counter).
 _state = {"seed": 1305, "call": 0, "engines": {}, "last": None, "max_tries": 0, "max_ref_steps": -1, "fwd_cache": {},
-          "exact_scores": None, "exact_sampling": False, "strict_reference": False}
+          "exact_scores": None, "exact_sampling": False, "strict_reference": False, "strict_training": False}
 
 
 def set_seed(seed, call=0):
@@ -615,6 +622,14 @@ def set_strict_reference(on):
     CvLevMarq trial test.  Implies exact scores and exact sampling; a verification route, several times slower.  backward() and
     backward_batch() raise ValueError while it is on: the training path has no strict mode."""
     _state["strict_reference"] = bool(on)
+
+
+def set_strict_training(on):
+    """True: backward() and backward_batch() follow the reference in every stage where the default knowingly differs
+    (ESAC_FLAG_STRICT_TRAINING): Horn / Jacobi alignment in the sampler and in the 18 perturbed solves of dPNP, NaN scores from
+    non-finite scene coordinates (the call returns a NaN loss and NaN gradients instead of raising), the plain CvLevMarq trial
+    test in the slot refinement, the SVD pseudo-inverse on every slot.  A verification route; forward() ignores it."""
+    _state["strict_training"] = bool(on)
 
 
 def _no_strict_training(who):
@@ -834,7 +849,8 @@ def backward(sceneCoordinates, outGradients, hypAssignment, gtPose, wLossRot, wL
             raise RuntimeError("esac.backward: hypAssignment values must lie in [0,%d), found [%d,%d]" % (E, lo, hi))
     p = eng.make_params(E, H, W, N, shiftX, shiftY, focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha,
                         inlierBeta, maxReproj, subSampling, seed=_state["seed"], call=_state["call"],
-                        max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"])
+                        max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"],
+                        strict_training=_state["strict_training"])
     _state["call"] += 1
     in_place = outGradients.is_cuda and outGradients.is_contiguous() and outGradients.device == eng.device
     grads = outGradients if in_place else outGradients.to(eng.device).contiguous()
@@ -879,7 +895,8 @@ def backward_batch(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLoss
     eng = engine(sceneCoordinates.device.index if sceneCoordinates.is_cuda else None)
     p = eng.make_params(E, H, W, N, shiftX, shiftY, focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha,
                         inlierBeta, maxReproj, subSampling, seed=_state["seed"], call=_state["call"],
-                        max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"])
+                        max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"],
+                        strict_training=_state["strict_training"])
     _state["call"] += B
     in_place = outGradients.is_cuda and outGradients.is_contiguous() and outGradients.device == eng.device
     grads = outGradients if in_place else outGradients.to(eng.device).contiguous()

@@ -294,4 +294,88 @@ ESAC_HD void pinv_sym6_jacobi(const double U21[21], double Ainv[36]) {
     }
 }
 
+// The same pseudo-inverse with ROLLED loops over three 6x6 matrices in memory the caller provides (the device: LDS; A, V, out: 36
+// doubles each): a few hundred bytes of code and no registers beyond the loop's own, for the one lane that runs it inside
+// k_bwd_paths (esac_backward.hip: pinv_sym6_lds).  Operation by operation pinv_sym6_jacobi and the oracle's pinv_sym6 / jacobi_sym.
+ESAC_HD void pinv_sym6_rolled(const double (&U21)[21], double* A, double* V, double* out) {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = i; j < 6; j++) {
+            A[i * 6 + j] = U21[k];
+            A[j * 6 + i] = U21[k];
+            k++;
+        }
+    for (int i = 0; i < 36; i++) V[i] = (i % 7 == 0) ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 60; sweep++) {
+        double off = 0;
+        for (int i = 0; i < 6; i++)
+            for (int j = i + 1; j < 6; j++) off += A[i * 6 + j] * A[i * 6 + j];
+        if (off == 0) break;
+        for (int p = 0; p < 6; p++)
+            for (int q = p + 1; q < 6; q++) {
+                const double apq = A[p * 6 + q];
+                const double theta = (A[q * 6 + q] - A[p * 6 + p]) / (2 * apq);
+                double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1));
+                if (!(fabs(theta) <= 1.7976931348623157e308)) t = 0;  // apq negligible (theta = inf / nan)
+                if (apq == 0) t = 0;                                   // identity rotation = the reference's `continue`
+                const double c = 1 / sqrt(t * t + 1), sn = t * c;
+                for (int m = 0; m < 6; m++) {
+                    const double akp = A[m * 6 + p], akq = A[m * 6 + q];
+                    A[m * 6 + p] = c * akp - sn * akq;
+                    A[m * 6 + q] = sn * akp + c * akq;
+                }
+                for (int m = 0; m < 6; m++) {
+                    const double apk = A[p * 6 + m], aqk = A[q * 6 + m];
+                    A[p * 6 + m] = c * apk - sn * aqk;
+                    A[q * 6 + m] = sn * apk + c * aqk;
+                }
+                for (int m = 0; m < 6; m++) {
+                    const double vkp = V[m * 6 + p], vkq = V[m * 6 + q];
+                    V[m * 6 + p] = c * vkp - sn * vkq;
+                    V[m * 6 + q] = sn * vkp + c * vkq;
+                }
+            }
+    }
+    double thresh = 0;
+    for (int i = 0; i < 6; i++) thresh += fabs(A[i * 7]);
+    thresh *= 2 * 2.220446049250313e-16;
+    for (int i = 0; i < 36; i++) out[i] = 0;
+    for (int m = 0; m < 6; m++) {
+        const double w = A[m * 7];
+        if (!(fabs(w) > thresh)) continue;
+        for (int i = 0; i < 6; i++)
+            for (int j = 0; j < 6; j++) out[i * 6 + j] += V[i * 6 + m] * V[j * 6 + m] / w;
+    }
+}
+
+// dPNP of the 4-point solver (esac_derivative.h:128-185): the solve with coordinate q (point q / 3, axis q % 3; q < 9) of the FLOAT
+// object points moved by +eps (minus = false) or -eps.  The reference perturbs in place (+eps, -2 eps, +eps), which does not
+// always restore the float value: coordinates handled before q carry that residue into this solve.  Align: the alignment of the
+// 4-point solver (AlignTriad: the default training path, AlignHorn: ESAC_FLAG_STRICT_TRAINING).  false: no solution.
+template <class Align>
+ESAC_HD bool dpnp_solve(const float (&obj_in)[12], const double (&mu)[4], const double (&mv)[4], const Cam& cam, int q, bool minus,
+                        double sol[6]) {
+    const float eps = 0.001f;
+    float obj[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) obj[k] = obj_in[k];
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        const float up = obj[k] + eps;
+        const float down = up - 2 * eps;
+        const float back = down + eps;
+        obj[k] = k < q ? back : (k == q ? (minus ? down : up) : obj[k]);
+    }
+    V3 Pt[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) Pt[j] = V3{(double)obj[3 * j], (double)obj[3 * j + 1], (double)obj[3 * j + 2]};
+    double Rp[9], Tp[3];
+    if (!p3p_4pt<Align>(Pt, mu, mv, cam, Rp, Tp)) return false;
+    rodrigues_mat2vec(Rp, sol);
+    sol[3] = Tp[0]; sol[4] = Tp[1]; sol[5] = Tp[2];
+    return true;
+}
+
 }  // namespace esac

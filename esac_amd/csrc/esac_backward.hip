@@ -29,7 +29,12 @@ constexpr int BWD_B = 512;  // threads per slot in the gradient kernels: 8 wavef
 
 // ================================================================= K5: softmax + ordered selection
 // BATCH: esac_hip_backward_batch -- one workgroup per frame, the batch-wide overflow word, the frame's assignment check
-template <int B, bool BATCH>
+// STRICT (ESAC_FLAG_STRICT_TRAINING): the reference on NaN scores (k_rescore_strict lets a non-finite coordinate through).  softMax
+// divides by a NaN sum: EVERY probability is NaN, the entropy is 0 (`dist > 0` is false), the expected loss is NaN; no hypothesis
+// is below PROB_THRESH (`NaN < t` is false), so the reference carries all N through its loops and adds NaN-weighted slabs: every
+// gradient entry of every expert that owns a hypothesis ends as NaN.  Here that end state is produced directly: nothing is
+// selected (no slot, no refinement, no slab), n_sel[3] = 1 tells k_bwd_accumulate_strict to store the NaNs.
+template <int B, bool BATCH, bool STRICT = false>
 __global__ __launch_bounds__(B) void k_bwd_select(KArgs a) {
     __shared__ double s_part[2 * (B / 64)];
     __shared__ double s_tot[2];
@@ -69,6 +74,7 @@ __global__ __launch_bounds__(B) void k_bwd_select(KArgs a) {
     for (int i = threadIdx.x; i < a.N; i += B) acc[0] += exp(a.scores[i] - m);
     block_sum<2, B>(acc, s_part, s_tot);
     const double sum = acc[0];
+    const bool poisoned = STRICT && sum != sum;  // (workgroup-uniform: block_sum hands every lane the same total)
     // probabilities, entropy, the pose every unselected hypothesis keeps, and the ordered selection:
     // rounds of B consecutive hypotheses, ballot prefix inside a wavefront, wavefront offsets through LDS
     double ent = 0;
@@ -81,7 +87,7 @@ __global__ __launch_bounds__(B) void k_bwd_select(KArgs a) {
             if (p > 0) ent -= p * log2(p);
 #pragma unroll
             for (int k = 0; k < 6; k++) a.bwd.ref_hyps[(size_t)i * 6 + k] = a.hyps[(size_t)i * 6 + k];
-            pick = !(p < kProbThresh);
+            pick = !(p < kProbThresh) && !poisoned;
         }
         const unsigned long long bal = __ballot(pick);
         if (lane == 0) s_wcount[wave] = __popcll(bal);
@@ -105,6 +111,7 @@ __global__ __launch_bounds__(B) void k_bwd_select(KArgs a) {
     block_sum<2, B>(acc, s_part, s_tot);
     if (threadIdx.x == 0) {
         if (BATCH) a.bwd.n_sel[2] = bad != 0;
+        if (STRICT) a.bwd.n_sel[3] = poisoned ? 1 : 0;
         a.bwd.n_sel[0] = s_base < a.bwd.cap ? s_base : a.bwd.cap;
         a.bwd.n_sel[1] = s_base;  // unclamped: > cap tells the host to grow the slot workspace and run the call again
         if (BATCH) atomicMax(a.bwd.sel_max, s_base);  // a batch: the accumulation of every frame looks at the largest
@@ -182,65 +189,15 @@ __device__ __forceinline__ void pinv_sym6_lds(const double (&U21)[21], double (&
     double* V = lds + 36;   // [6][6]
     double* out = lds + 72; // [6][6]
     __syncthreads();
-    if (threadIdx.x == 0) {
-        int k = 0;
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-#pragma unroll
-            for (int j = i; j < 6; j++) {
-                A[i * 6 + j] = U21[k];
-                A[j * 6 + i] = U21[k];
-                k++;
-            }
-        for (int i = 0; i < 36; i++) V[i] = (i % 7 == 0) ? 1.0 : 0.0;
-        for (int sweep = 0; sweep < 60; sweep++) {
-            double off = 0;
-            for (int i = 0; i < 6; i++)
-                for (int j = i + 1; j < 6; j++) off += A[i * 6 + j] * A[i * 6 + j];
-            if (off == 0) break;
-            for (int p = 0; p < 6; p++)
-                for (int q = p + 1; q < 6; q++) {
-                    const double apq = A[p * 6 + q];
-                    const double theta = (A[q * 6 + q] - A[p * 6 + p]) / (2 * apq);
-                    double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1));
-                    if (!(fabs(theta) <= 1.7976931348623157e308)) t = 0;  // apq negligible (theta = inf / nan)
-                    if (apq == 0) t = 0;                                   // identity rotation = the reference's `continue`
-                    const double c = 1 / sqrt(t * t + 1), sn = t * c;
-                    for (int m = 0; m < 6; m++) {
-                        const double akp = A[m * 6 + p], akq = A[m * 6 + q];
-                        A[m * 6 + p] = c * akp - sn * akq;
-                        A[m * 6 + q] = sn * akp + c * akq;
-                    }
-                    for (int m = 0; m < 6; m++) {
-                        const double apk = A[p * 6 + m], aqk = A[q * 6 + m];
-                        A[p * 6 + m] = c * apk - sn * aqk;
-                        A[q * 6 + m] = sn * apk + c * aqk;
-                    }
-                    for (int m = 0; m < 6; m++) {
-                        const double vkp = V[m * 6 + p], vkq = V[m * 6 + q];
-                        V[m * 6 + p] = c * vkp - sn * vkq;
-                        V[m * 6 + q] = sn * vkp + c * vkq;
-                    }
-                }
-        }
-        double thresh = 0;
-        for (int i = 0; i < 6; i++) thresh += fabs(A[i * 7]);
-        thresh *= 2 * 2.220446049250313e-16;
-        for (int i = 0; i < 36; i++) out[i] = 0;
-        for (int m = 0; m < 6; m++) {
-            const double w = A[m * 7];
-            if (!(fabs(w) > thresh)) continue;
-            for (int i = 0; i < 6; i++)
-                for (int j = 0; j < 6; j++) out[i * 6 + j] += V[i * 6 + m] * V[j * 6 + m] / w;
-        }
-    }
+    if (threadIdx.x == 0) pinv_sym6_rolled(U21, A, V, out);  // (bwd_math.hpp: host + device, the CPU suite runs it against the oracle)
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < 36; i++) Ainv[i] = out[i];
     __syncthreads();
 }
 
-template <int B>
+// STRICT (ESAC_FLAG_STRICT_TRAINING): the pseudo-inverse on EVERY slot, as the reference computes (J^T J).inv(DECOMP_SVD)
+template <int B, bool STRICT>
 __device__ __forceinline__ void bwd_path1(const KArgs& a, int slot, double* s_part, double* s_tot, double* s_max) {
     if (slot >= a.bwd.n_sel[0]) return;
     const int h = a.bwd.sel[slot];
@@ -278,7 +235,8 @@ __device__ __forceinline__ void bwd_path1(const KArgs& a, int slot, double* s_pa
     }
     block_sum28<21, B>(U, s_part, s_tot);
     double Ainv[36];
-    if (!inv_spd6(U, Ainv)) pinv_sym6_lds(U, Ainv, s_part);  // workgroup-uniform: every lane holds the same sums
+    if (STRICT) pinv_sym6_lds(U, Ainv, s_part);
+    else if (!inv_spd6(U, Ainv)) pinv_sym6_lds(U, Ainv, s_part);  // workgroup-uniform: every lane holds the same sums
     double dL[6];
 #pragma unroll
     for (int k = 0; k < 6; k++) dL[k] = a.bwd.dloss[(size_t)slot * 6 + k];
@@ -333,7 +291,8 @@ __device__ __forceinline__ void bwd_path1(const KArgs& a, int slot, double* s_pa
 // reprojection error, and the four sampled cells through the pose (dPNP: central differences of the 4-point solver
 // with a float step of 1e-3, esac_derivative.h:128-185).  sum_cells (dRE * dErr/dPose) * dPose/dObj is linear in the
 // per-cell term, so the 6 pose-space sums are reduced first and multiplied with the 6x12 dPNP matrix once.
-template <int B>
+// STRICT (ESAC_FLAG_STRICT_TRAINING): the 18 perturbed solves align with Horn / Jacobi (bwd_math.hpp: dpnp_solve<AlignHorn>)
+template <int B, bool STRICT>
 __device__ __forceinline__ void bwd_path2(const KArgs& a, int slot, double* s_part, double* s_tot, double (*s_sol)[6], double* s_J, int& s_bad) {
     if (slot >= a.bwd.n_sel[0]) return;
     const int h = a.bwd.sel[slot];
@@ -363,26 +322,37 @@ __device__ __forceinline__ void bwd_path2(const KArgs& a, int slot, double* s_pa
             mu[j] = (double)cell_px(a, sxy[2 * j]);
             mv[j] = (double)cell_py(a, sxy[2 * j + 1]);
         }
-        // the reference perturbs in place (+eps, -2eps, +eps), which does not always restore the float value:
-        // coordinates handled before q carry that residue into this solve
+        if constexpr (STRICT) {
+            double sol[6];
+            if (dpnp_solve<AlignHorn>(obj, mu, mv, cam, q, minus, sol)) {
+                double* o = s_sol[threadIdx.x];
 #pragma unroll
-        for (int k = 0; k < 9; k++) {
-            const float up = obj[k] + eps;
-            const float down = up - 2 * eps;
-            const float back = down + eps;
-            obj[k] = k < q ? back : (k == q ? (minus ? down : up) : obj[k]);
-        }
-        V3 Pt[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) Pt[j] = V3{(double)obj[3 * j], (double)obj[3 * j + 1], (double)obj[3 * j + 2]};
-        double Rp[9], Tp[3], rvec[3];
-        if (p3p_4pt(Pt, mu, mv, cam, Rp, Tp)) {
-            rodrigues_mat2vec(Rp, rvec);
-            double* o = s_sol[threadIdx.x];
-            o[0] = rvec[0]; o[1] = rvec[1]; o[2] = rvec[2];
-            o[3] = Tp[0]; o[4] = Tp[1]; o[5] = Tp[2];
+                for (int k = 0; k < 6; k++) o[k] = sol[k];
+            } else {
+                atomicOr(&s_bad, 1);
+            }
         } else {
-            atomicOr(&s_bad, 1);
+            // the reference perturbs in place (+eps, -2eps, +eps), which does not always restore the float value:
+            // coordinates handled before q carry that residue into this solve
+#pragma unroll
+            for (int k = 0; k < 9; k++) {
+                const float up = obj[k] + eps;
+                const float down = up - 2 * eps;
+                const float back = down + eps;
+                obj[k] = k < q ? back : (k == q ? (minus ? down : up) : obj[k]);
+            }
+            V3 Pt[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) Pt[j] = V3{(double)obj[3 * j], (double)obj[3 * j + 1], (double)obj[3 * j + 2]};
+            double Rp[9], Tp[3], rvec[3];
+            if (p3p_4pt(Pt, mu, mv, cam, Rp, Tp)) {
+                rodrigues_mat2vec(Rp, rvec);
+                double* o = s_sol[threadIdx.x];
+                o[0] = rvec[0]; o[1] = rvec[1]; o[2] = rvec[2];
+                o[3] = Tp[0]; o[4] = Tp[1]; o[5] = Tp[2];
+            } else {
+                atomicOr(&s_bad, 1);
+            }
         }
     }
     __syncthreads();
@@ -454,7 +424,10 @@ __device__ __forceinline__ void bwd_path2(const KArgs& a, int slot, double* s_pa
 // cells, d E / d score), and with a few dozen slots either one is a chain one workgroup long on an otherwise empty chip: workgroups
 // [0, slots) take path I, [slots, 2 slots) path II -- 47 + 36 us in sequence became max(path I, path II), with no second stream
 // and no event between them (round 6 measured that variant: the fork and the join cost 7 us each).
-template <int B>
+// STRICT: ESAC_FLAG_STRICT_TRAINING, an instantiation of its own so that the default keeps its registers (250 VGPRs).  The strict
+// one fits the same budget (249, no scratch, two wavefronts per SIMD): one lane runs one solve at a time, the eigen-solve's 4x4s
+// live after the quartic's state has died
+template <int B, bool STRICT = false>
 __global__ __launch_bounds__(B) void k_bwd_paths(KArgs a) {
     __shared__ double s_part[28 * (B / 64) > 108 ? 28 * (B / 64) : 108];
     __shared__ double s_tot[28];
@@ -465,8 +438,8 @@ __global__ __launch_bounds__(B) void k_bwd_paths(KArgs a) {
     frame_view(a);  // (a batch: grid (2 slots, frames))
     bwd_frame_view(a, (int)blockIdx.y);
     const int slots = (int)gridDim.x >> 1;
-    if ((int)blockIdx.x < slots) bwd_path1<B>(a, (int)blockIdx.x, s_part, s_tot, s_max);
-    else                         bwd_path2<B>(a, (int)blockIdx.x - slots, s_part, s_tot, s_sol, s_J, s_bad);
+    if ((int)blockIdx.x < slots) bwd_path1<B, STRICT>(a, (int)blockIdx.x, s_part, s_tot, s_max);
+    else                         bwd_path2<B, STRICT>(a, (int)blockIdx.x - slots, s_part, s_tot, s_sol, s_J, s_bad);
 }
 
 // ================================================================= K9: ordered accumulation into the float tensor
@@ -474,7 +447,10 @@ __global__ __launch_bounds__(B) void k_bwd_paths(KArgs a) {
 // belongs to this expert (ballot prefix) together with their probabilities into LDS; then one thread per tensor
 // element walks that list with unconditional, coalesced slab loads (slabs are planar like the tensor), U loads in
 // flight, while the float `+=` chain itself stays in slot order.
-__global__ __launch_bounds__(256) void k_bwd_accumulate(KArgs a) {
+// STRICT (ESAC_FLAG_STRICT_TRAINING): a frame whose scores held a NaN (k_bwd_select<.., true>: n_sel[3]) -- every entry of every
+// expert that owns a hypothesis becomes NaN (the reference's float += of NaN-weighted slabs), the other experts' entries stay.
+template <bool STRICT>
+__device__ __forceinline__ void bwd_accumulate_body(const KArgs& a) {
     __shared__ int s_slot[ESAC_BWD_SLOTS_K];
     __shared__ double s_prob[ESAC_BWD_SLOTS_K];
     __shared__ int s_count;
@@ -490,7 +466,16 @@ __global__ __launch_bounds__(256) void k_bwd_accumulate(KArgs a) {
     const bool team_failed = a.bwd.team && __hip_atomic_load(a.coop_counter + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.bwd.team_tag;
     // A batch: ONE frame's overflow stops every frame (the host reruns all of them), so they all read the batch-wide maximum.
     const bool skip = (a.bwd.sel_max ? a.bwd.sel_max[0] : f.bwd.n_sel[1]) > a.bwd.cap || team_failed;
-    if (!skip) {
+    if (STRICT && !skip && f.bwd.n_sel[3] != 0) {  // (workgroup-uniform)
+        int mine = 0;
+        for (int h = threadIdx.x; h < f.N; h += blockDim.x) mine |= expert_of(f, h) == e;
+        const int owns = __syncthreads_or(mine);
+        const int rem = blockIdx.x * blockDim.x + threadIdx.x;
+        if (owns && rem < 3 * P) {
+            float* o = f.bwd.out_grad + (size_t)e * 3 * P + rem;
+            *o = *o + __builtin_nanf("");
+        }
+    } else if (!skip) {
         if (threadIdx.x < 64) {
             int count = 0;
             for (int base = 0; base < n_sel; base += 64) {
@@ -552,12 +537,21 @@ __global__ __launch_bounds__(256) void k_bwd_accumulate(KArgs a) {
         pin_deliver(a.result_pin + (size_t)fr * ESAC_PIN_DOUBLES, v);
     }
 }
+__global__ __launch_bounds__(256) void k_bwd_accumulate(KArgs a) { bwd_accumulate_body<false>(a); }
+__global__ __launch_bounds__(256) void k_bwd_accumulate_strict(KArgs a) { bwd_accumulate_body<true>(a); }
 
 // ---------------------------------------------------------------- launchers
 static inline int slot_grid(const KArgs& a) { return a.N < a.bwd.cap ? a.N : a.bwd.cap; }
 
 // (a.frames > 1: esac_hip_backward_batch -- frame b in grid row / layer b)
+static inline bool bwd_strict(const KArgs& a) { return (a.flags & ESAC_FLAG_STRICT_TRAINING_K) != 0; }
+
 void launch_bwd_select(const KArgs& a, hipStream_t s) {
+    if (bwd_strict(a)) {
+        if (a.bwd.gt_frames) hipLaunchKernelGGL((k_bwd_select<1024, true, true>), dim3(1, a.frames), dim3(1024), 0, s, a);
+        else                 hipLaunchKernelGGL((k_bwd_select<1024, false, true>), dim3(1), dim3(1024), 0, s, a);
+        return;
+    }
     if (a.bwd.gt_frames) hipLaunchKernelGGL((k_bwd_select<1024, true>), dim3(1, a.frames), dim3(1024), 0, s, a);
     else                 hipLaunchKernelGGL((k_bwd_select<1024, false>), dim3(1), dim3(1024), 0, s, a);
 }
@@ -566,11 +560,14 @@ void launch_bwd_loss(const KArgs& a, hipStream_t s) {
     else                 hipLaunchKernelGGL((k_bwd_loss<BWD_B, false>), dim3(1), dim3(BWD_B), 0, s, a);
 }
 void launch_bwd_paths(const KArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_bwd_paths<BWD_B>, dim3(2 * slot_grid(a), a.frames), dim3(BWD_B), 0, s, a);
+    if (bwd_strict(a)) hipLaunchKernelGGL((k_bwd_paths<BWD_B, true>), dim3(2 * slot_grid(a), a.frames), dim3(BWD_B), 0, s, a);
+    else               hipLaunchKernelGGL(k_bwd_paths<BWD_B>, dim3(2 * slot_grid(a), a.frames), dim3(BWD_B), 0, s, a);
 }
 void launch_bwd_accumulate(const KArgs& a, hipStream_t s) {
     const int per_expert = 3 * a.H * a.W;
-    hipLaunchKernelGGL(k_bwd_accumulate, dim3((unsigned)((per_expert + 255) / 256), a.E, a.frames), dim3(256), 0, s, a);
+    const dim3 grid((unsigned)((per_expert + 255) / 256), a.E, a.frames);
+    if (bwd_strict(a)) hipLaunchKernelGGL(k_bwd_accumulate_strict, grid, dim3(256), 0, s, a);
+    else               hipLaunchKernelGGL(k_bwd_accumulate, grid, dim3(256), 0, s, a);
 }
 
 }  // namespace esac

@@ -35,6 +35,7 @@ static_assert(ESAC_RES_SCORE == ESAC_RES_SCORE_K && ESAC_RES_HYP == ESAC_RES_HYP
                   ESAC_MAX_REF_STEPS == ESAC_MAX_REF_STEPS_K && ESAC_BWD_MAX_SLOTS == ESAC_BWD_SLOTS_K &&
                   ESAC_FLAG_EXACT_SCORES == ESAC_FLAG_EXACT_SCORES_K && ESAC_FLAG_EXACT_SAMPLING == ESAC_FLAG_EXACT_SAMPLING_K &&
                   ESAC_FLAG_SCORES_BY_INDEX == ESAC_FLAG_SCORES_BY_INDEX_K && ESAC_FLAG_STRICT_REFERENCE == ESAC_FLAG_STRICT_REFERENCE_K &&
+                  ESAC_FLAG_STRICT_TRAINING == ESAC_FLAG_STRICT_TRAINING_K &&
                   ESAC_REFINE_TEAM_MAX == ESAC_REFINE_TEAM_MAX_K &&
                   ESAC_REFINE_TEAM_DEFAULT == ESAC_REFINE_TEAM_DEFAULT_K &&
                   (ESAC_FLAG_AUTO_EXACT & (ESAC_FLAG_EXACT_SCORES | ESAC_FLAG_EXACT_SAMPLING | ESAC_FLAG_SCORES_BY_INDEX)) == 0,
@@ -468,8 +469,9 @@ static esac_hip_params with_cam(const esac_hip_params& p, const esac_hip_frame_c
 }
 
 // Validation: what the reference leaves to accessor<>() / OpenCV asserts.
+// training: the call is one of esac_hip_backward* (the only entry points that honour ESAC_FLAG_STRICT_TRAINING)
 static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign, const esac_hip_params* p, KArgs* out,
-                     int B = 1, long long sc_frame_stride = 0, int cam_frame = -1) {
+                     int B = 1, long long sc_frame_stride = 0, int cam_frame = -1, bool training = false) {
     if (!c) return fail(-1, "null context");
     if (!p) return fail(-1, "null params");
     if (!d_sc || !d_assign) return fail(-1, "null scene-coordinate or assignment pointer");
@@ -482,6 +484,14 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
     if ((p->flags & ESAC_FLAG_STRICT_REFERENCE) && (p->flags & (ESAC_FLAG_SCORE_TILED | ESAC_FLAG_SCORE_STREAM | ESAC_FLAG_AUTO_EXACT)))
         return fail(-4, "ESAC_FLAG_STRICT_REFERENCE cannot be combined with ESAC_FLAG_SCORE_TILED, ESAC_FLAG_SCORE_STREAM or ESAC_FLAG_AUTO_EXACT "
                         "(flags=%d): strict mode scores every hypothesis in reference arithmetic", p->flags);
+    if (p->flags & ESAC_FLAG_STRICT_TRAINING) {
+        if (p->flags & ESAC_FLAG_STRICT_REFERENCE)
+            return fail(-4, "ESAC_FLAG_STRICT_TRAINING cannot be combined with ESAC_FLAG_STRICT_REFERENCE (flags=%d): one is the training "
+                            "path's strict mode, the other the forward path's", p->flags);
+        if (!training)
+            return fail(-4, "ESAC_FLAG_STRICT_TRAINING is a flag of esac_hip_backward, esac_hip_backward_batch and esac_hip_backward_batch_cams "
+                            "(flags=%d): the forward path's strict mode is ESAC_FLAG_STRICT_REFERENCE", p->flags);
+    }
     if (int rc_cam = check_cam(p, p->shift_x, p->shift_y, p->focal, cam_frame)) return rc_cam;
     const int P = p->H * p->W;
     if (B < 1 || B > ESAC_MAX_BATCH) return fail(-4, "batch size %d outside [1,%d]", B, ESAC_MAX_BATCH);
@@ -528,6 +538,8 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
     a.samp_cap = (int)(((long long)c->capN * ESAC_SAMPLE_LIST_PER_HYP) > 0x7fffffffLL ? 0x7fffffff : (long long)c->capN * ESAC_SAMPLE_LIST_PER_HYP);
     a.flags = p->flags;
     if (a.flags & ESAC_FLAG_STRICT_REFERENCE) a.flags |= ESAC_FLAG_EXACT_SCORES | ESAC_FLAG_EXACT_SAMPLING;  // (implied)
+    // the training path's strict mode: the strict bit the samplers, k_rescore_strict and trial_rejected read, and the two exact routes
+    if (a.flags & ESAC_FLAG_STRICT_TRAINING) a.flags |= ESAC_FLAG_STRICT_REFERENCE | ESAC_FLAG_EXACT_SCORES | ESAC_FLAG_EXACT_SAMPLING;
     c->epoch += 1.0;  // every call gets its own epoch: result hand-off word and the tag of the status word
     a.epoch = c->epoch;
     a.sample_epoch = c->sample_epoch;  // launches that sample call mark_sampling() and overwrite this
@@ -1222,7 +1234,7 @@ extern "C" int esac_hip_backward(esac_hip_ctx* c, const float* d_sc, float* d_ou
         return fail(-4, "esac_hip_backward: the training path has no strict mode (ESAC_FLAG_STRICT_REFERENCE is a forward flag)");
     DeviceGuard guard(c->device);
     KArgs a;
-    int rc = make_args(c, d_sc, d_assign, p, &a);
+    int rc = make_args(c, d_sc, d_assign, p, &a, 1, 0, -1, true);
     if (rc) return rc;
     if (p->E > 65535) return fail(-4, "esac_hip_backward: at most 65535 experts (one grid row per expert in the accumulation kernel)");
     if (p->d_hyp_index || p->hyp_offset)
@@ -1373,9 +1385,9 @@ extern "C" int esac_hip_backward_batch_cams(esac_hip_ctx* c, int B, const float*
     int rc;
     if (h_cams) {
         const esac_hip_params p0 = with_cam(*p, h_cams[0]);
-        if ((rc = make_args(c, d_sc, d_assign, &p0, &a, 1, 0, 0))) return rc;
+        if ((rc = make_args(c, d_sc, d_assign, &p0, &a, 1, 0, 0, true))) return rc;
         if ((rc = stage_cams(c, &p0, h_cams, B, s))) return rc;  // (checks every record before the first launch)
-    } else if ((rc = make_args(c, d_sc, d_assign, p, &a, 1, 0))) {
+    } else if ((rc = make_args(c, d_sc, d_assign, p, &a, 1, 0, -1, true))) {
         return rc;
     }
     HIP_OK(hipMemcpyAsync(c->d_gt, c->h_gt, (size_t)B * 22 * sizeof(double), hipMemcpyHostToDevice, s));
@@ -1393,7 +1405,7 @@ extern "C" int esac_hip_backward_batch_cams(esac_hip_ctx* c, int B, const float*
         int nb = chunk_frames(cap, B - b0);
         esac_hip_params pc = h_cams ? with_cam(*p, h_cams[b0]) : *p;
         pc.call = p->call + (uint64_t)b0;
-        if ((rc = make_args(c, d_sc + (size_t)b0 * sc_frame_stride, d_assign + (size_t)b0 * N, &pc, &a, nb, sc_frame_stride))) return rc;
+        if ((rc = make_args(c, d_sc + (size_t)b0 * sc_frame_stride, d_assign + (size_t)b0 * N, &pc, &a, nb, sc_frame_stride, -1, true))) return rc;
         if (h_cams) a.cams = c->d_cams + b0;
         a.tstamps = nullptr;
         c->rt32_stale = false;

@@ -49,7 +49,8 @@ __device__ __forceinline__ void pin_deliver(double* pin, double v) {
 constexpr int ESAC_FLAG_EXACT_SCORES_K = 1;  // = ESAC_FLAG_EXACT_SCORES (include/esac_hip.h)
 constexpr int ESAC_FLAG_EXACT_SAMPLING_K = 16, ESAC_FLAG_SCORES_BY_INDEX_K = 32;  // = ESAC_FLAG_* (checked in esac_capi.hip)
 constexpr int ESAC_FLAG_STRICT_REFERENCE_K = 256;  // the reference's rule wherever the default knowingly differs (include/esac_hip.h)
-constexpr int ESAC_SELECT_SPLIT = 16;          // cell ranges (workgroups) per contender in k_select_rescore when H*W >= 32768
+constexpr int ESAC_FLAG_STRICT_TRAINING_K = 512;   // the training path's strict mode: the C ABI turns it into the strict bit above + this one
+constexpr int ESAC_SELECT_SPLIT = 16;         // cell ranges (workgroups) per contender in k_select_rescore when H*W >= 32768
 constexpr int ESAC_CAND_DOUBLES = 26;          // record parked with an accepted entry of the "maybe" list: 6 + 9 + 6 + 4 doubles (+1 pad)
 constexpr int ESAC_SAMPLE_LIST_PER_HYP = 16;   // capacity of the prescreen's global "maybe" list, per hypothesis in flight
 constexpr int ESAC_TILED_HC = 256;            // hypotheses per chunk of the tile-stationary score kernel

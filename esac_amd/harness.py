@@ -165,7 +165,7 @@ def clamp_probs(probs, n):
 
 def train_step(image, gt_pose, gating, experts, focal_length, hypotheses=256, threshold=10.0, inlier_alpha=100.0,
                inlier_beta=0.5, max_reprojection=100.0, subsample=8, weight_rot=1.0, weight_trans=100.0, loss_cut=100.0,
-               max_experts=-1, expert_selection=False, shift=None, generator=None):
+               max_experts=-1, expert_selection=False, shift=None, generator=None, strict_training=False):
     """One iteration of the end-to-end training loop (train_esac.py:104-192) up to and including
     `torch.autograd.backward`; the optimiser step stays with the caller (`ensemble.update`, train_esac.py:195).
 
@@ -175,6 +175,7 @@ def train_step(image, gt_pose, gating, experts, focal_length, hypotheses=256, th
       * `torch.exp(gating_log_probs).cpu()` (:129) is gone -- clamp / multinomial / histc run on the device, only the
         E activity flags and the loss value reach the host.
     gating(image) -> log-probabilities [1,E] (with grad); experts[e](image) -> [1,3,H/s,W/s] (with grad).
+    strict_training: this call's esac.backward follows the reference in every stage (esac.set_strict_training).
     Returns dict(loss, e_hyps, e_hist, prediction, prediction_gradients, gating_log_probs, pad)."""
     dev = image.device
     E = len(experts)
@@ -201,9 +202,14 @@ def train_step(image, gt_pose, gating, experts, focal_length, hypotheses=256, th
     outputs = [experts[e](image)[0] if on else torch.zeros((3, pred_h, pred_w), device=dev) for e, on in enumerate(active)]
     prediction = torch.stack(outputs)  # [E,3,h,w]; rows of inactive experts are zeros and never read
     prediction_gradients = torch.zeros_like(prediction)
-    loss = api.backward(prediction.detach(), prediction_gradients, e_hyps, torch.as_tensor(gt_pose, dtype=torch.float32).cpu(),
-                        weight_rot, weight_trans, loss_cut, pad_x, pad_y, float(focal_length), pp_x, pp_y, threshold,
-                        inlier_alpha, inlier_beta, max_reprojection, subsample)
+    strict_before = api._state["strict_training"]
+    api.set_strict_training(strict_before or strict_training)
+    try:
+        loss = api.backward(prediction.detach(), prediction_gradients, e_hyps, torch.as_tensor(gt_pose, dtype=torch.float32).cpu(),
+                            weight_rot, weight_trans, loss_cut, pad_x, pad_y, float(focal_length), pp_x, pp_y, threshold,
+                            inlier_alpha, inlier_beta, max_reprojection, subsample)
+    finally:
+        api.set_strict_training(strict_before)
     # gating gradients: REINFORCE-style, loss per drawn hypothesis (train_esac.py:171-177)
     if expert_selection:
         gating_grads = torch.zeros_like(gating_log_probs)
@@ -225,7 +231,7 @@ def train_step(image, gt_pose, gating, experts, focal_length, hypotheses=256, th
 
 def train_batch(images, gt_poses, gating, experts, focal_lengths, hypotheses=256, threshold=10.0, inlier_alpha=100.0,
                 inlier_beta=0.5, max_reprojection=100.0, subsample=8, weight_rot=1.0, weight_trans=100.0, loss_cut=100.0,
-                max_experts=-1, expert_selection=False, shifts=None, e_hyps=None, generator=None):
+                max_experts=-1, expert_selection=False, shifts=None, e_hyps=None, generator=None, strict_training=False):
     """The mini-batch form of `train_step`: B images through ONE `esac.backward_batch` with a shift and a focal length per
     image (train_esac.py:112 reads the focal length per image, :125 draws a new shift for every image), up to and including
     one `torch.autograd.backward`.
@@ -236,6 +242,7 @@ def train_batch(images, gt_poses, gating, experts, focal_lengths, hypotheses=256
     on the batch, the hypothesis assignment is drawn per frame on the device (or given: `e_hyps` [B,N]), and every expert that
     is active in at least one frame runs once on the batch: the rows of frames in which it is inactive are never read by the
     kernels and receive a zero gradient.  Only the B x E activity flags and the B losses reach the host.
+    strict_training: this call's esac.backward_batch follows the reference in every stage (esac.set_strict_training).
     Returns dict(losses (list of B floats), e_hyps [B,N], e_hist [B,E], prediction [B,E,3,h,w], prediction_gradients,
     gating_log_probs [B,E], pads (list of B pairs))."""
     dev = images.device
@@ -286,11 +293,16 @@ def train_batch(images, gt_poses, gating, experts, focal_lengths, hypotheses=256
     outputs = [experts[e](images) if on else torch.zeros((B, 3, pred_h, pred_w), device=dev) for e, on in enumerate(active_any)]
     prediction = torch.stack(outputs, dim=1)  # [B,E,3,h,w]
     prediction_gradients = torch.zeros_like(prediction)
-    losses = api.backward_batch(prediction.detach(), prediction_gradients, e_hyps.contiguous(),
-                                torch.as_tensor(np.asarray(gt_poses, np.float32) if not isinstance(gt_poses, torch.Tensor) else gt_poses,
-                                                dtype=torch.float32).cpu(),
-                                weight_rot, weight_trans, loss_cut, [p[0] for p in pads], [p[1] for p in pads], focals, pp_x, pp_y,
-                                threshold, inlier_alpha, inlier_beta, max_reprojection, subsample)
+    strict_before = api._state["strict_training"]
+    api.set_strict_training(strict_before or strict_training)
+    try:
+        losses = api.backward_batch(prediction.detach(), prediction_gradients, e_hyps.contiguous(),
+                                    torch.as_tensor(np.asarray(gt_poses, np.float32) if not isinstance(gt_poses, torch.Tensor) else gt_poses,
+                                                    dtype=torch.float32).cpu(),
+                                    weight_rot, weight_trans, loss_cut, [p[0] for p in pads], [p[1] for p in pads], focals, pp_x, pp_y,
+                                    threshold, inlier_alpha, inlier_beta, max_reprojection, subsample)
+    finally:
+        api.set_strict_training(strict_before)
     # gating gradients, per frame: REINFORCE-style, loss per drawn hypothesis (train_esac.py:171-177)
     loss_t = torch.tensor(losses, device=dev, dtype=torch.float32)
     if expert_selection:

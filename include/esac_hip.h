@@ -135,9 +135,23 @@ typedef struct esac_hip_frame_cam {
  * jacobi, CvLevMarq), and libm's last bits (pow, acos, cos) differ between host and device, so a try that rounding decides may
  * still differ.
  * Honoured by esac_hip_forward, esac_hip_forward_batch and esac_hip_forward_batch_cams.  Combined with ESAC_FLAG_SCORE_TILED,
- * ESAC_FLAG_SCORE_STREAM or ESAC_FLAG_AUTO_EXACT it is an argument error (-4); esac_hip_backward* return -4 with it: the
- * training path has no strict mode. */
+ * ESAC_FLAG_SCORE_STREAM or ESAC_FLAG_AUTO_EXACT it is an argument error (-4); esac_hip_backward* return -4 with it ("the
+ * training path has no strict mode" under THIS flag: its form for the training path is ESAC_FLAG_STRICT_TRAINING). */
 #define ESAC_FLAG_STRICT_REFERENCE 256
+/* The strict mode of the TRAINING path: every stage of esac_backward follows the reference where the default knowingly differs,
+ * so that the gradient of the four sampled cells of a hypothesis (central differences of the 4-point solver, step 1e-3: the two
+ * solvers' disagreement times 500) meets the bar of every other cell:
+ *   - sampling, scores, LM trial test: as under ESAC_FLAG_STRICT_REFERENCE (Horn / Jacobi alignment, NaN scores, plain test);
+ *   - path II: the 18 perturbed solves of dPNP use the Horn / Jacobi alignment;
+ *   - path I: (J^T J).inv(DECOMP_SVD) -- the cyclic-Jacobi pseudo-inverse -- on EVERY slot (default: LDL^T at full rank);
+ *   - a non-finite scene coordinate: every probability is NaN (softMax), the entropy is 0, the expected loss is NaN, no slot is
+ *     refined (h_out[1] = 0) and every gradient entry of every expert that owns a hypothesis becomes NaN, the other experts'
+ *     entries stay as they were -- what the reference's `+=` of NaN-weighted slabs leaves.  The call returns 0.
+ * Honoured by esac_hip_backward (blocking and asynchronous), esac_hip_backward_batch and esac_hip_backward_batch_cams.  An
+ * argument error (-4, before any launch) on every forward / phase entry point, and together with ESAC_FLAG_STRICT_REFERENCE.
+ * Inside the library it implies the exact-sampling and exact-score routes.  A verification route, several times slower where
+ * wrong-expert hypotheses search long (LAB_NOTES.md, "Strict training"). */
+#define ESAC_FLAG_STRICT_TRAINING 512
 
 #define ESAC_DEFAULT_MARGIN 1e-3f
 

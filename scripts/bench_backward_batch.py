@@ -7,6 +7,7 @@ mean number of slots (hypotheses with p >= PROB_THRESH) per frame.
 
     python scripts/bench_backward_batch.py [--batches 1,8,32,128] [--reps 5] [--configs cfg2,cfg3]
     python scripts/bench_backward_batch.py --only-batch 32 --configs cfg2 --reps 3   # one shape, e.g. under a kernel trace
+    python scripts/bench_backward_batch.py --strict-training  # the same measurement with ESAC_FLAG_STRICT_TRAINING
     python scripts/bench_backward_batch.py --per-frame-cams   # after each shared-camera line, the same frames and counters with a
                                                               # shift (|shift| <= sub/2) and a focal length per frame
 """
@@ -60,6 +61,8 @@ def main():
     ap.add_argument("--only-batch", type=int, default=0, help="time the batched call only, at this B")
     ap.add_argument("--per-frame-cams", action="store_true",
                     help="also time every (config, B) with a shift and a focal length per frame (one more JSON line, cams=per-frame)")
+    ap.add_argument("--strict-training", action="store_true",
+                    help="every call with ESAC_FLAG_STRICT_TRAINING (the verification route: each JSON line says strict_training=true)")
     args = ap.parse_args()
     eng = api.Engine(0)
     batches = [args.only_batch] if args.only_batch else [int(x) for x in args.batches.split(",")]
@@ -75,7 +78,8 @@ def main():
             def params(call, b=0):  # (a sequential call of a per-frame batch carries frame b's camera in its own params)
                 c = cams[b] if per_frame else cams[0]
                 return eng.make_params(E, H, W, cfg["N"], shift_x=int(c["shift_x"]), shift_y=int(c["shift_y"]), focal=float(c["focal"]),
-                                       ppx=float(c["ppx"]), ppy=float(c["ppy"]), sub_sampling=f0["sub"], inlier_alpha=100.0, call=call)
+                                       ppx=float(c["ppx"]), ppy=float(c["ppy"]), sub_sampling=f0["sub"], inlier_alpha=100.0, call=call,
+                                       strict_training=args.strict_training)
 
             def run_batch():
                 return eng.backward_batch(sc[:B], grads[:B], ha[:B], gts[:B], 1.0, 100.0, 100.0, params(0),
@@ -102,7 +106,7 @@ def main():
                 t_seq.append(time.perf_counter() - t0)
             line = {"config": name, "B": B, "E": E, "N": cfg["N"], "grid": "%dx%d" % (H, W), "cams": "per-frame" if per_frame else "shared",
                     "batch_ms_per_frame": round(1e3 * float(np.median(t_batch)) / B, 4),
-                    "slots_per_frame": round(float(out[:, 1].mean()), 2), "reps": args.reps}
+                    "slots_per_frame": round(float(out[:, 1].mean()), 2), "reps": args.reps, "strict_training": args.strict_training}
             if t_seq:
                 line["sequential_ms_per_frame"] = round(1e3 * float(np.median(t_seq)) / B, 4)
                 line["speedup"] = round(float(np.median(t_seq)) / float(np.median(t_batch)), 2)
