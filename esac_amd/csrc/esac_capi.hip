@@ -138,6 +138,7 @@ struct esac_hip_ctx {
     // speculative forward (forward_impl): the straggler chain of the sampler runs on this stream beside the launch stream
     hipStream_t side = nullptr;
     hipStream_t side2 = nullptr;          // ... and the selection among the settled hypotheses + the join on this one, beside the speculative refinement
+    hipEvent_t spec_ev = nullptr;         // recorded on the caller's stream at the entry of a speculative call: both streams wait for it
     bool spec_off = false, spec_env_off = false;  // ESAC_DEBUG_NO_SPECULATION / ESAC_SPECULATE=0
     bool spec_second_best = false;        // ESAC_DEBUG_SPEC_SECOND_BEST
     bool spec_lose_chain = false;         // ESAC_DEBUG_SPEC_LOSE_CHAIN
@@ -287,6 +288,7 @@ extern "C" int esac_hip_destroy(esac_hip_ctx* c) {
     drop_comm(c);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->side2) (void)hipStreamDestroy(c->side2);
+    if (c->spec_ev) (void)hipEventDestroy(c->spec_ev);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     for (auto& ev : c->ev)
         if (ev) (void)hipEventDestroy(ev);
@@ -761,6 +763,9 @@ static int forward_impl(esac_hip_ctx* c, const float* d_sc, long long sc_frame_s
     if (spec_ok && !c->side2) {
         HIP_OK(hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking));
     }
+    if (spec_ok && !c->spec_ev) {
+        HIP_OK(hipEventCreateWithFlags(&c->spec_ev, hipEventDisableTiming));
+    }
     if (tm) HIP_OK(hipEventRecord(c->ev[0], s));
     c->rt32_stale = false;
     mark_sampling(c, a);
@@ -772,14 +777,22 @@ static int forward_impl(esac_hip_ctx* c, const float* d_sc, long long sc_frame_s
         a.spec_flag = c->ws.spec_flag;
         KArgs chain;
         int chain_waves = 0;
+        // The caller's stream may hold any amount of work ahead of this call (the expert networks that produce d_sc), and the
+        // context's own streams are ordered against it by nothing else: they wait for THIS event before anything of this call
+        // runs on them, so that their bounded waits for the hand-off words below start counting when the caller's stream has
+        // reached the call -- not when the host enqueued it.  (Recorded here, in front of the first pass: on an idle stream it
+        // is satisfied long before the two streams get their first launch, and their wait for it sits beside the first pass and
+        // the score kernel, off the critical path.)
+        HIP_OK(hipEventRecord(c->spec_ev, s));
         launch_sample_split(a, s, &chain, &chain_waves);
         if ((rc = check_launch("k_sample (first pass)"))) return rc;
         c->host_ns[1] = now_ns() - t_entry;
         if (tm) HIP_OK(hipEventRecord(c->ev[1], s));
-        // The two streams hand over through WORDS in device memory (spec_state[3]: "the chain may start", [4]: "the chain is
-        // done"), not through events: an event between two streams costs the waiting side 8-13 us on this platform even when it is
-        // long satisfied (profiles/r06_ab_speculation.txt).  Whoever waits is enqueued BEHIND the launch it waits for (host order
-        // below), so that even two streams that share a hardware queue cannot wait for each other; every wait is bounded in wall time.
+        // WITHIN the call the streams hand over through WORDS in device memory (spec_state[3]: "the chain may start", [4]: "the
+        // chain is done"), not through events: an event between two streams costs the waiting side 8-13 us on this platform even
+        // when it is long satisfied (profiles/r06_ab_speculation.txt).  Whoever waits is enqueued BEHIND the launch it waits for
+        // (host order below), so that even two streams that share a hardware queue cannot wait for each other; every wait is
+        // bounded in wall time -- and begins behind spec_ev, i.e. when the caller's stream has reached this call.
         KArgs as = a;  // the settled hypotheses: score, selection, refinement of their winner -- no record leaves the workspace
         as.spec_mode = 1;
         as.result_user = nullptr;
@@ -808,9 +821,11 @@ static int forward_impl(esac_hip_ctx* c, const float* d_sc, long long sc_frame_s
         if ((rc = check_launch("k_refine (speculative)"))) return rc;
         // (host order: the selection first -- the join waits behind it; a launch call is 3-4 us of host time, and the chain's five
         // in front of it would hold the selection back by 20 us.  The JOIN is enqueued behind the chain it waits for.)
+        HIP_OK(hipStreamWaitEvent(c->side2, c->spec_ev, 0));
         launch_spec_wait(a, 3, c->side2);
         launch_select_rescore(as, c->side2);
         if ((rc = check_launch("k_select_rescore (settled)"))) return rc;
+        HIP_OK(hipStreamWaitEvent(c->side, c->spec_ev, 0));
         launch_spec_wait(a, 3, c->side);
         launch_sample_stragglers_on(chain, chain_waves, c->side);
         if (!c->spec_lose_chain) launch_score_stragglers(a, c->side);  // behind the chain on the side stream; its last workgroup writes "the chain is done"

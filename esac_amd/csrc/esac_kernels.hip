@@ -1029,7 +1029,11 @@ __global__ __launch_bounds__(B) void k_select_rescore(KArgs a) {
 // The waits are bounded in wall time: a word that never comes (the other stream's launch failed) costs ESAC_SPEC_WAIT_TICKS, is
 // counted in spec_state[5] and reported by the join (status 5) -- never a hang.
 __global__ __launch_bounds__(64) void k_spec_wait(KArgs a, int which) {
-    if (threadIdx.x == 0 && !spec_wait_word(a, which)) a.spec_state[5] += 1.0;  // (timed out: the chain runs late, the results stay right)
+    // Enqueued behind the call's entry event (forward_impl: spec_ev), so the wait begins when the caller's stream has reached the
+    // call: the word comes within the first pass, the score kernel and the start of the refinement.  A time-out is counted and
+    // NOT harmless -- what follows on this stream then runs on whatever the launch stream has left so far; the event is what
+    // keeps a caller's backlog from causing one.
+    if (threadIdx.x == 0 && !spec_wait_word(a, which)) a.spec_state[5] += 1.0;
 }
 void launch_spec_wait(const KArgs& a, int which, hipStream_t s) { hipLaunchKernelGGL(k_spec_wait, dim3(1), dim3(64), 0, s, a, which); }
 

@@ -62,7 +62,8 @@ FILLER_LIB = os.path.join(HERE, "libfiller.so")
 
 
 def build_filler(force=False):
-    """DEVICE build of the CU filler (filler.hip): workgroups that hold the CUs of one XCD and leave one by one."""
+    """DEVICE build of the test fillers (filler.hip): workgroups that hold the CUs of one XCD and leave one by one, and
+    hold_launch -- one sleeping wavefront that holds a STREAM for a bounded time (tests/test_gpu_stream_order.py)."""
     if force or not os.path.exists(FILLER_LIB) or os.path.getmtime(FILLER_SRC) > os.path.getmtime(FILLER_LIB):
         hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
         subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-result", FILLER_SRC, "-o", FILLER_LIB])

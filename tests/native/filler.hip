@@ -25,3 +25,18 @@ extern "C" int filler_launch(void* stream, int xcd, float step_ms, int blocks, u
     hipLaunchKernelGGL(k_filler, dim3(blocks), dim3(64), 0, s, xcd, (long long)(step_ms * 1e5f), d_counter, 0);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
+
+// ---- hold_launch: TEST-ONLY, occupies a STREAM (tests/test_gpu_stream_order.py: a producer that finishes late ahead of a library
+// call).  One 64-thread workgroup, no LDS (every CU stays free for whatever other streams run), asleep until `ms` of the
+// 100 MHz wall clock have passed.  The spin is bounded by that clock; more than HOLD_MAX_MS is refused and launches nothing.
+#define HOLD_MAX_MS 200.0f
+__global__ __launch_bounds__(64) void k_hold(long long ticks) {
+    const long long t0 = wall_clock64();
+    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
+}
+
+extern "C" int hold_launch(void* stream, float ms) {
+    if (!(ms >= 0.0f) || ms > HOLD_MAX_MS) return -1;
+    hipLaunchKernelGGL(k_hold, dim3(1), dim3(64), 0, (hipStream_t)stream, (long long)((double)ms * 1e5));
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}

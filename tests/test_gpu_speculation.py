@@ -199,14 +199,18 @@ def test_streams_that_share_one_hardware_queue():
     """The route's three streams hand over through polled words, and every waiter is enqueued behind the launch it waits for -- so
     streams that the runtime maps onto ONE hardware queue (GPU_MAX_HW_QUEUES=1: everything serialises) cannot wait for each other:
     the same comparisons in a process of that kind -- no time-out (status 5 would switch the speculation off and the
-    `last_speculative` assertions would fail), every output the serial route's."""
+    `last_speculative` assertions would fail), every output the serial route's.  One call of tests/test_gpu_stream_order.py runs
+    there too: the route behind a caller's stream that holds 1.5 bounds of work ahead of the call (the two streams then wait for
+    the call's entry event in that one queue as well)."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, GPU_MAX_HW_QUEUES="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_speculation.py"), "-q", "-x", "-m", "gpu", "-k",
-                        "equals_the_serial_route or straggler_that_wins or not_the_winner_of_the_settled or asynchronous"],
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_speculation.py"),
+                        os.path.join(root, "tests", "test_gpu_stream_order.py"), "-q", "-x", "-m", "gpu", "-k",
+                        "equals_the_serial_route or straggler_that_wins or not_the_winner_of_the_settled or asynchronous_call_delivers or "
+                        "(behind_a_busy_stream and 10x1024-1.5x-blocking)"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert " passed" in r.stdout and "failed" not in r.stdout, r.stdout[-2000:]
