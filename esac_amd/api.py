@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "esac_hip_comm_unique_id", "esac_hip_comm_init", "esac_hip_comm_destroy", "esac_hip_allreduce_sum", "esac_hip_comm_info",
     "esac_hip_host_turn_mean", "esac_hip_backward_batch",
     "esac_hip_forward_batch_cams", "esac_hip_backward_batch_cams",
+    "esac_hip_backward_batch_dev",  # additive: the ABI version stays
 ]
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
@@ -145,6 +146,8 @@ def load_library():
                                                 pp, vp, vp]
         lib.esac_hip_backward_batch_cams.argtypes = [vp, i32, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_float, C.c_float,
                                                      C.c_float, pp, vp, vp]
+        lib.esac_hip_backward_batch_dev.argtypes = [vp, i32, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_float, C.c_float,
+                                                    C.c_float, pp, vp, vp]
         lib.esac_hip_read.argtypes = [vp, i32, vp, C.c_size_t]
         lib.esac_hip_write_hyps.argtypes = [vp, vp, i32]
         lib.esac_hip_phase_ms.argtypes = [vp, vp]
@@ -361,6 +364,51 @@ class Engine:
             err.records = host
             raise err
         return host
+
+    def backward_batch_async(self, scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, cams=None,
+                             out=None):
+        """backward_batch without the host inside the call (esac_hip_backward_batch_dev): returns once the launches are enqueued
+        on torch's current stream; everything is read and written in stream order.  gt_poses: a float32 [B,4,4] tensor on this
+        device (the point of the call), or a host array / tensor, uploaded with non_blocking=True on the launch stream.
+        Returns the device float64 tensor [B,4] of records (`out` when given).  A singular ground-truth pose or an out-of-range
+        assignment is a per-frame outcome (record[3] = 2 / 1): check() after a synchronisation raises for it.
+        cams: None or B per-frame camera records (make_cams), copied before the call returns."""
+        sc = scene_coords if scene_coords.is_cuda else scene_coords.to(self.device, non_blocking=True)
+        ha = hyp_assign if hyp_assign.is_cuda else hyp_assign.to(self.device, non_blocking=True)
+        sc, ha = sc.contiguous(), ha.contiguous()
+        B = int(ha.shape[0])
+        if not (out_gradients.is_cuda and out_gradients.is_contiguous() and out_gradients.dtype == torch.float32
+                and out_gradients.dim() == 5 and out_gradients.shape[0] == B and tuple(out_gradients.shape[1:]) == tuple(sc.shape[-4:])):
+            raise RuntimeError("esac.backward_batch_async: the gradient tensor must be a dense float32 device tensor [B,E,3,H,W]")
+        if isinstance(gt_poses, torch.Tensor) and gt_poses.is_cuda:
+            gt = gt_poses
+        else:
+            # through pinned staging (torch's caching host allocator keeps it until the copy has run): the caller's array is free
+            # when the call returns, and the upload is a true asynchronous copy on the launch stream
+            host = gt_poses.detach() if isinstance(gt_poses, torch.Tensor) else torch.from_numpy(np.asarray(gt_poses, np.float32))
+            pin = torch.empty(tuple(host.shape), dtype=torch.float32, pin_memory=True)
+            pin.copy_(host)
+            with torch.cuda.device(self.device):
+                gt = pin.to(self.device, non_blocking=True)
+        if gt.dtype != torch.float32 or gt.numel() != 16 * B:
+            raise RuntimeError("esac.backward_batch_async: gtPoses must hold B float32 4x4 poses")
+        gt = gt.contiguous()
+        if out is None:
+            out = torch.empty((B, 4), dtype=torch.float64, device=self.device)
+        elif not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (B, 4)):
+            raise RuntimeError("esac.backward_batch_async: out must be a dense float64 device tensor [B,4]")
+        sc_stride = int(sc.stride(0)) if sc.dim() == 5 else 0
+        table = None
+        if cams is not None:
+            table = _cams_arg(cams, B, "esac.backward_batch_async")
+        rc = self.lib.esac_hip_backward_batch_dev(
+            self.ctx, B, sc.data_ptr(), sc_stride, out_gradients.data_ptr(), int(out_gradients.stride(0)), ha.data_ptr(),
+            gt.data_ptr(), table.ctypes.data if table is not None else None, float(w_rot), float(w_trans), float(loss_cut),
+            C.byref(params), self._stream(), out.data_ptr())
+        if rc != 0:
+            _check(rc, self.lib)
+        self._keep = (sc, ha, out_gradients, gt, out)  # alive until the kernels have run
+        return out
 
     def read_frames(self, which, B):
         """A training-path buffer (BUF_BWD_PROBS / _LOSSES / _REF_HYPS / _SCORE_GRADS / _SLOTS / _SLOT_INFO / _DLOSS) of all B
@@ -906,3 +954,54 @@ def backward_batch(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLoss
         outGradients.copy_(grads)  # the accumulated tensors back into the caller's (CPU or strided) storage
     _state["last"] = {"backward": out}
     return [float(v) for v in out[:, 0]]
+
+
+def backward_batch_async(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLossRot, wLossTrans, lossCut, shiftX, shiftY,
+                         focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling):
+    """`backward_batch` without a host round trip (esac_hip_backward_batch_dev): the call returns once its launches are enqueued on
+    torch's current stream and reads its inputs in stream order, so the networks that produce them may still be running and the
+    autograd backward can be enqueued behind it at once.  sceneCoordinates, hypAssignment and a contiguous outGradients must be
+    device tensors (an asynchronous call cannot copy back into host or strided storage); gtPoses float32 [B,4,4] on the device,
+    or on the host (uploaded asynchronously).  Returns the [B] DEVICE tensor of expected losses (float64; column 0 of the
+    record); last_result()["backward"] holds the [B,4] device record.  A singular ground-truth pose or an out-of-range
+    assignment is a per-frame outcome (record[b,3] = 2 / 1, engine().check() raises after a synchronisation).
+    Advances the call counter by B.  The camera arguments are host values, as in backward_batch."""
+    who = "esac.backward_batch_async"
+    _no_strict_training(who)
+    for name, t in (("sceneCoordinates", sceneCoordinates), ("outGradients", outGradients), ("hypAssignment", hypAssignment),
+                    ("gtPoses", gtPoses)):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError("%s: %s must be a torch.Tensor" % (who, name))
+    if hypAssignment.dtype != torch.int64 or hypAssignment.dim() != 2 or hypAssignment.numel() == 0:
+        raise RuntimeError("%s: hypAssignment must be a non-empty int64 [B,N]" % who)
+    B, N = hypAssignment.shape
+    if sceneCoordinates.dtype != torch.float32 or sceneCoordinates.dim() not in (4, 5) or sceneCoordinates.size(-3) != 3:
+        raise RuntimeError("%s: sceneCoordinates must be float32 [B,E,3,H,W] or [E,3,H,W]" % who)
+    if sceneCoordinates.dim() == 5 and sceneCoordinates.size(0) != B:
+        raise RuntimeError("%s: batch sizes of sceneCoordinates and hypAssignment differ" % who)
+    E, H, W = sceneCoordinates.shape[-4], sceneCoordinates.shape[-2], sceneCoordinates.shape[-1]
+    if outGradients.dtype != torch.float32 or tuple(outGradients.shape) != (B, E, 3, H, W):
+        raise RuntimeError("%s: outGradients must be float32 [B,E,3,H,W]" % who)
+    if gtPoses.dtype != torch.float32 or tuple(gtPoses.shape) != (B, 4, 4):
+        raise RuntimeError("%s: gtPoses must be float32 [B,4,4]" % who)
+    (shiftX, shiftY, focalLength, ppointX, ppointY), cams = _per_frame_cams(who, B, shiftX, shiftY, focalLength, ppointX, ppointY)
+    if not outGradients.is_contiguous():
+        raise RuntimeError("%s: outGradients must be contiguous (an asynchronous call cannot copy back into strided storage)" % who)
+    if not outGradients.is_cuda:
+        raise RuntimeError("%s: outGradients must be a device tensor (an asynchronous call cannot copy back into host storage)" % who)
+    if not sceneCoordinates.is_cuda:
+        raise RuntimeError("%s: sceneCoordinates must be a device tensor (an asynchronous call stages nothing on the host)" % who)
+    if not hypAssignment.is_cuda:
+        raise RuntimeError("%s: hypAssignment must be a device tensor (an asynchronous call stages nothing on the host)" % who)
+    if outGradients.device != sceneCoordinates.device or hypAssignment.device != sceneCoordinates.device or \
+            (gtPoses.is_cuda and gtPoses.device != sceneCoordinates.device):
+        raise RuntimeError("%s: sceneCoordinates, outGradients, hypAssignment and a device gtPoses must live on one device" % who)
+    eng = engine(sceneCoordinates.device.index)
+    p = eng.make_params(E, H, W, N, shiftX, shiftY, focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha,
+                        inlierBeta, maxReproj, subSampling, seed=_state["seed"], call=_state["call"],
+                        max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"],
+                        strict_training=_state["strict_training"])
+    _state["call"] += B
+    rec = eng.backward_batch_async(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLossRot, wLossTrans, lossCut, p, cams=cams)
+    _state["last"] = {"backward": rec}
+    return rec[:, 0]

@@ -8,6 +8,7 @@
 //   K7 k_bwd_path1       refined pose -> scene coordinates through the last re-fit             esac.cpp:375-463
 //   K8 k_bwd_path2       score -> scene coordinates (direct + via the 4 sampled points)        esac_derivative.h:205-330
 //   K9 k_bwd_accumulate  outGradients += p_h * pathI_h + pathII_h, hypotheses in order          esac.cpp:491-508
+//      k_bwd_gt_prepare  per-frame ground truth of the asynchronous batch, on the device          esac_util.h:555-568
 //
 // The reference allocates per-hypothesis (1 x 3P) and (P x 3) double matrices on the host heap for ALL N
 // hypotheses and adds them into the float tensor one hypothesis after the other.  Here only the <= 1000
@@ -21,6 +22,7 @@
 #include "bwd_math.hpp"
 #include "device_common.hpp"
 #include "esac_kernels.hpp"
+#include "gt_math.hpp"
 #include "pose_math.hpp"
 
 namespace esac {
@@ -75,6 +77,9 @@ __global__ __launch_bounds__(B) void k_bwd_select(KArgs a) {
     block_sum<2, B>(acc, s_part, s_tot);
     const double sum = acc[0];
     const bool poisoned = STRICT && sum != sum;  // (workgroup-uniform: block_sum hands every lane the same total)
+    // esac_hip_backward_batch_dev: a frame whose ground-truth pose is singular (k_bwd_gt_prepare) selects nothing -- no slot, no
+    // slab, nothing accumulated: its gradients stay as they are (workgroup-uniform)
+    const bool dead = BATCH && a.bwd.frame_status && a.bwd.frame_status[blockIdx.y] == 2;
     // probabilities, entropy, the pose every unselected hypothesis keeps, and the ordered selection:
     // rounds of B consecutive hypotheses, ballot prefix inside a wavefront, wavefront offsets through LDS
     double ent = 0;
@@ -87,7 +92,7 @@ __global__ __launch_bounds__(B) void k_bwd_select(KArgs a) {
             if (p > 0) ent -= p * log2(p);
 #pragma unroll
             for (int k = 0; k < 6; k++) a.bwd.ref_hyps[(size_t)i * 6 + k] = a.hyps[(size_t)i * 6 + k];
-            pick = !(p < kProbThresh) && !poisoned;
+            pick = !(p < kProbThresh) && !poisoned && !dead;
         }
         const unsigned long long bal = __ballot(pick);
         if (lane == 0) s_wcount[wave] = __popcll(bal);
@@ -111,7 +116,7 @@ __global__ __launch_bounds__(B) void k_bwd_select(KArgs a) {
     block_sum<2, B>(acc, s_part, s_tot);
     if (threadIdx.x == 0) {
         if (BATCH) a.bwd.n_sel[2] = bad != 0;
-        if (STRICT) a.bwd.n_sel[3] = poisoned ? 1 : 0;
+        if (STRICT) a.bwd.n_sel[3] = poisoned && !dead ? 1 : 0;
         a.bwd.n_sel[0] = s_base < a.bwd.cap ? s_base : a.bwd.cap;
         a.bwd.n_sel[1] = s_base;  // unclamped: > cap tells the host to grow the slot workspace and run the call again
         if (BATCH) atomicMax(a.bwd.sel_max, s_base);  // a batch: the accumulation of every frame looks at the largest
@@ -168,11 +173,41 @@ __global__ __launch_bounds__(B) void k_bwd_loss(KArgs a) {
     // its own assignment row (k_bwd_select looked at it: n_sel[2])
     const bool bad = BATCH ? a.bwd.n_sel[2] != 0 : a.status[0] == (unsigned long long)a.sample_epoch;
     if (threadIdx.x == 0) {
-        a.bwd.out[0] = expected;
-        a.bwd.out[1] = (double)a.bwd.n_sel[1];
-        a.bwd.out[2] = a.stats[2];
-        a.bwd.out[3] = bad ? 1.0 : 0.0;
+        double rec[4] = {expected, (double)a.bwd.n_sel[1], a.stats[2], bad ? 1.0 : 0.0};
+        if (BATCH && a.bwd.frame_status) {  // esac_hip_backward_batch_dev: per-frame outcomes, read by esac_hip_check
+            int* st = a.bwd.frame_status + blockIdx.y;
+            if (*st == 2) {  // singular ground truth: the record says so, nothing else of the frame is meaningful
+                rec[0] = __builtin_nan("");
+                rec[1] = 0.0; rec[2] = 0.0; rec[3] = 2.0;
+            } else if (bad) {
+                *st = 1;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) a.bwd.out[k] = rec[k];
+        if (BATCH && a.bwd.rec_dev) {  // the record does not depend on the accumulation: no slot overflow exists on this route
+#pragma unroll
+            for (int k = 0; k < 4; k++) a.bwd.rec_dev[(size_t)blockIdx.y * 4 + k] = rec[k];
+        }
     }
+}
+
+// ================================================================= ground truth on the device (esac_hip_backward_batch_dev)
+// One lane per frame: the float 4x4 pose -> gt[16] | gt_pose[6], the text the blocking calls run on the host (gt_math.hpp).  A
+// singular pose leaves NaNs in the record and 2 in the frame's status word; every other frame's word is reset to 0.
+__global__ __launch_bounds__(64) void k_bwd_gt_prepare(const float* __restrict__ poses, int B, double* __restrict__ gt_frames,
+                                                       int* __restrict__ status) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    float in[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) in[k] = poses[(size_t)b * 16 + k];
+    double gt[16], gt_pose[6];
+    const bool ok = gt_from_pose(in, gt, gt_pose);
+    double* g = gt_frames + (size_t)b * ESAC_GT_DOUBLES;
+    for (int k = 0; k < 16; k++) g[k] = ok ? gt[k] : __builtin_nan("");
+    for (int k = 0; k < 6; k++) g[16 + k] = ok ? gt_pose[k] : __builtin_nan("");
+    status[b] = ok ? 0 : 2;
 }
 
 // ================================================================= K7: path I
@@ -562,6 +597,9 @@ void launch_bwd_loss(const KArgs& a, hipStream_t s) {
 void launch_bwd_paths(const KArgs& a, hipStream_t s) {
     if (bwd_strict(a)) hipLaunchKernelGGL((k_bwd_paths<BWD_B, true>), dim3(2 * slot_grid(a), a.frames), dim3(BWD_B), 0, s, a);
     else               hipLaunchKernelGGL(k_bwd_paths<BWD_B>, dim3(2 * slot_grid(a), a.frames), dim3(BWD_B), 0, s, a);
+}
+void launch_bwd_gt_prepare(const float* d_gt_poses, int B, double* gt_frames, int* status, hipStream_t s) {
+    hipLaunchKernelGGL(k_bwd_gt_prepare, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, d_gt_poses, B, gt_frames, status);
 }
 void launch_bwd_accumulate(const KArgs& a, hipStream_t s) {
     const int per_expert = 3 * a.H * a.W;

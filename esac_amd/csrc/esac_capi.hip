@@ -16,6 +16,7 @@
 
 #include "../../include/esac_hip.h"
 #include "esac_kernels.hpp"
+#include "gt_math.hpp"
 #include "pose_math.hpp"
 
 using namespace esac;
@@ -120,6 +121,10 @@ struct esac_hip_ctx {
     int last_bwd_batch_cap = 0;               // slots per frame of the last launch set when it was a batch's (0: a single call)
     double* h_gt = nullptr;                   // pinned staging of the per-frame ground truth [ESAC_MAX_BATCH,22]
     double* d_gt = nullptr;                   // ... and its device copy
+    // esac_hip_backward_batch_dev: nothing of the call is staged on the host
+    double* d_gt_dev = nullptr;               // [ESAC_MAX_BATCH,22] written by k_bwd_gt_prepare in stream order
+    int* d_frame_status = nullptr;            // [ESAC_MAX_BATCH] per-frame outcome of the most recent such call (BwdArgs::frame_status)
+    int last_dev_batch = 0;                   // its B while it is the most recent call on the context (esac_hip_check reads that many words)
     // per-frame cameras of a batch (esac_hip_forward_batch_cams / esac_hip_backward_batch_cams)
     FrameCam* h_cams = nullptr;               // pinned staging [ESAC_MAX_BATCH]: the caller's array is free when the call returns
     FrameCam* d_cams = nullptr;               // ... and the table the kernels read (KArgs::cams)
@@ -280,6 +285,8 @@ extern "C" int esac_hip_destroy(esac_hip_ctx* c) {
     free_ws(c);
     free_bws(c);
     if (c->d_gt) (void)hipFree(c->d_gt);
+    if (c->d_gt_dev) (void)hipFree(c->d_gt_dev);
+    if (c->d_frame_status) (void)hipFree(c->d_frame_status);
     if (c->d_cams) (void)hipFree(c->d_cams);
     if (c->h_cams) (void)hipHostFree(c->h_cams);
     if (c->cams_ev) (void)hipEventDestroy(c->cams_ev);
@@ -553,6 +560,7 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
     a.margin = p->rescore_margin > 0 ? p->rescore_margin : fabsf(p->inlier_alpha) * (ESAC_DEFAULT_MARGIN + 2.0f / (float)P);
     c->lastN = p->N; c->lastH = p->H; c->lastW = p->W;
     c->lastB = B;
+    c->last_dev_batch = 0;  // (esac_hip_backward_batch_dev sets it again once its launches are queued)
     *out = a;
     return 0;
 }
@@ -1173,72 +1181,9 @@ static int ensure_bws(esac_hip_ctx* c, int N, int P, int cap, int B = 1) {
     return 0;
 }
 
-// general 4x4 inverse, Gauss-Jordan with partial pivoting (cv::Mat::inv() of trans2pose, esac_util.h:557)
-static bool inv4_host(const double A[16], double Ai[16]) {
-    double M[4][8];
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < 4; j++) {
-            M[i][j] = A[4 * i + j];
-            M[i][4 + j] = i == j;
-        }
-    for (int col = 0; col < 4; col++) {
-        int piv = col;
-        for (int r = col + 1; r < 4; r++)
-            if (fabs(M[r][col]) > fabs(M[piv][col])) piv = r;
-        if (M[piv][col] == 0) return false;
-        if (piv != col)
-            for (int j = 0; j < 8; j++) {
-                const double t = M[piv][j];
-                M[piv][j] = M[col][j];
-                M[col][j] = t;
-            }
-        const double d = 1.0 / M[col][col];
-        for (int j = 0; j < 8; j++) M[col][j] *= d;
-        for (int r = 0; r < 4; r++) {
-            if (r == col) continue;
-            const double f = M[r][col];
-            if (f == 0) continue;
-            for (int j = 0; j < 8; j++) M[r][j] -= f * M[col][j];
-        }
-    }
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < 4; j++) Ai[4 * i + j] = M[i][4 + j];
-    return true;
-}
-
-// nearest rotation of a 3x3 (orthogonal polar factor = U*Vt of its SVD, what cv::Rodrigues applies to a matrix
-// input): Newton iteration X <- (X + X^-T) / 2, quadratic from the ~1e-7 non-orthonormality of a float pose
-static void nearest_rotation_host(double R[9]) {
-    for (int it = 0; it < 20; it++) {
-        const double* a = R;
-        const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[5] * a[6] - a[3] * a[8], c02 = a[3] * a[7] - a[4] * a[6];
-        const double c10 = a[2] * a[7] - a[1] * a[8], c11 = a[0] * a[8] - a[2] * a[6], c12 = a[1] * a[6] - a[0] * a[7];
-        const double c20 = a[1] * a[5] - a[2] * a[4], c21 = a[2] * a[3] - a[0] * a[5], c22 = a[0] * a[4] - a[1] * a[3];
-        const double det = a[0] * c00 + a[1] * c01 + a[2] * c02;
-        if (det == 0) return;
-        const double invT[9] = {c00 / det, c01 / det, c02 / det, c10 / det, c11 / det, c12 / det, c20 / det, c21 / det, c22 / det};
-        double delta = 0;
-        for (int k = 0; k < 9; k++) {
-            const double n = 0.5 * (R[k] + invT[k]);
-            delta += fabs(n - R[k]);
-            R[k] = n;
-        }
-        if (delta < 1e-15) break;
-    }
-}
-
-// The loss's view of a ground-truth camera pose: gt (double of the float input) and trans2pose(gt) (esac_util.h:555-568).
+// The loss's view of a ground-truth camera pose (gt_math.hpp: the text k_bwd_gt_prepare runs on the device), on the host.
 // false: singular.
-static bool gt_host(const float* h_gt_pose, double gt[16], double gt_pose[6]) {
-    double Ti[16];
-    for (int i = 0; i < 16; i++) gt[i] = (double)h_gt_pose[i];
-    if (!inv4_host(gt, Ti)) return false;
-    double Rg[9] = {Ti[0], Ti[1], Ti[2], Ti[4], Ti[5], Ti[6], Ti[8], Ti[9], Ti[10]};
-    nearest_rotation_host(Rg);
-    rodrigues_mat2vec(Rg, gt_pose);
-    gt_pose[3] = Ti[3]; gt_pose[4] = Ti[7]; gt_pose[5] = Ti[11];
-    return true;
-}
+static bool gt_host(const float* h_gt_pose, double gt[16], double gt_pose[6]) { return gt_from_pose(h_gt_pose, gt, gt_pose); }
 
 extern "C" int esac_hip_backward(esac_hip_ctx* c, const float* d_sc, float* d_out_gradients, const int64_t* d_assign,
                                  const float* h_gt_pose, float w_loss_rot, float w_loss_trans, float loss_cut,
@@ -1486,6 +1431,111 @@ extern "C" int esac_hip_backward_batch_cams(esac_hip_ctx* c, int B, const float*
     return 0;
 }
 
+// The asynchronous batch (include/esac_hip.h): ground truth, records and per-frame outcomes stay on the device, the host enqueues
+// and returns.  Nothing in here waits for the stream -- the one wait is stage_cams' on the PREVIOUS call's table copy -- and
+// nothing is run twice: every frame owns the worst-case min(N, 1000) slots, so no selection can overflow, and the frames go in
+// chunks of consecutive frames sized by that worst case, one launch set after the other on the stream (which serialises their
+// use of the workspace).  A workspace that has to grow is grown before the first launch (ensure_ws / ensure_bws: one device
+// synchronisation, on the first call of a shape only).
+extern "C" int esac_hip_backward_batch_dev(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
+                                           int64_t grad_frame_stride, const int64_t* d_assign, const float* d_gt_poses,
+                                           const esac_hip_frame_cam* h_cams, float w_loss_rot, float w_loss_trans, float loss_cut,
+                                           const esac_hip_params* p, void* stream, double* d_out) {
+    if (!c) return fail(-1, "null context");
+    if (!p) return fail(-1, "null params");
+    if (!d_sc || !d_out_gradients || !d_assign || !d_gt_poses)
+        return fail(-1, "esac_hip_backward_batch: null coordinate, gradient, assignment or ground-truth pointer");
+    if (!d_out) return fail(-1, "esac_hip_backward_batch_dev: d_out (device double[B,4]) is required");
+    if (p->flags & ESAC_FLAG_STRICT_REFERENCE)
+        return fail(-4, "esac_hip_backward_batch: the training path has no strict mode (ESAC_FLAG_STRICT_REFERENCE is a forward flag)");
+    if (B < 1 || B > ESAC_MAX_BATCH) return fail(-4, "esac_hip_backward_batch: batch size %d outside [1,%d]", B, ESAC_MAX_BATCH);
+    if (p->d_hyp_index || p->hyp_offset)
+        return fail(-4, "esac_hip_backward_batch: sharded calls are not supported (the expectation needs every hypothesis)");
+    if (p->E > 65535) return fail(-4, "esac_hip_backward_batch: at most 65535 experts (one grid row per expert in the accumulation kernel)");
+    if (p->E <= 0 || p->H <= 0 || p->W <= 0 || p->N <= 0) return fail(-4, "E=%d, H=%d, W=%d, N=%d must be positive", p->E, p->H, p->W, p->N);
+    const long long slab = (long long)p->E * 3 * p->H * p->W;
+    if (sc_frame_stride < 0) return fail(-4, "esac_hip_backward_batch: negative coordinate frame stride");
+    if (B > 1 && grad_frame_stride < slab)
+        return fail(-4, "esac_hip_backward_batch: gradient frame stride %lld < E*3*H*W = %lld (frames would share gradients)",
+                    (long long)grad_frame_stride, slab);
+    // the chunking is known before anything is launched: cap is the worst case, so the first chunk is the largest
+    const int N = p->N, P = p->H * p->W, cap = bwd_rows(N);
+    const long long per_slot = 2LL * P + 2LL * 3 * P * (long long)sizeof(double) +
+                               (P > ESAC_REFINE_LDS_CAP ? corr_entries(P) * 16 : 0);  // inlier maps, two slabs, correspondence list
+    const long long fit = c->bwd_budget / ((long long)cap * per_slot);
+    if (fit < 1)
+        return fail(-4, "esac_hip_backward_batch_dev: one frame's worst case (%d slots, %lld MiB) exceeds the slot-workspace budget of "
+                        "%lld MiB (ESAC_BWD_BATCH_BUDGET_MB); the blocking esac_hip_backward_batch sizes the workspace by the "
+                        "selection's true count", cap, ((long long)cap * per_slot) >> 20, c->bwd_budget >> 20);
+    const int chunk = (int)(fit > B ? B : fit);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (!c->d_gt_dev) {
+        HIP_OK(hipMalloc((void**)&c->d_gt_dev, (size_t)ESAC_MAX_BATCH * ESAC_GT_DOUBLES * sizeof(double)));
+        HIP_OK(hipMalloc((void**)&c->d_frame_status, (size_t)ESAC_MAX_BATCH * sizeof(int)));
+    }
+    // validation of the parameters and of every camera record, and the workspaces of the largest chunk, before anything is
+    // launched: the caller's gradients stay untouched on an error
+    KArgs a;
+    int rc;
+    if (h_cams) {
+        const esac_hip_params p0 = with_cam(*p, h_cams[0]);
+        if ((rc = make_args(c, d_sc, d_assign, &p0, &a, chunk, sc_frame_stride, 0, true))) return rc;
+        if ((rc = ensure_bws(c, N, P, cap, chunk))) return rc;
+        if ((rc = stage_cams(c, &p0, h_cams, B, s))) return rc;  // (checks every record before the first launch)
+    } else {
+        if ((rc = make_args(c, d_sc, d_assign, p, &a, chunk, sc_frame_stride, -1, true))) return rc;
+        if ((rc = ensure_bws(c, N, P, cap, chunk))) return rc;
+    }
+    launch_bwd_gt_prepare(d_gt_poses, B, c->d_gt_dev, c->d_frame_status, s);
+    if ((rc = check_launch("k_bwd_gt_prepare"))) return rc;
+    for (int b0 = 0; b0 < B;) {
+        const int nb = B - b0 < chunk ? B - b0 : chunk;
+        esac_hip_params pc = h_cams ? with_cam(*p, h_cams[b0]) : *p;
+        pc.call = p->call + (uint64_t)b0;
+        if ((rc = make_args(c, d_sc + (size_t)b0 * sc_frame_stride, d_assign + (size_t)b0 * N, &pc, &a, nb, sc_frame_stride, -1, true))) return rc;
+        if (h_cams) a.cams = c->d_cams + b0;
+        a.tstamps = nullptr;
+        c->rt32_stale = false;
+        mark_sampling(c, a);
+        launch_sample(a, s);                                    // frame b: call p->call + b
+        if ((rc = check_launch("k_sample"))) return rc;
+        launch_rescore_all(a, s, true);                         // (each frame summed as a single call sums it)
+        if ((rc = check_launch("k_rescore(all)"))) return rc;
+        c->last_bwd_frames = nb;  // (the slot workspace was sized for the largest chunk above)
+        c->last_bwd_batch_cap = cap;
+        a.bwd = c->bws;
+        a.bwd.cap = cap;
+        a.bwd.team = 0;
+        a.bwd.team_tag = 0;
+        a.bwd.team_max_slots = 0;  // one workgroup per slot
+        a.bwd.out_grad = d_out_gradients + (size_t)b0 * grad_frame_stride;
+        a.bwd.grad_frame_stride = grad_frame_stride;
+        a.bwd.gt_frames = c->d_gt_dev + (size_t)b0 * ESAC_GT_DOUBLES;
+        a.bwd.frame_status = c->d_frame_status + b0;
+        a.bwd.rec_dev = d_out + (size_t)b0 * 4;
+        a.bwd.w_rot = (double)w_loss_rot;
+        a.bwd.w_trans = (double)w_loss_trans;
+        a.bwd.cut = (double)loss_cut;
+        HIP_OK(hipMemsetAsync(a.bwd.sel_max, 0, sizeof(int), s));
+        launch_bwd_select(a, s);
+        if ((rc = check_launch("k_bwd_select"))) return rc;
+        launch_refine_slots(a, s);
+        if ((rc = check_launch("k_refine(slots)"))) return rc;
+        launch_bwd_loss(a, s);                                  // (also frame b's record into d_out[b*4..])
+        if ((rc = check_launch("k_bwd_loss"))) return rc;
+        launch_bwd_paths(a, s);
+        if ((rc = check_launch("k_bwd_paths"))) return rc;
+        KArgs acc = a;
+        acc.result_pin = nullptr;  // nobody polls
+        launch_bwd_accumulate(acc, s);
+        if ((rc = check_launch("k_bwd_accumulate"))) return rc;
+        b0 += nb;
+    }
+    c->last_dev_batch = B;
+    return 0;
+}
+
 // Asynchronous calls (no host result) cannot report an out-of-range hypAssignment themselves: this waits for the
 // device and returns -10 when the most recent call on the context flagged one, 0 otherwise.
 extern "C" int esac_hip_check(esac_hip_ctx* c) {
@@ -1509,6 +1559,17 @@ extern "C" int esac_hip_check(esac_hip_ctx* c) {
             }
         }
         return fail(-12, "the cooperating refinement workgroups of the most recent call could not synchronise (not all of them became resident)");
+    }
+    if (c->last_dev_batch > 0) {  // esac_hip_backward_batch_dev was the most recent call: its per-frame outcomes
+        static thread_local int words[ESAC_MAX_BATCH];
+        const int B = c->last_dev_batch;
+        HIP_OK(hipMemcpy(words, c->d_frame_status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; b++)
+            if (words[b] == 2) return fail(-4, "esac_hip_backward_batch_dev: the ground-truth pose of frame %d is singular", b);
+        for (int b = 0; b < B; b++)
+            if (words[b] == 1)
+                return fail(-10, "hypAssignment holds a value outside [0,E) in frame %d of the most recent batch (d_out[b*4+3] = 1 names "
+                                 "every such frame; such hypotheses were scored against expert 0)", b);
     }
     if (st != 0 && (double)st == c->sample_epoch) return fail(-10, "hypAssignment held a value outside [0,E) in the most recent sampling call");
     return 0;

@@ -99,6 +99,11 @@ struct BwdArgs {
     const double* gt_frames;         // [B,22] per-frame gt[16] | gt_pose[6] (replaces the inline fields)
     int* sel_max;                    // [1] the largest unclamped selection of any frame: > cap stops the accumulation of EVERY frame
     long long grad_frame_stride;     // elements between the gradient tensors of consecutive frames
+    // esac_hip_backward_batch_dev (no host inside the call); null on every other call.  Both are indexed by the frame of the
+    // launch (the C ABI offsets them by the chunk's first frame), not moved by bwd_frame_view
+    int* frame_status;               // [B] 0, or 2: the frame's ground-truth pose is singular (k_bwd_gt_prepare) -- the frame selects
+                                     // nothing and adds nothing; k_bwd_loss sets 1 when the frame's assignment was out of range
+    double* rec_dev;                 // [B,4] the caller's device records: k_bwd_loss writes frame b's four values itself
 };
 
 constexpr int ESAC_SPEC_CNT_FAN = 32, ESAC_SPEC_CNT_STRIDE = 32;  // counters of the second level; ints between two counters (128 bytes)
@@ -260,6 +265,8 @@ void launch_bwd_select(const KArgs& a, hipStream_t s);
 void launch_bwd_loss(const KArgs& a, hipStream_t s);
 void launch_bwd_paths(const KArgs& a, hipStream_t s);  // path I and path II of every slot, one launch
 void launch_bwd_accumulate(const KArgs& a, hipStream_t s);
+// float poses [B,4,4] (device) -> the [B,22] records of BwdArgs::gt_frames + status[b] = 0 / 2 (singular), in stream order
+void launch_bwd_gt_prepare(const float* d_gt_poses, int B, double* gt_frames, int* status, hipStream_t s);
 // rows of the per-slot tables (dloss, map_info) of one frame: the worst case, so that a batch's tables are frame-major [B,rows]
 __host__ __device__ inline int bwd_rows(int N) { return N < ESAC_BWD_SLOTS_K ? N : ESAC_BWD_SLOTS_K; }
 

@@ -231,7 +231,8 @@ def train_step(image, gt_pose, gating, experts, focal_length, hypotheses=256, th
 
 def train_batch(images, gt_poses, gating, experts, focal_lengths, hypotheses=256, threshold=10.0, inlier_alpha=100.0,
                 inlier_beta=0.5, max_reprojection=100.0, subsample=8, weight_rot=1.0, weight_trans=100.0, loss_cut=100.0,
-                max_experts=-1, expert_selection=False, shifts=None, e_hyps=None, generator=None, strict_training=False):
+                max_experts=-1, expert_selection=False, shifts=None, e_hyps=None, generator=None, strict_training=False,
+                asynchronous=False, all_experts=False):
     """The mini-batch form of `train_step`: B images through ONE `esac.backward_batch` with a shift and a focal length per
     image (train_esac.py:112 reads the focal length per image, :125 draws a new shift for every image), up to and including
     one `torch.autograd.backward`.
@@ -243,8 +244,15 @@ def train_batch(images, gt_poses, gating, experts, focal_lengths, hypotheses=256
     is active in at least one frame runs once on the batch: the rows of frames in which it is inactive are never read by the
     kernels and receive a zero gradient.  Only the B x E activity flags and the B losses reach the host.
     strict_training: this call's esac.backward_batch follows the reference in every stage (esac.set_strict_training).
-    Returns dict(losses (list of B floats), e_hyps [B,N], e_hist [B,E], prediction [B,E,3,h,w], prediction_gradients,
-    gating_log_probs [B,E], pads (list of B pairs))."""
+    asynchronous: the solver is `esac.backward_batch_async` -- the call returns once its launches are enqueued, `losses` stays a
+    DEVICE tensor [B] (float64) and the gating gradients are formed from it on the device, so the autograd backward is enqueued
+    while the solver still runs.  all_experts: every expert runs on the batch and the `.cpu()` of the B x E activity flags is
+    skipped (the rows of inactive experts are still never read).  With both, the step up to and including
+    `torch.autograd.backward` contains no host synchronisation, given device `images`, a device `gt_poses` tensor and `e_hyps`
+    drawn on the device.  What remains host-side: the shifts (drawn or given on the host, one pad per image) and the focal lengths,
+    which travel as the call's per-frame camera table; a host `gt_poses` is uploaded asynchronously.
+    Returns dict(losses (list of B floats; asynchronous: device tensor [B]), e_hyps [B,N], e_hist [B,E], prediction [B,E,3,h,w],
+    prediction_gradients, gating_log_probs [B,E], pads (list of B pairs))."""
     dev = images.device
     B, E = int(images.size(0)), len(experts)
     pp_x = float(images.size(3) / 2)
@@ -288,23 +296,30 @@ def train_batch(images, gt_poses, gating, experts, focal_lengths, hypotheses=256
             else:
                 e_hyps = torch.multinomial(gating_probs, hypotheses, replacement=True, generator=generator)  # one row of draws per frame
         e_hist = torch.zeros((B, E), device=dev).scatter_add_(1, e_hyps, torch.ones(e_hyps.shape, device=dev))
-        active = (e_hist > 0).cpu()  # [B,E] flags: all that reaches the host before the call
-        active_any = active.any(dim=0).tolist()
+        if all_experts:
+            active_any = [True] * E  # no flags cross to the host: every expert runs
+        else:
+            active = (e_hist > 0).cpu()  # [B,E] flags: all that reaches the host before the call
+            active_any = active.any(dim=0).tolist()
     outputs = [experts[e](images) if on else torch.zeros((B, 3, pred_h, pred_w), device=dev) for e, on in enumerate(active_any)]
     prediction = torch.stack(outputs, dim=1)  # [B,E,3,h,w]
     prediction_gradients = torch.zeros_like(prediction)
     strict_before = api._state["strict_training"]
     api.set_strict_training(strict_before or strict_training)
+    gt_t = torch.as_tensor(np.asarray(gt_poses, np.float32) if not isinstance(gt_poses, torch.Tensor) else gt_poses, dtype=torch.float32)
     try:
-        losses = api.backward_batch(prediction.detach(), prediction_gradients, e_hyps.contiguous(),
-                                    torch.as_tensor(np.asarray(gt_poses, np.float32) if not isinstance(gt_poses, torch.Tensor) else gt_poses,
-                                                    dtype=torch.float32).cpu(),
-                                    weight_rot, weight_trans, loss_cut, [p[0] for p in pads], [p[1] for p in pads], focals, pp_x, pp_y,
-                                    threshold, inlier_alpha, inlier_beta, max_reprojection, subsample)
+        if asynchronous:  # (a device gt_poses stays where it is)
+            losses = api.backward_batch_async(prediction.detach(), prediction_gradients, e_hyps.contiguous(), gt_t,
+                                              weight_rot, weight_trans, loss_cut, [p[0] for p in pads], [p[1] for p in pads], focals,
+                                              pp_x, pp_y, threshold, inlier_alpha, inlier_beta, max_reprojection, subsample)
+        else:
+            losses = api.backward_batch(prediction.detach(), prediction_gradients, e_hyps.contiguous(), gt_t.cpu(),
+                                        weight_rot, weight_trans, loss_cut, [p[0] for p in pads], [p[1] for p in pads], focals, pp_x, pp_y,
+                                        threshold, inlier_alpha, inlier_beta, max_reprojection, subsample)
     finally:
         api.set_strict_training(strict_before)
     # gating gradients, per frame: REINFORCE-style, loss per drawn hypothesis (train_esac.py:171-177)
-    loss_t = torch.tensor(losses, device=dev, dtype=torch.float32)
+    loss_t = losses.to(torch.float32) if asynchronous else torch.tensor(losses, device=dev, dtype=torch.float32)
     if expert_selection:
         gating_grads = torch.zeros_like(gating_log_probs)
         gating_grads.scatter_(1, expert, loss_t.unsqueeze(1).to(gating_log_probs.dtype))

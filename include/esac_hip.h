@@ -392,6 +392,34 @@ int esac_hip_backward_batch_cams(esac_hip_ctx* ctx, int B, const float* d_scene_
                                  const float* h_gt_poses, const esac_hip_frame_cam* h_cams, float w_loss_rot,
                                  float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* h_out);
 
+/*
+ * The ASYNCHRONOUS batch of the training path: esac_hip_backward_batch_cams with the ground truth and the records in device
+ * memory.  The call returns once its launches are enqueued on `stream`; it waits for nothing on the stream, polls nothing and
+ * runs nothing twice (the one host wait it can meet is on the PREVIOUS call's camera-table copy having left its staging buffer).
+ * Everything it reads -- coordinates, assignment, ground-truth poses, the gradients' prior content -- is read in stream order: a
+ * producer queued ahead on `stream` is honoured, a consumer queued behind it sees the final gradients and records.
+ * d_gt_poses   DEVICE float [B,4,4].  The 4x4 inverse, polar factor and Rodrigues step run in a kernel (the same text the
+ *              blocking calls run on the host).  A singular pose cannot be rejected before the launch: it is a per-frame outcome
+ *              -- that frame's gradients are left untouched, its record is (NaN, 0, 0, 2), the other frames are unaffected, and
+ *              esac_hip_check afterwards returns -4 naming the frame.
+ * h_cams       host, B records or NULL, as in esac_hip_backward_batch_cams (copied before the call returns).
+ * d_out        DEVICE double [B,4], REQUIRED: frame b's record at d_out[b*4 + 0..3], the four values of esac_hip_backward.  An
+ *              out-of-range assignment in frame b sets d_out[b*4+3] = 1; esac_hip_check afterwards returns -10.
+ * Slot workspace: the host cannot look at the selection's count, so every frame owns the worst case min(N, ESAC_BWD_MAX_SLOTS)
+ * slots -- no overflow, no second pass -- and the frames run in chunks of consecutive frames within the context's budget
+ * (ESAC_BWD_BATCH_BUDGET_MB), one launch set after the other on `stream`.  One frame's worst case beyond the budget: -4 before
+ * anything is launched (the blocking call sizes the workspace by the true count).  Slots are refined with one workgroup each:
+ * frame b is bit for bit frame b of the blocking batch on the same inputs.
+ * ESAC_FLAG_STRICT_TRAINING and per-frame cameras as in esac_hip_backward_batch_cams; ESAC_FLAG_STRICT_REFERENCE, sharding, B
+ * outside [1,ESAC_MAX_BATCH], null pointers, a too small grad_frame_stride, E > 65535 and a bad camera record are rejected with
+ * its codes and messages before anything is launched.  esac_hip_read after a device synchronisation: as after the blocking batch
+ * (the last chunk's frames, frame-major).
+ */
+int esac_hip_backward_batch_dev(esac_hip_ctx* ctx, int B, const float* d_scene_coords, int64_t sc_frame_stride,
+                                float* d_out_gradients, int64_t grad_frame_stride, const int64_t* d_hyp_assign,
+                                const float* d_gt_poses, const esac_hip_frame_cam* h_cams, float w_loss_rot,
+                                float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* d_out);
+
 /* The same phases one at a time (asynchronous on `stream`), for stage-wise parity
  * tests and for callers that interleave other work.  Order: sample, score, select, refine. */
 int esac_hip_sample(esac_hip_ctx* ctx, const float* d_scene_coords, const int64_t* d_hyp_assign,
@@ -413,7 +441,9 @@ int esac_hip_score_exact(esac_hip_ctx* ctx, const float* d_scene_coords, const i
  * could not synchronise (blocking calls report the former themselves and, when a small-grid team timed out, run the
  * refinement again in one workgroup; asynchronous ones -- no host result pointer -- cannot: their device record then
  * carries ESAC_RES_VALID = 3 and this function counts the time-out towards the same two-in-a-row latch), else 0.
- * Out-of-range values never cause an out-of-bounds read: such hypotheses are evaluated against expert 0. */
+ * Out-of-range values never cause an out-of-bounds read: such hypotheses are evaluated against expert 0.
+ * When the most recent call was esac_hip_backward_batch_dev, its per-frame outcomes are reported: -4 naming the first frame
+ * whose ground-truth pose was singular, else -10 naming the first frame whose assignment was out of range. */
 int esac_hip_check(esac_hip_ctx* ctx);
 
 /* Stage buffer access (synchronous). `bytes` must match the buffer size for (which, N, H, W).  After a batched call of B frames

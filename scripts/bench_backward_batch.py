@@ -10,6 +10,8 @@ mean number of slots (hypotheses with p >= PROB_THRESH) per frame.
     python scripts/bench_backward_batch.py --strict-training  # the same measurement with ESAC_FLAG_STRICT_TRAINING
     python scripts/bench_backward_batch.py --per-frame-cams   # after each shared-camera line, the same frames and counters with a
                                                               # shift (|shift| <= sub/2) and a focal length per frame
+    python scripts/bench_backward_batch.py --asynchronous [--batches 8,32,128] [--steps 4] [--reps 5]
+                                                              # Engine.backward_batch_async against the blocking batch (see main_async)
 """
 import argparse
 import json
@@ -53,8 +55,105 @@ def make_inputs(cfg, B, per_frame=False):
     return frames[0], sc, ha, np.stack(gts), cams
 
 
+def main_async(args):
+    """--asynchronous: K = --steps batches both ways in this process, interleaved rep by rep after a warm-up of both.
+      (a) K blocking `backward_batch` calls;
+      (b) K `backward_batch_async` calls enqueued back to back (device ground truth), one synchronisation at the end.
+    Per (config, B) one JSON line: wall time per frame of each (for (a) the host waits inside every call, so this is its device
+    time plus its launch-to-drain gaps; for (b) the stream never drains), the host time spent inside the calls, and a
+    step-overlap leg: a fixed filler (--filler-matmuls fp32 4096^3 products, standing in for the CNN backward) enqueued behind
+    each call, K steps both ways.  Medians over --reps, with the min..max spread of each."""
+    eng = api.Engine(0)
+    batches = [int(x) for x in (args.batches if args.batches != "1,8,32,128" else "8,32,128").split(",")]
+    K = args.steps
+    fa = torch.randn(4096, 4096, device="cuda")
+    fc = torch.empty_like(fa)
+
+    def filler():
+        for _ in range(args.filler_matmuls):
+            torch.mm(fa, fa, out=fc)
+
+    for name in args.configs.split(","):
+        cfg = CONFIGS[name]
+        f0, sc_all, ha_all, gts_all, _ = make_inputs(cfg, max(batches))
+        E, _, H, W = f0["coords"].shape
+        grads = torch.zeros((max(batches), E, 3, H, W), dtype=torch.float32, device="cuda")
+        gt_dev_all = torch.from_numpy(gts_all).cuda()
+        for B in batches:
+            sc, ha, gts, gt_dev, g = sc_all[:B], ha_all[:B], gts_all[:B], gt_dev_all[:B], grads[:B]
+            recs = [torch.empty((B, 4), dtype=torch.float64, device="cuda") for _ in range(K)]
+
+            def params(call):
+                return eng.make_params(E, H, W, cfg["N"], focal=f0["focal"], ppx=f0["ppx"], ppy=f0["ppy"], sub_sampling=f0["sub"],
+                                       inlier_alpha=100.0, call=call, strict_training=args.strict_training)
+
+            def blocking(with_filler):
+                host = 0.0
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for k in range(K):
+                    t1 = time.perf_counter()
+                    out = eng.backward_batch(sc, g, ha, gts, 1.0, 100.0, 100.0, params(k * B))
+                    host += time.perf_counter() - t1
+                    if with_filler:
+                        filler()
+                torch.cuda.synchronize()
+                return time.perf_counter() - t0, host, out
+
+            def asynchronous(with_filler):
+                host = 0.0
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for k in range(K):
+                    t1 = time.perf_counter()
+                    eng.backward_batch_async(sc, g, ha, gt_dev, 1.0, 100.0, 100.0, params(k * B), out=recs[k])
+                    host += time.perf_counter() - t1
+                    if with_filler:
+                        filler()
+                torch.cuda.synchronize()
+                return time.perf_counter() - t0, host
+
+            out = blocking(True)[2]  # warm-up of both routes and the filler (the workspaces grow here)
+            asynchronous(True)
+            eng.check()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(K):
+                filler()
+            torch.cuda.synchronize()
+            filler_ms = 1e3 * (time.perf_counter() - t0) / K
+            rows = {"a": [], "b": [], "a_host": [], "b_host": [], "a_step": [], "b_step": []}
+            for _ in range(args.reps):
+                t, h, _ = blocking(False)
+                rows["a"].append(t), rows["a_host"].append(h)
+                t, h = asynchronous(False)
+                rows["b"].append(t), rows["b_host"].append(h)
+                rows["a_step"].append(blocking(True)[0])
+                rows["b_step"].append(asynchronous(True)[0])
+            per_frame = lambda v: 1e3 * np.asarray(v) / (K * B)
+            per_step = lambda v: 1e3 * np.asarray(v) / K
+            med = lambda v: round(float(np.median(v)), 4)
+            spread = lambda v: [round(float(np.min(v)), 4), round(float(np.max(v)), 4)]
+            a, b = per_frame(rows["a"]), per_frame(rows["b"])
+            line = {"config": name, "B": B, "E": E, "N": cfg["N"], "grid": "%dx%d" % (H, W), "steps": K, "reps": args.reps,
+                    "slots_per_frame": round(float(out[:, 1].mean()), 2), "strict_training": args.strict_training,
+                    "blocking_ms_per_frame": med(a), "blocking_spread": spread(a),
+                    "async_ms_per_frame": med(b), "async_spread": spread(b),
+                    "async_over_blocking": round(float(np.median(b) / np.median(a)), 4),
+                    "blocking_host_ms_per_call": med(per_step(rows["a_host"])), "async_host_ms_per_call": med(per_step(rows["b_host"])),
+                    "filler_ms": round(filler_ms, 4),
+                    "blocking_step_ms": med(per_step(rows["a_step"])), "blocking_step_spread": spread(per_step(rows["a_step"])),
+                    "async_step_ms": med(per_step(rows["b_step"])), "async_step_spread": spread(per_step(rows["b_step"]))}
+            line["step_ms_saved"] = round(line["blocking_step_ms"] - line["async_step_ms"], 4)
+            print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--asynchronous", action="store_true",
+                    help="Engine.backward_batch_async against the blocking batch: time per frame, host time in the call, step overlap")
+    ap.add_argument("--steps", type=int, default=4, help="--asynchronous: batches per timed run (K)")
+    ap.add_argument("--filler-matmuls", type=int, default=4, help="--asynchronous: fp32 4096^3 products behind each call in the step leg")
     ap.add_argument("--batches", default="1,8,32,128")
     ap.add_argument("--configs", default="cfg2,cfg3")
     ap.add_argument("--reps", type=int, default=5)
@@ -64,6 +163,8 @@ def main():
     ap.add_argument("--strict-training", action="store_true",
                     help="every call with ESAC_FLAG_STRICT_TRAINING (the verification route: each JSON line says strict_training=true)")
     args = ap.parse_args()
+    if args.asynchronous:
+        return main_async(args)
     eng = api.Engine(0)
     batches = [args.only_batch] if args.only_batch else [int(x) for x in args.batches.split(",")]
     for name in args.configs.split(","):
