@@ -330,23 +330,28 @@ class Engine:
         self._keep = (sc, ha, out_gradients)
         return host
 
-    def backward_batch(self, scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, cams=None):
-        """Training path over B frames in one set of launches (esac_hip_backward_batch). scene_coords [B,E,3,H,W] (or [E,3,H,W]
-        shared by all frames), out_gradients float32 [B,E,3,H,W] on this device, contiguous, accumulated into; hyp_assign [B,N];
-        gt_poses [B,4,4]. `params` describes one frame, frame b uses call + b. Returns np.float64 [B,4] (one record per frame).
-        An out-of-range device assignment raises after every frame has run; the exception's `records` holds the [B,4] records.
-        cams: None or B per-frame camera records (make_cams), as in forward_batch (esac_hip_backward_batch_cams)."""
+    def _batch_inputs(self, who, scene_coords, out_gradients, hyp_assign):
+        """The device inputs of a batched training call: dense scene coordinates and assignment on this device, the checked
+        gradient tensor's batch size B and the coordinates' frame stride (0: one [E,3,H,W] shared by all frames)."""
         sc = scene_coords if scene_coords.is_cuda else scene_coords.to(self.device, non_blocking=True)
         ha = hyp_assign if hyp_assign.is_cuda else hyp_assign.to(self.device, non_blocking=True)
         sc, ha = sc.contiguous(), ha.contiguous()
         B = int(ha.shape[0])
         if not (out_gradients.is_cuda and out_gradients.is_contiguous() and out_gradients.dtype == torch.float32
                 and out_gradients.dim() == 5 and out_gradients.shape[0] == B and tuple(out_gradients.shape[1:]) == tuple(sc.shape[-4:])):
-            raise RuntimeError("esac.backward_batch: the gradient tensor must be a dense float32 device tensor [B,E,3,H,W]")
+            raise RuntimeError("%s: the gradient tensor must be a dense float32 device tensor [B,E,3,H,W]" % who)
+        return sc, ha, B, int(sc.stride(0)) if sc.dim() == 5 else 0
+
+    def backward_batch(self, scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, cams=None):
+        """Training path over B frames in one set of launches (esac_hip_backward_batch). scene_coords [B,E,3,H,W] (or [E,3,H,W]
+        shared by all frames), out_gradients float32 [B,E,3,H,W] on this device, contiguous, accumulated into; hyp_assign [B,N];
+        gt_poses [B,4,4]. `params` describes one frame, frame b uses call + b. Returns np.float64 [B,4] (one record per frame).
+        An out-of-range device assignment raises after every frame has run; the exception's `records` holds the [B,4] records.
+        cams: None or B per-frame camera records (make_cams), as in forward_batch (esac_hip_backward_batch_cams)."""
+        sc, ha, B, sc_stride = self._batch_inputs("esac.backward_batch", scene_coords, out_gradients, hyp_assign)
         gt = np.ascontiguousarray(np.asarray(gt_poses, np.float32).reshape(-1))
         if gt.size != 16 * B:
             raise RuntimeError("esac.backward_batch: gtPoses must hold B 4x4 poses")
-        sc_stride = int(sc.stride(0)) if sc.dim() == 5 else 0
         host = np.zeros((B, 4), np.float64)
         if cams is None:
             rc = self.lib.esac_hip_backward_batch(
@@ -373,13 +378,7 @@ class Engine:
         Returns the device float64 tensor [B,4] of records (`out` when given).  A singular ground-truth pose or an out-of-range
         assignment is a per-frame outcome (record[3] = 2 / 1): check() after a synchronisation raises for it.
         cams: None or B per-frame camera records (make_cams), copied before the call returns."""
-        sc = scene_coords if scene_coords.is_cuda else scene_coords.to(self.device, non_blocking=True)
-        ha = hyp_assign if hyp_assign.is_cuda else hyp_assign.to(self.device, non_blocking=True)
-        sc, ha = sc.contiguous(), ha.contiguous()
-        B = int(ha.shape[0])
-        if not (out_gradients.is_cuda and out_gradients.is_contiguous() and out_gradients.dtype == torch.float32
-                and out_gradients.dim() == 5 and out_gradients.shape[0] == B and tuple(out_gradients.shape[1:]) == tuple(sc.shape[-4:])):
-            raise RuntimeError("esac.backward_batch_async: the gradient tensor must be a dense float32 device tensor [B,E,3,H,W]")
+        sc, ha, B, sc_stride = self._batch_inputs("esac.backward_batch_async", scene_coords, out_gradients, hyp_assign)
         if isinstance(gt_poses, torch.Tensor) and gt_poses.is_cuda:
             gt = gt_poses
         else:
@@ -397,7 +396,6 @@ class Engine:
             out = torch.empty((B, 4), dtype=torch.float64, device=self.device)
         elif not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (B, 4)):
             raise RuntimeError("esac.backward_batch_async: out must be a dense float64 device tensor [B,4]")
-        sc_stride = int(sc.stride(0)) if sc.dim() == 5 else 0
         table = None
         if cams is not None:
             table = _cams_arg(cams, B, "esac.backward_batch_async")
@@ -910,6 +908,30 @@ def backward(sceneCoordinates, outGradients, hypAssignment, gtPose, wLossRot, wL
     return float(out[0])
 
 
+def _check_batch_tensors(who, sceneCoordinates, outGradients, hypAssignment, gtPoses, name_each):
+    """Types, dtypes and shapes of a batched training call's four tensors; returns B, N, E, H, W.
+    name_each: an argument that is no tensor is reported by its name (backward_batch_async), otherwise in one sentence for all
+    four (backward_batch)."""
+    for name, t in (("sceneCoordinates", sceneCoordinates), ("outGradients", outGradients), ("hypAssignment", hypAssignment),
+                    ("gtPoses", gtPoses)):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError("%s: %s must be a torch.Tensor" % (who, name) if name_each else
+                               "%s: every tensor argument must be a torch.Tensor" % who)
+    if hypAssignment.dtype != torch.int64 or hypAssignment.dim() != 2 or hypAssignment.numel() == 0:
+        raise RuntimeError("%s: hypAssignment must be a non-empty int64 [B,N]" % who)
+    B, N = hypAssignment.shape
+    if sceneCoordinates.dtype != torch.float32 or sceneCoordinates.dim() not in (4, 5) or sceneCoordinates.size(-3) != 3:
+        raise RuntimeError("%s: sceneCoordinates must be float32 [B,E,3,H,W] or [E,3,H,W]" % who)
+    if sceneCoordinates.dim() == 5 and sceneCoordinates.size(0) != B:
+        raise RuntimeError("%s: batch sizes of sceneCoordinates and hypAssignment differ" % who)
+    E, H, W = sceneCoordinates.shape[-4], sceneCoordinates.shape[-2], sceneCoordinates.shape[-1]
+    if outGradients.dtype != torch.float32 or tuple(outGradients.shape) != (B, E, 3, H, W):
+        raise RuntimeError("%s: outGradients must be float32 [B,E,3,H,W]" % who)
+    if gtPoses.dtype != torch.float32 or tuple(gtPoses.shape) != (B, 4, 4):
+        raise RuntimeError("%s: gtPoses must be float32 [B,4,4]" % who)
+    return B, N, E, H, W
+
+
 def backward_batch(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLossRot, wLossTrans, lossCut, shiftX, shiftY,
                    focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling):
     """Batched companion of `backward` (new API): sceneCoordinates [B,E,3,H,W] (or [E,3,H,W] shared by all frames),
@@ -920,20 +942,7 @@ def backward_batch(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLoss
     Each of shiftX, shiftY, focalLength, ppointX, ppointY is a scalar (the whole batch) or a length-B sequence / 1-D tensor /
     numpy array: frame b uses element b (a training mini-batch: one random shift and one focal length per image)."""
     _no_strict_training("esac.backward_batch")
-    if not all(isinstance(t, torch.Tensor) for t in (sceneCoordinates, outGradients, hypAssignment, gtPoses)):
-        raise RuntimeError("esac.backward_batch: every tensor argument must be a torch.Tensor")
-    if hypAssignment.dtype != torch.int64 or hypAssignment.dim() != 2 or hypAssignment.numel() == 0:
-        raise RuntimeError("esac.backward_batch: hypAssignment must be a non-empty int64 [B,N]")
-    B, N = hypAssignment.shape
-    if sceneCoordinates.dtype != torch.float32 or sceneCoordinates.dim() not in (4, 5) or sceneCoordinates.size(-3) != 3:
-        raise RuntimeError("esac.backward_batch: sceneCoordinates must be float32 [B,E,3,H,W] or [E,3,H,W]")
-    if sceneCoordinates.dim() == 5 and sceneCoordinates.size(0) != B:
-        raise RuntimeError("esac.backward_batch: batch sizes of sceneCoordinates and hypAssignment differ")
-    E, H, W = sceneCoordinates.shape[-4], sceneCoordinates.shape[-2], sceneCoordinates.shape[-1]
-    if outGradients.dtype != torch.float32 or tuple(outGradients.shape) != (B, E, 3, H, W):
-        raise RuntimeError("esac.backward_batch: outGradients must be float32 [B,E,3,H,W]")
-    if gtPoses.dtype != torch.float32 or tuple(gtPoses.shape) != (B, 4, 4):
-        raise RuntimeError("esac.backward_batch: gtPoses must be float32 [B,4,4]")
+    B, N, E, H, W = _check_batch_tensors("esac.backward_batch", sceneCoordinates, outGradients, hypAssignment, gtPoses, name_each=False)
     if not hypAssignment.is_cuda:
         lo, hi = int(hypAssignment.min()), int(hypAssignment.max())
         if lo < 0 or hi >= E:
@@ -968,22 +977,7 @@ def backward_batch_async(sceneCoordinates, outGradients, hypAssignment, gtPoses,
     Advances the call counter by B.  The camera arguments are host values, as in backward_batch."""
     who = "esac.backward_batch_async"
     _no_strict_training(who)
-    for name, t in (("sceneCoordinates", sceneCoordinates), ("outGradients", outGradients), ("hypAssignment", hypAssignment),
-                    ("gtPoses", gtPoses)):
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError("%s: %s must be a torch.Tensor" % (who, name))
-    if hypAssignment.dtype != torch.int64 or hypAssignment.dim() != 2 or hypAssignment.numel() == 0:
-        raise RuntimeError("%s: hypAssignment must be a non-empty int64 [B,N]" % who)
-    B, N = hypAssignment.shape
-    if sceneCoordinates.dtype != torch.float32 or sceneCoordinates.dim() not in (4, 5) or sceneCoordinates.size(-3) != 3:
-        raise RuntimeError("%s: sceneCoordinates must be float32 [B,E,3,H,W] or [E,3,H,W]" % who)
-    if sceneCoordinates.dim() == 5 and sceneCoordinates.size(0) != B:
-        raise RuntimeError("%s: batch sizes of sceneCoordinates and hypAssignment differ" % who)
-    E, H, W = sceneCoordinates.shape[-4], sceneCoordinates.shape[-2], sceneCoordinates.shape[-1]
-    if outGradients.dtype != torch.float32 or tuple(outGradients.shape) != (B, E, 3, H, W):
-        raise RuntimeError("%s: outGradients must be float32 [B,E,3,H,W]" % who)
-    if gtPoses.dtype != torch.float32 or tuple(gtPoses.shape) != (B, 4, 4):
-        raise RuntimeError("%s: gtPoses must be float32 [B,4,4]" % who)
+    B, N, E, H, W = _check_batch_tensors(who, sceneCoordinates, outGradients, hypAssignment, gtPoses, name_each=True)
     (shiftX, shiftY, focalLength, ppointX, ppointY), cams = _per_frame_cams(who, B, shiftX, shiftY, focalLength, ppointX, ppointY)
     if not outGradients.is_contiguous():
         raise RuntimeError("%s: outGradients must be contiguous (an asynchronous call cannot copy back into strided storage)" % who)

@@ -1181,9 +1181,138 @@ static int ensure_bws(esac_hip_ctx* c, int N, int P, int cap, int B = 1) {
     return 0;
 }
 
+// Bytes of slot workspace one slot is CHARGED against the context's budget (ESAC_BWD_BATCH_BUDGET_MB): two inlier maps, the two
+// 3P-double slabs, and the correspondence list at its true size corr_entries(P).  The batched calls size their chunks by this
+// and nothing else.  It is less than ensure_bws allocates per slot: that rounds the list up to its bound P + 2048 entries and
+// adds the slot's team granules (2 * ESAC_REFINE_TEAM_MAX * 32 granules of 16 bytes), and the per-frame tables (selection,
+// probabilities, losses, poses, dloss, map_info: a few dozen bytes per hypothesis) are not charged at all.  The chunk sizes
+// that tests and callers see under a given budget follow from this value, so it stays what it is.
+static long long bwd_slot_bytes(int P) {
+    return 2LL * P + 2LL * 3 * P * (long long)sizeof(double) + (P > ESAC_REFINE_LDS_CAP ? corr_entries(P) * 16 : 0);
+}
+
+// The slot count a rerun after an overflow is sized by: the selection's true count in whole 32s, at most the worst case
+static int grown_cap(int needed, int worst) { return needed + 31 > worst ? worst : (needed + 31) / 32 * 32; }
+
 // The loss's view of a ground-truth camera pose (gt_math.hpp: the text k_bwd_gt_prepare runs on the device), on the host.
 // false: singular.
 static bool gt_host(const float* h_gt_pose, double gt[16], double gt_pose[6]) { return gt_from_pose(h_gt_pose, gt, gt_pose); }
+
+// The checks of the two batched entry points, before either touches the device.  Both report under `who` (the asynchronous call
+// under the blocking call's name too: its callers match these messages); what they differ in is the result pointer -- `out` is
+// host memory of the blocking call (async == false) and device memory of the asynchronous one, each with its own message and
+// its own place in the order.
+static int check_batch_call(const char* who, const esac_hip_ctx* c, const esac_hip_params* p, int B, bool tensors, bool async, const void* out,
+                            int64_t sc_frame_stride, int64_t grad_frame_stride) {
+    if (!c) return fail(-1, "null context");
+    if (!p) return fail(-1, "null params");
+    if (!tensors) return fail(-1, "%s: null coordinate, gradient, assignment or ground-truth pointer", who);
+    if (async && !out) return fail(-1, "esac_hip_backward_batch_dev: d_out (device double[B,4]) is required");
+    if (p->flags & ESAC_FLAG_STRICT_REFERENCE)
+        return fail(-4, "%s: the training path has no strict mode (ESAC_FLAG_STRICT_REFERENCE is a forward flag)", who);
+    if (!async && !out) return fail(-4, "%s: the batched call is blocking only: h_out (host double[B,4]) is required", who);
+    if (B < 1 || B > ESAC_MAX_BATCH) return fail(-4, "%s: batch size %d outside [1,%d]", who, B, ESAC_MAX_BATCH);
+    if (p->d_hyp_index || p->hyp_offset)
+        return fail(-4, "%s: sharded calls are not supported (the expectation needs every hypothesis)", who);
+    if (p->E > 65535) return fail(-4, "%s: at most 65535 experts (one grid row per expert in the accumulation kernel)", who);
+    if (p->E <= 0 || p->H <= 0 || p->W <= 0 || p->N <= 0) return fail(-4, "E=%d, H=%d, W=%d, N=%d must be positive", p->E, p->H, p->W, p->N);
+    const long long slab = (long long)p->E * 3 * p->H * p->W;
+    if (sc_frame_stride < 0) return fail(-4, "%s: negative coordinate frame stride", who);
+    if (B > 1 && grad_frame_stride < slab)
+        return fail(-4, "%s: gradient frame stride %lld < E*3*H*W = %lld (frames would share gradients)", who,
+                    (long long)grad_frame_stride, slab);
+    return 0;
+}
+
+// Hypotheses and their reference-arithmetic scores of every frame of `a` (per_frame_shape: each frame of a batch summed as a
+// single call sums it)
+static int enqueue_bwd_sampling(esac_hip_ctx* c, KArgs& a, hipStream_t s, bool per_frame_shape) {
+    a.tstamps = nullptr;
+    c->rt32_stale = false;
+    mark_sampling(c, a);
+    launch_sample(a, s);                                        // esac.cpp:276; frame b of a batch: call p->call + b
+    if (int rc = check_launch("k_sample")) return rc;
+    launch_rescore_all(a, s, per_frame_shape);                  // esac.cpp:295-316, reference arithmetic for every hypothesis
+    return check_launch("k_rescore(all)");
+}
+
+// The KArgs of a batch's chunk [b0, b0 + nb): camera record b0 in the inline fields, the call counter, the tensors and the camera
+// table offset by the chunk's first frame (validated, workspaces grown, a fresh epoch: make_args)
+static int chunk_args(esac_hip_ctx* c, const float* d_sc, int64_t sc_frame_stride, const int64_t* d_assign, const esac_hip_params* p,
+                      const esac_hip_frame_cam* h_cams, int b0, int nb, KArgs* a) {
+    esac_hip_params pc = h_cams ? with_cam(*p, h_cams[b0]) : *p;
+    pc.call = p->call + (uint64_t)b0;
+    if (int rc = make_args(c, d_sc + (size_t)b0 * sc_frame_stride, d_assign + (size_t)b0 * p->N, &pc, a, nb, sc_frame_stride, -1, true)) return rc;
+    if (h_cams) a->cams = c->d_cams + b0;
+    return 0;
+}
+
+// What a training call works on and towards, beyond the context's workspace.  The per-frame pointers are those of the call's
+// frame 0: fill_bwd offsets them by a chunk's first frame.
+struct BwdCall {
+    float* out_grad;              // accumulated into
+    long long grad_frame_stride;  // 0: a single call
+    double w_rot, w_trans, cut;
+    const double* gt = nullptr;        // single call: gt[16] and gt_pose[6] on the host, passed inline; or
+    const double* gt_pose = nullptr;
+    const double* gt_frames = nullptr; // batch: [B, ESAC_GT_DOUBLES] on the device
+    bool batch = false;                // the batch-wide overflow word (BwdArgs::sel_max)
+    int* frame_status = nullptr;       // asynchronous batch only: [B] per-frame outcomes and
+    double* rec_dev = nullptr;         // [B,4] the caller's device records
+};
+
+// a.bwd of one selection .. accumulation pass over `frames` frames from frame b0 of the call, `cap` slots each, in the context's
+// slot workspace (which ensure_bws has sized).  Every field a route does not use is null / 0 here, in this one place.
+// want_teams: refine the slots by teams where this call can (single blocking calls; a.bwd.team_max_slots != 0 says it will).
+static void fill_bwd(esac_hip_ctx* c, KArgs& a, const BwdCall& call, int b0, int frames, int cap, bool want_teams) {
+    c->last_bwd_frames = frames;
+    c->last_bwd_batch_cap = call.batch ? cap : 0;
+    a.frames = frames;  // (a rerun after an overflow may take fewer frames: their samples stay where they are)
+    a.bwd = c->bws;
+    a.bwd.cap = cap;
+    a.bwd.team = 0;  // (the slot-team launch sets these two)
+    a.bwd.team_tag = 0;
+    a.bwd.team_max_slots = want_teams && refine_slots_can_team(a) ? ESAC_SLOT_TEAMS_MAX : 0;  // 0: one workgroup per slot
+    a.bwd.out_grad = call.out_grad + (size_t)b0 * call.grad_frame_stride;
+    a.bwd.grad_frame_stride = call.grad_frame_stride;
+    a.bwd.w_rot = call.w_rot;
+    a.bwd.w_trans = call.w_trans;
+    a.bwd.cut = call.cut;
+    for (int i = 0; i < 16; i++) a.bwd.gt[i] = call.gt ? call.gt[i] : 0.0;
+    for (int i = 0; i < 6; i++) a.bwd.gt_pose[i] = call.gt_pose ? call.gt_pose[i] : 0.0;
+    a.bwd.gt_frames = call.gt_frames ? call.gt_frames + (size_t)b0 * ESAC_GT_DOUBLES : nullptr;
+    if (!call.batch) a.bwd.sel_max = nullptr;
+    a.bwd.frame_status = call.frame_status ? call.frame_status + b0 : nullptr;
+    a.bwd.rec_dev = call.rec_dev ? call.rec_dev + (size_t)b0 * 4 : nullptr;
+}
+
+// Selection .. accumulation of a.bwd's frames on `s`: enqueues and returns; a caller that wants the outcome waits for it.
+// Slot refinement (esac.cpp:328-347): by teams of 8 (esac_refine_team.hip) when THIS call's selection holds few enough slots
+// that every team has an XCD's CUs to itself (<= 32), one workgroup per slot otherwise.  The count is only known on the
+// device, so both launches are issued and each returns at once when the other one's case applies (team_max_slots): the
+// route is a function of the call's own inputs, not of what an earlier call on the context selected.
+// result_pin: the last workgroup of the accumulation hands the call's records (a frame's four values + "a slot team timed out")
+// to the pinned slots, one per frame: no copies, no stream-completion round trip.  NULL: nobody polls.
+static int enqueue_bwd_chain(esac_hip_ctx* c, KArgs& a, hipStream_t s, double* result_pin) {
+    int rc;
+    if (a.bwd.sel_max) HIP_OK(hipMemsetAsync(a.bwd.sel_max, 0, sizeof(int), s));
+    launch_bwd_select(a, s);                                    // esac.cpp:319-331
+    if ((rc = check_launch("k_bwd_select"))) return rc;
+    if (a.bwd.team_max_slots) {
+        launch_refine_slots_team(a, s);                         // a team per slot, when n_sel <= team_max_slots
+        c->slot_team_calls++;
+    }
+    launch_refine_slots(a, s);                                  // one workgroup per slot otherwise
+    if ((rc = check_launch("k_refine(slots)"))) return rc;
+    launch_bwd_loss(a, s);                                      // esac.cpp:354-362 + dLoss + softmax derivative (+ rec_dev)
+    if ((rc = check_launch("k_bwd_loss"))) return rc;
+    launch_bwd_paths(a, s);                                     // esac.cpp:375-463 (path I) and :470-488 (path II), side by side
+    if ((rc = check_launch("k_bwd_paths"))) return rc;
+    KArgs acc = a;
+    acc.result_pin = result_pin;
+    launch_bwd_accumulate(acc, s);                              // esac.cpp:491-508
+    return check_launch("k_bwd_accumulate");
+}
 
 extern "C" int esac_hip_backward(esac_hip_ctx* c, const float* d_sc, float* d_out_gradients, const int64_t* d_assign,
                                  const float* h_gt_pose, float w_loss_rot, float w_loss_trans, float loss_cut,
@@ -1213,58 +1342,20 @@ extern "C" int esac_hip_backward(esac_hip_ctx* c, const float* d_sc, float* d_ou
     }
     double gt[16], gt_pose[6];
     if (!gt_host(h_gt_pose, gt, gt_pose)) return fail(-4, "esac_hip_backward: the ground-truth pose is singular");
-    a.tstamps = nullptr;
+    BwdCall call = {d_out_gradients, 0, w_loss_rot, w_loss_trans, loss_cut};
+    call.gt = gt;
+    call.gt_pose = gt_pose;
     hipStream_t s = (hipStream_t)stream;
-    c->rt32_stale = false;
-    mark_sampling(c, a);
-    launch_sample(a, s);                                        // esac.cpp:276
-    if ((rc = check_launch("k_sample"))) return rc;
-    launch_rescore_all(a, s);                                   // esac.cpp:295-316, reference arithmetic for every hypothesis
-    if ((rc = check_launch("k_rescore(all)"))) return rc;
-    // Slot refinement (esac.cpp:328-347): by teams of 8 (esac_refine_team.hip) when THIS call's selection holds few enough slots
-    // that every team has an XCD's CUs to itself (<= 32), one workgroup per slot otherwise.  The count is only known on the
-    // device, so both launches are issued and each returns at once when the other one's case applies (team_max_slots): the
-    // route is a function of the call's own inputs, not of what an earlier call on the context selected.  A blocking call can
-    // refine again with one workgroup per slot should a team time out; an asynchronous one cannot and does not use teams.
+    if ((rc = enqueue_bwd_sampling(c, a, s, false))) return rc;
+    // A blocking call can refine again with one workgroup per slot should a slot team time out; an asynchronous one cannot and
+    // does not use teams.
     bool use_teams = h_out && c->slot_teams;
     for (int attempt = 0;; attempt++) {
         if ((rc = ensure_bws(c, p->N, P, cap))) return rc;
         if (cap > c->bcap) c->bcap = cap;
-        c->last_bwd_frames = 1;
-        c->last_bwd_batch_cap = 0;
-        a.bwd = c->bws;
-        a.bwd.sel_max = nullptr;  // (batched calls only)
-        a.bwd.gt_frames = nullptr;
-        a.bwd.grad_frame_stride = 0;
-        a.bwd.cap = cap;
-        a.bwd.team = 0;
-        a.bwd.team_tag = 0;
-        a.bwd.out_grad = d_out_gradients;
-        a.bwd.w_rot = (double)w_loss_rot;
-        a.bwd.w_trans = (double)w_loss_trans;
-        a.bwd.cut = (double)loss_cut;
-        for (int i = 0; i < 16; i++) a.bwd.gt[i] = gt[i];
-        for (int i = 0; i < 6; i++) a.bwd.gt_pose[i] = gt_pose[i];
-        const bool teams = use_teams && refine_slots_can_team(a);
-        a.bwd.team_max_slots = teams ? ESAC_SLOT_TEAMS_MAX : 0;
-        launch_bwd_select(a, s);                                    // esac.cpp:319-331
-        if ((rc = check_launch("k_bwd_select"))) return rc;
-        if (teams) {
-            launch_refine_slots_team(a, s);                         // a team per slot, when n_sel <= team_max_slots
-            c->slot_team_calls++;
-        }
-        launch_refine_slots(a, s);                                  // one workgroup per slot otherwise
-        if ((rc = check_launch("k_refine(slots)"))) return rc;
-        launch_bwd_loss(a, s);                                      // esac.cpp:354-362 + dLoss + softmax derivative
-        if ((rc = check_launch("k_bwd_loss"))) return rc;
-        launch_bwd_paths(a, s);                                     // esac.cpp:375-463 (path I) and :470-488 (path II), side by side
-        if ((rc = check_launch("k_bwd_paths"))) return rc;
-        // the last workgroup of the accumulation hands the call's record (h_out's four values + "a slot team timed out") to the
-        // pinned slot: no copies, no stream-completion round trip (two hipMemcpyAsync + hipStreamSynchronize before)
-        KArgs acc = a;
-        acc.result_pin = h_out ? c->d_pin : nullptr;
-        launch_bwd_accumulate(acc, s);                              // esac.cpp:491-508
-        if ((rc = check_launch("k_bwd_accumulate"))) return rc;
+        fill_bwd(c, a, call, 0, 1, cap, use_teams);
+        const bool teams = a.bwd.team_max_slots != 0;
+        if ((rc = enqueue_bwd_chain(c, a, s, h_out ? c->d_pin : nullptr))) return rc;
         if (!h_out) return 0;
         if ((rc = wait_record(c, s, 1, a.epoch, "esac_hip_backward: the accumulation kernel"))) return rc;
         __sync_synchronize();
@@ -1283,7 +1374,7 @@ extern "C" int esac_hip_backward(esac_hip_ctx* c, const float* d_sc, float* d_ou
         c->last_bwd_teams = teams && c->last_nsel <= ESAC_SLOT_TEAMS_MAX;
         const int needed = (int)h_out[1];
         if (needed <= cap || attempt >= 1) break;  // one retry suffices: the second pass is sized by the true count
-        cap = needed + 31 > worst ? worst : (needed + 31) / 32 * 32;
+        cap = grown_cap(needed, worst);
         c->epoch += 1.0;
         a.epoch = c->epoch;
     }
@@ -1311,99 +1402,47 @@ extern "C" int esac_hip_backward_batch_cams(esac_hip_ctx* c, int B, const float*
                                             int64_t grad_frame_stride, const int64_t* d_assign, const float* h_gt_poses,
                                             const esac_hip_frame_cam* h_cams, float w_loss_rot, float w_loss_trans, float loss_cut,
                                             const esac_hip_params* p, void* stream, double* h_out) {
-    if (!c) return fail(-1, "null context");
-    if (!p) return fail(-1, "null params");
-    if (!d_sc || !d_out_gradients || !d_assign || !h_gt_poses)
-        return fail(-1, "esac_hip_backward_batch: null coordinate, gradient, assignment or ground-truth pointer");
-    if (p->flags & ESAC_FLAG_STRICT_REFERENCE)
-        return fail(-4, "esac_hip_backward_batch: the training path has no strict mode (ESAC_FLAG_STRICT_REFERENCE is a forward flag)");
-    if (!h_out) return fail(-4, "esac_hip_backward_batch: the batched call is blocking only: h_out (host double[B,4]) is required");
-    if (B < 1 || B > ESAC_MAX_BATCH) return fail(-4, "esac_hip_backward_batch: batch size %d outside [1,%d]", B, ESAC_MAX_BATCH);
-    if (p->d_hyp_index || p->hyp_offset)
-        return fail(-4, "esac_hip_backward_batch: sharded calls are not supported (the expectation needs every hypothesis)");
-    if (p->E > 65535) return fail(-4, "esac_hip_backward_batch: at most 65535 experts (one grid row per expert in the accumulation kernel)");
-    if (p->E <= 0 || p->H <= 0 || p->W <= 0 || p->N <= 0) return fail(-4, "E=%d, H=%d, W=%d, N=%d must be positive", p->E, p->H, p->W, p->N);
-    const long long slab = (long long)p->E * 3 * p->H * p->W;
-    if (sc_frame_stride < 0) return fail(-4, "esac_hip_backward_batch: negative coordinate frame stride");
-    if (B > 1 && grad_frame_stride < slab)
-        return fail(-4, "esac_hip_backward_batch: gradient frame stride %lld < E*3*H*W = %lld (frames would share gradients)",
-                    (long long)grad_frame_stride, slab);
+    int rc = check_batch_call("esac_hip_backward_batch", c, p, B, d_sc && d_out_gradients && d_assign && h_gt_poses, false, h_out,
+                              sc_frame_stride, grad_frame_stride);
+    if (rc) return rc;
     DeviceGuard guard(c->device);
     hipStream_t s = (hipStream_t)stream;
     if (!c->h_gt) {
-        HIP_OK(hipHostMalloc((void**)&c->h_gt, (size_t)ESAC_MAX_BATCH * 22 * sizeof(double), hipHostMallocDefault));
-        HIP_OK(hipMalloc((void**)&c->d_gt, (size_t)ESAC_MAX_BATCH * 22 * sizeof(double)));
+        HIP_OK(hipHostMalloc((void**)&c->h_gt, (size_t)ESAC_MAX_BATCH * ESAC_GT_DOUBLES * sizeof(double), hipHostMallocDefault));
+        HIP_OK(hipMalloc((void**)&c->d_gt, (size_t)ESAC_MAX_BATCH * ESAC_GT_DOUBLES * sizeof(double)));
     }
     HIP_OK(hipStreamSynchronize(s));  // (the staging buffer is free: a batch that failed half-way may have left its copy queued)
     for (int b = 0; b < B; b++) {
-        double* g = c->h_gt + (size_t)b * 22;
+        double* g = c->h_gt + (size_t)b * ESAC_GT_DOUBLES;
         if (!gt_host(h_gt_poses + (size_t)b * 16, g, g + 16))
             return fail(-4, "esac_hip_backward_batch: the ground-truth pose of frame %d is singular", b);
     }
     // validation of the parameters (make_args) before anything is launched: the caller's gradients stay untouched on an error
     KArgs a;
-    int rc;
-    if (h_cams) {
-        const esac_hip_params p0 = with_cam(*p, h_cams[0]);
-        if ((rc = make_args(c, d_sc, d_assign, &p0, &a, 1, 0, 0, true))) return rc;
-        if ((rc = stage_cams(c, &p0, h_cams, B, s))) return rc;  // (checks every record before the first launch)
-    } else if ((rc = make_args(c, d_sc, d_assign, p, &a, 1, 0, -1, true))) {
-        return rc;
-    }
-    HIP_OK(hipMemcpyAsync(c->d_gt, c->h_gt, (size_t)B * 22 * sizeof(double), hipMemcpyHostToDevice, s));
+    const esac_hip_params p0 = h_cams ? with_cam(*p, h_cams[0]) : *p;
+    if ((rc = make_args(c, d_sc, d_assign, &p0, &a, 1, 0, h_cams ? 0 : -1, true))) return rc;
+    if (h_cams && (rc = stage_cams(c, &p0, h_cams, B, s))) return rc;  // (checks every record before the first launch)
+    HIP_OK(hipMemcpyAsync(c->d_gt, c->h_gt, (size_t)B * ESAC_GT_DOUBLES * sizeof(double), hipMemcpyHostToDevice, s));
+    BwdCall call = {d_out_gradients, grad_frame_stride, w_loss_rot, w_loss_trans, loss_cut};
+    call.gt_frames = c->d_gt;
+    call.batch = true;
     const int N = p->N, P = p->H * p->W, worst = bwd_rows(N);
-    const long long per_slot = 2LL * P + 2LL * 3 * P * (long long)sizeof(double) +
-                               (P > ESAC_REFINE_LDS_CAP ? corr_entries(P) * 16 : 0);  // inlier maps, two slabs, correspondence list
     int cap = c->bcap_batch > 64 ? c->bcap_batch : 64;
     if (cap > worst) cap = worst;
     auto chunk_frames = [&](int cap_, int left) {
-        const long long f = c->bwd_budget / ((long long)cap_ * per_slot);
+        const long long f = c->bwd_budget / ((long long)cap_ * bwd_slot_bytes(P));
         return (int)(f < 1 ? 1 : (f > left ? left : f));
     };
     bool any_bad = false;
     for (int b0 = 0; b0 < B;) {
         int nb = chunk_frames(cap, B - b0);
-        esac_hip_params pc = h_cams ? with_cam(*p, h_cams[b0]) : *p;
-        pc.call = p->call + (uint64_t)b0;
-        if ((rc = make_args(c, d_sc + (size_t)b0 * sc_frame_stride, d_assign + (size_t)b0 * N, &pc, &a, nb, sc_frame_stride, -1, true))) return rc;
-        if (h_cams) a.cams = c->d_cams + b0;
-        a.tstamps = nullptr;
-        c->rt32_stale = false;
-        mark_sampling(c, a);
-        launch_sample(a, s);                                    // frame b: call p->call + b
-        if ((rc = check_launch("k_sample"))) return rc;
-        launch_rescore_all(a, s, true);                         // (each frame summed as a single call sums it)
-        if ((rc = check_launch("k_rescore(all)"))) return rc;
+        if ((rc = chunk_args(c, d_sc, sc_frame_stride, d_assign, p, h_cams, b0, nb, &a))) return rc;
+        if ((rc = enqueue_bwd_sampling(c, a, s, true))) return rc;
         for (int attempt = 0;; attempt++) {
             if ((rc = ensure_bws(c, N, P, cap, nb))) return rc;
             if (cap > c->bcap_batch) c->bcap_batch = cap;
-            c->last_bwd_frames = nb;
-            c->last_bwd_batch_cap = cap;
-            a.frames = nb;  // (a rerun after an overflow may take fewer frames: their samples stay where they are)
-            a.bwd = c->bws;
-            a.bwd.cap = cap;
-            a.bwd.team = 0;
-            a.bwd.team_tag = 0;
-            a.bwd.team_max_slots = 0;  // one workgroup per slot
-            a.bwd.out_grad = d_out_gradients + (size_t)b0 * grad_frame_stride;
-            a.bwd.grad_frame_stride = grad_frame_stride;
-            a.bwd.gt_frames = c->d_gt + (size_t)b0 * 22;
-            a.bwd.w_rot = (double)w_loss_rot;
-            a.bwd.w_trans = (double)w_loss_trans;
-            a.bwd.cut = (double)loss_cut;
-            HIP_OK(hipMemsetAsync(a.bwd.sel_max, 0, sizeof(int), s));
-            launch_bwd_select(a, s);
-            if ((rc = check_launch("k_bwd_select"))) return rc;
-            launch_refine_slots(a, s);
-            if ((rc = check_launch("k_refine(slots)"))) return rc;
-            launch_bwd_loss(a, s);
-            if ((rc = check_launch("k_bwd_loss"))) return rc;
-            launch_bwd_paths(a, s);
-            if ((rc = check_launch("k_bwd_paths"))) return rc;
-            KArgs acc = a;
-            acc.result_pin = c->d_pin;  // one pinned slot per frame of the chunk
-            launch_bwd_accumulate(acc, s);
-            if ((rc = check_launch("k_bwd_accumulate"))) return rc;
+            fill_bwd(c, a, call, b0, nb, cap, false);
+            if ((rc = enqueue_bwd_chain(c, a, s, c->d_pin))) return rc;  // one pinned slot per frame of the chunk
             if ((rc = wait_record(c, s, nb, a.epoch, "esac_hip_backward_batch: the accumulation kernel"))) return rc;
             __sync_synchronize();
             int needed = 0;
@@ -1416,7 +1455,7 @@ extern "C" int esac_hip_backward_batch_cams(esac_hip_ctx* c, int B, const float*
                     for (int k = 0; k < 4; k++) h_out[(size_t)(b0 + b) * 4 + k] = c->h_pin[(size_t)b * ESAC_PIN_DOUBLES + k];
                 break;
             }
-            cap = needed + 31 > worst ? worst : (needed + 31) / 32 * 32;
+            cap = grown_cap(needed, worst);
             const int fit = chunk_frames(cap, nb);
             nb = fit < nb ? fit : nb;
             c->epoch += 1.0;
@@ -1441,32 +1480,16 @@ extern "C" int esac_hip_backward_batch_dev(esac_hip_ctx* c, int B, const float* 
                                            int64_t grad_frame_stride, const int64_t* d_assign, const float* d_gt_poses,
                                            const esac_hip_frame_cam* h_cams, float w_loss_rot, float w_loss_trans, float loss_cut,
                                            const esac_hip_params* p, void* stream, double* d_out) {
-    if (!c) return fail(-1, "null context");
-    if (!p) return fail(-1, "null params");
-    if (!d_sc || !d_out_gradients || !d_assign || !d_gt_poses)
-        return fail(-1, "esac_hip_backward_batch: null coordinate, gradient, assignment or ground-truth pointer");
-    if (!d_out) return fail(-1, "esac_hip_backward_batch_dev: d_out (device double[B,4]) is required");
-    if (p->flags & ESAC_FLAG_STRICT_REFERENCE)
-        return fail(-4, "esac_hip_backward_batch: the training path has no strict mode (ESAC_FLAG_STRICT_REFERENCE is a forward flag)");
-    if (B < 1 || B > ESAC_MAX_BATCH) return fail(-4, "esac_hip_backward_batch: batch size %d outside [1,%d]", B, ESAC_MAX_BATCH);
-    if (p->d_hyp_index || p->hyp_offset)
-        return fail(-4, "esac_hip_backward_batch: sharded calls are not supported (the expectation needs every hypothesis)");
-    if (p->E > 65535) return fail(-4, "esac_hip_backward_batch: at most 65535 experts (one grid row per expert in the accumulation kernel)");
-    if (p->E <= 0 || p->H <= 0 || p->W <= 0 || p->N <= 0) return fail(-4, "E=%d, H=%d, W=%d, N=%d must be positive", p->E, p->H, p->W, p->N);
-    const long long slab = (long long)p->E * 3 * p->H * p->W;
-    if (sc_frame_stride < 0) return fail(-4, "esac_hip_backward_batch: negative coordinate frame stride");
-    if (B > 1 && grad_frame_stride < slab)
-        return fail(-4, "esac_hip_backward_batch: gradient frame stride %lld < E*3*H*W = %lld (frames would share gradients)",
-                    (long long)grad_frame_stride, slab);
+    int rc = check_batch_call("esac_hip_backward_batch", c, p, B, d_sc && d_out_gradients && d_assign && d_gt_poses, true, d_out,
+                              sc_frame_stride, grad_frame_stride);
+    if (rc) return rc;
     // the chunking is known before anything is launched: cap is the worst case, so the first chunk is the largest
     const int N = p->N, P = p->H * p->W, cap = bwd_rows(N);
-    const long long per_slot = 2LL * P + 2LL * 3 * P * (long long)sizeof(double) +
-                               (P > ESAC_REFINE_LDS_CAP ? corr_entries(P) * 16 : 0);  // inlier maps, two slabs, correspondence list
-    const long long fit = c->bwd_budget / ((long long)cap * per_slot);
+    const long long fit = c->bwd_budget / ((long long)cap * bwd_slot_bytes(P));
     if (fit < 1)
         return fail(-4, "esac_hip_backward_batch_dev: one frame's worst case (%d slots, %lld MiB) exceeds the slot-workspace budget of "
                         "%lld MiB (ESAC_BWD_BATCH_BUDGET_MB); the blocking esac_hip_backward_batch sizes the workspace by the "
-                        "selection's true count", cap, ((long long)cap * per_slot) >> 20, c->bwd_budget >> 20);
+                        "selection's true count", cap, ((long long)cap * bwd_slot_bytes(P)) >> 20, c->bwd_budget >> 20);
     const int chunk = (int)(fit > B ? B : fit);
     DeviceGuard guard(c->device);
     hipStream_t s = (hipStream_t)stream;
@@ -1477,60 +1500,23 @@ extern "C" int esac_hip_backward_batch_dev(esac_hip_ctx* c, int B, const float* 
     // validation of the parameters and of every camera record, and the workspaces of the largest chunk, before anything is
     // launched: the caller's gradients stay untouched on an error
     KArgs a;
-    int rc;
-    if (h_cams) {
-        const esac_hip_params p0 = with_cam(*p, h_cams[0]);
-        if ((rc = make_args(c, d_sc, d_assign, &p0, &a, chunk, sc_frame_stride, 0, true))) return rc;
-        if ((rc = ensure_bws(c, N, P, cap, chunk))) return rc;
-        if ((rc = stage_cams(c, &p0, h_cams, B, s))) return rc;  // (checks every record before the first launch)
-    } else {
-        if ((rc = make_args(c, d_sc, d_assign, p, &a, chunk, sc_frame_stride, -1, true))) return rc;
-        if ((rc = ensure_bws(c, N, P, cap, chunk))) return rc;
-    }
+    const esac_hip_params p0 = h_cams ? with_cam(*p, h_cams[0]) : *p;
+    if ((rc = make_args(c, d_sc, d_assign, &p0, &a, chunk, sc_frame_stride, h_cams ? 0 : -1, true))) return rc;
+    if ((rc = ensure_bws(c, N, P, cap, chunk))) return rc;
+    if (h_cams && (rc = stage_cams(c, &p0, h_cams, B, s))) return rc;  // (checks every record before the first launch)
     launch_bwd_gt_prepare(d_gt_poses, B, c->d_gt_dev, c->d_frame_status, s);
     if ((rc = check_launch("k_bwd_gt_prepare"))) return rc;
-    for (int b0 = 0; b0 < B;) {
+    BwdCall call = {d_out_gradients, grad_frame_stride, w_loss_rot, w_loss_trans, loss_cut};
+    call.gt_frames = c->d_gt_dev;
+    call.batch = true;
+    call.frame_status = c->d_frame_status;
+    call.rec_dev = d_out;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = B - b0 < chunk ? B - b0 : chunk;
-        esac_hip_params pc = h_cams ? with_cam(*p, h_cams[b0]) : *p;
-        pc.call = p->call + (uint64_t)b0;
-        if ((rc = make_args(c, d_sc + (size_t)b0 * sc_frame_stride, d_assign + (size_t)b0 * N, &pc, &a, nb, sc_frame_stride, -1, true))) return rc;
-        if (h_cams) a.cams = c->d_cams + b0;
-        a.tstamps = nullptr;
-        c->rt32_stale = false;
-        mark_sampling(c, a);
-        launch_sample(a, s);                                    // frame b: call p->call + b
-        if ((rc = check_launch("k_sample"))) return rc;
-        launch_rescore_all(a, s, true);                         // (each frame summed as a single call sums it)
-        if ((rc = check_launch("k_rescore(all)"))) return rc;
-        c->last_bwd_frames = nb;  // (the slot workspace was sized for the largest chunk above)
-        c->last_bwd_batch_cap = cap;
-        a.bwd = c->bws;
-        a.bwd.cap = cap;
-        a.bwd.team = 0;
-        a.bwd.team_tag = 0;
-        a.bwd.team_max_slots = 0;  // one workgroup per slot
-        a.bwd.out_grad = d_out_gradients + (size_t)b0 * grad_frame_stride;
-        a.bwd.grad_frame_stride = grad_frame_stride;
-        a.bwd.gt_frames = c->d_gt_dev + (size_t)b0 * ESAC_GT_DOUBLES;
-        a.bwd.frame_status = c->d_frame_status + b0;
-        a.bwd.rec_dev = d_out + (size_t)b0 * 4;
-        a.bwd.w_rot = (double)w_loss_rot;
-        a.bwd.w_trans = (double)w_loss_trans;
-        a.bwd.cut = (double)loss_cut;
-        HIP_OK(hipMemsetAsync(a.bwd.sel_max, 0, sizeof(int), s));
-        launch_bwd_select(a, s);
-        if ((rc = check_launch("k_bwd_select"))) return rc;
-        launch_refine_slots(a, s);
-        if ((rc = check_launch("k_refine(slots)"))) return rc;
-        launch_bwd_loss(a, s);                                  // (also frame b's record into d_out[b*4..])
-        if ((rc = check_launch("k_bwd_loss"))) return rc;
-        launch_bwd_paths(a, s);
-        if ((rc = check_launch("k_bwd_paths"))) return rc;
-        KArgs acc = a;
-        acc.result_pin = nullptr;  // nobody polls
-        launch_bwd_accumulate(acc, s);
-        if ((rc = check_launch("k_bwd_accumulate"))) return rc;
-        b0 += nb;
+        if ((rc = chunk_args(c, d_sc, sc_frame_stride, d_assign, p, h_cams, b0, nb, &a))) return rc;
+        if ((rc = enqueue_bwd_sampling(c, a, s, true))) return rc;
+        fill_bwd(c, a, call, b0, nb, cap, false);  // (the slot workspace was sized for the largest chunk above)
+        if ((rc = enqueue_bwd_chain(c, a, s, nullptr))) return rc;  // k_bwd_loss writes frame b's record into d_out[b*4..]
     }
     c->last_dev_batch = B;
     return 0;

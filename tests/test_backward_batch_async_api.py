@@ -31,15 +31,27 @@ def test_the_abi_version_is_still_6():
 
 
 def test_the_call_path_holds_no_host_wait():
-    """The body of esac_hip_backward_batch_dev: no stream synchronisation, no blocking copy, no polling of a pinned record, and
-    no second pass."""
+    """esac_hip_backward_batch_dev and the helpers on its launch path (the chunk prologue, the sampling prologue, the fill of
+    a.bwd and the selection .. accumulation chain, each from its signature to its closing brace): no stream synchronisation, no
+    blocking copy, no polling of a pinned record, and no second pass.  The accumulation is launched from one place in the file,
+    so no entry point has a chain of its own beside the shared one."""
     with open(os.path.join(ROOT, "esac_amd", "csrc", "esac_capi.hip")) as fh:
         text = fh.read()
-    start = text.index('extern "C" int esac_hip_backward_batch_dev(')
-    body = text[start:text.index('\nextern "C"', start + 10)]
+    bodies = []
+    for signature in ('extern "C" int esac_hip_backward_batch_dev(', "static int chunk_args(", "static int enqueue_bwd_sampling(",
+                      "static void fill_bwd(", "static int enqueue_bwd_chain("):
+        assert text.count(signature) == 1, signature
+        start = text.index(signature)
+        bodies.append(text[start:text.index("\n}\n", start) + 3])
+        assert bodies[-1].count("\n") > 5, signature  # (a body, not a declaration)
+    dev = bodies[0]
+    for helper in ("chunk_args(", "enqueue_bwd_sampling(", "fill_bwd(", "enqueue_bwd_chain("):
+        assert helper in dev, helper
+    body = "\n".join(bodies)
     assert "launch_bwd_accumulate" in body and "launch_bwd_gt_prepare" in body
     for word in ("hipStreamSynchronize", "hipDeviceSynchronize", "hipMemcpy(", "wait_record", "hipEventSynchronize", "attempt"):
         assert word not in body, word
+    assert text.count("launch_bwd_accumulate(") == 1
 
 
 def test_backward_batch_async_is_exported_by_the_drop_in_module():

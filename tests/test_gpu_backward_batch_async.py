@@ -322,6 +322,66 @@ def test_an_out_of_range_assignment_flags_its_frame(solo):
     _assert_matches_blocking(got, want, "beside a flagged frame", frames=[0, 2, 3])
 
 
+def test_async_rejects_bad_arguments_before_launching(solo):
+    """esac_hip_backward_batch_dev's twin of test_gpu_backward_batch.py::test_batch_rejects_bad_arguments_before_launching, on its
+    shape (E=3, 60x80, N=64, B=4): every argument error is reported before a launch (the prefilled gradient tensor is
+    bit-unchanged after a synchronisation), with the status and the message written out here, and -- for every defect that
+    both entry points check -- with the very bytes that the blocking esac_hip_backward_batch reports for the same defect."""
+    f = S.make_frame(280, E=3, true_expert=0)
+    B, N, slab = 4, 64, 3 * 3 * 60 * 80
+    sc = torch.from_numpy(np.stack([f["coords"]] * B)).cuda()
+    ha = torch.zeros((B, N), dtype=torch.int64, device="cuda")
+    g = torch.from_numpy(np.random.default_rng(1).normal(size=(B,) + f["coords"].shape).astype(np.float32)).cuda()
+    g_keep = g.clone()
+    gt_host = np.stack([np.array(f["gt_pose"], np.float32)] * B)
+    gt_dev = torch.from_numpy(gt_host).cuda()
+    rec_dev = torch.zeros((B, 4), dtype=torch.float64, device="cuda")
+    rec_host = np.zeros((B, 4), np.float64)
+    lib = solo.lib
+
+    def call(dev, B_=B, sc_=None, grad=None, ha_=None, gt=None, stride=slab, p=None, out=None):
+        p = p if p is not None else solo.make_params(3, 60, 80, N)
+        head = (solo.ctx, B_, sc.data_ptr() if sc_ is None else sc_, slab, g.data_ptr() if grad is None else grad, stride,
+                ha.data_ptr() if ha_ is None else ha_)
+        tail = (1.0, 100.0, 100.0, C.byref(p), solo._stream())
+        if dev:
+            rc = lib.esac_hip_backward_batch_dev(*head, gt_dev.data_ptr() if gt is None else gt, None, *tail,
+                                                 rec_dev.data_ptr() if out is None else out)
+        else:
+            rc = lib.esac_hip_backward_batch(*head, gt_host.ctypes.data if gt is None else gt, *tail,
+                                             rec_host.ctypes.data if out is None else out)
+        return rc, lib.esac_hip_last_error()
+
+    who = b"esac_hip_backward_batch: "
+    null = (-1, who + b"null coordinate, gradient, assignment or ground-truth pointer")
+    cases = [  # (the defect, status and message of the asynchronous call, whether the blocking call checks the same thing)
+        (dict(B_=0), (-4, who + b"batch size 0 outside [1,1024]"), True),
+        (dict(B_=1025), (-4, who + b"batch size 1025 outside [1,1024]"), True),
+        (dict(sc_=0), null, True),
+        (dict(grad=0), null, True),
+        (dict(ha_=0), null, True),
+        (dict(gt=0), null, True),
+        (dict(out=0), (-1, b"esac_hip_backward_batch_dev: d_out (device double[B,4]) is required"), False),
+        (dict(p=solo.make_params(3, 60, 80, N, hyp_offset=16)),
+         (-4, who + b"sharded calls are not supported (the expectation needs every hypothesis)"), True),
+        (dict(stride=slab - 1), (-4, who + b"gradient frame stride 43199 < E*3*H*W = 43200 (frames would share gradients)"), True),
+        (dict(p=solo.make_params(70000, 60, 80, N)),
+         (-4, who + b"at most 65535 experts (one grid row per expert in the accumulation kernel)"), True),
+        (dict(p=solo.make_params(3, 60, 80, N, strict_reference=True)),
+         (-4, who + b"the training path has no strict mode (ESAC_FLAG_STRICT_REFERENCE is a forward flag)"), True),
+    ]
+    for kw, want, shared in cases:
+        got = call(True, **kw)
+        print(sorted(kw), got)
+        assert got[0] != 0 and got == want, (kw, got)
+        torch.cuda.synchronize()
+        assert torch.equal(g, g_keep), kw
+        if shared:
+            assert call(False, **kw) == got, kw
+            torch.cuda.synchronize()
+            assert torch.equal(g, g_keep), kw
+
+
 # ---------------------------------------------------------------- 6. the other features
 def test_async_with_per_frame_cameras(solo):
     frames, has, gts, cams = _cam_case(1100)
