@@ -608,11 +608,18 @@ static int check_launch(const char* what) {
 
 // A launch that (re)samples the hypotheses: the status word (out-of-range hypAssignment) is tagged with ITS epoch, and
 // every later stage / check on this context compares against that -- not against the epoch of whatever call came last.
+// (The sampler forms the fp32 [R|t] rows of its hypotheses itself: nothing of esac_hip_write_hyps is left to rebuild.)
 static void mark_sampling(esac_hip_ctx* c, KArgs& a) {
+    c->rt32_stale = false;
     c->sample_epoch = a.epoch;
     a.sample_epoch = a.epoch;
 }
 
+// hypotheses that came from esac_hip_write_hyps: the first stage that reads their fp32 [R|t] rows and rotation matrices forms them
+static void ensure_rt32(esac_hip_ctx* c, const KArgs& a, hipStream_t s) {
+    if (c->rt32_stale) launch_hyps_to_rt32(a, s);
+    c->rt32_stale = false;
+}
 // stage entry points: validate, make the context's GPU current, launch one phase on the caller's stream
 template <typename Launch>
 static int run_stage(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign, const esac_hip_params* p, void* stream,
@@ -629,25 +636,18 @@ extern "C" int esac_hip_sample(esac_hip_ctx* c, const float* d_sc, const int64_t
     return run_stage(c, d_sc, d_assign, p, stream, "k_sample", [](esac_hip_ctx* cc, const KArgs& a0, hipStream_t s) {
         KArgs a = a0;
         mark_sampling(cc, a);
-        cc->rt32_stale = false;
         launch_sample(a, s);
     });
 }
 extern "C" int esac_hip_score(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign, const esac_hip_params* p, void* stream) {
     return run_stage(c, d_sc, d_assign, p, stream, "k_score_fast", [](esac_hip_ctx* cc, const KArgs& a, hipStream_t s) {
-        if (cc->rt32_stale) {  // hypotheses came from esac_hip_write_hyps: their fp32 [R|t] rows need the maps' origins
-            launch_hyps_to_rt32(a, s);
-            cc->rt32_stale = false;
-        }
+        ensure_rt32(cc, a, s);
         launch_score(a, s);
     });
 }
 extern "C" int esac_hip_select(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign, const esac_hip_params* p, void* stream) {
     return run_stage(c, d_sc, d_assign, p, stream, "k_select_rescore", [](esac_hip_ctx* cc, const KArgs& a, hipStream_t s) {
-        if (cc->rt32_stale) {  // hypotheses came from esac_hip_write_hyps: their rotation matrices have not been formed yet
-            launch_hyps_to_rt32(a, s);
-            cc->rt32_stale = false;
-        }
+        ensure_rt32(cc, a, s);
         launch_select_rescore(a, s);
     });
 }
@@ -660,10 +660,7 @@ extern "C" int esac_hip_refine(esac_hip_ctx* c, const float* d_sc, const int64_t
 }
 extern "C" int esac_hip_score_exact(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign, const esac_hip_params* p, void* stream) {
     return run_stage(c, d_sc, d_assign, p, stream, "k_rescore(all)", [](esac_hip_ctx* cc, const KArgs& a, hipStream_t s) {
-        if (cc->rt32_stale) {
-            launch_hyps_to_rt32(a, s);
-            cc->rt32_stale = false;
-        }
+        ensure_rt32(cc, a, s);
         launch_rescore_all(a, s);
         launch_stats_exact(a, s);  // softmax statistics of the exact scores (the record's probability / entropy)
     });
@@ -708,22 +705,45 @@ static int wait_record(esac_hip_ctx* c, hipStream_t s, int B, double want, const
     return 0;
 }
 
-static int forward_impl(esac_hip_ctx* c, const float* d_sc, long long sc_frame_stride, const int64_t* d_assign,
-                        const esac_hip_params* p, int B, void* stream, double* d_scores_out, double* d_result_out,
-                        double* h_result_out, const esac_hip_frame_cam* h_cams = nullptr) {
-    if (!c) return fail(-1, "null context");
-    const double t_entry = now_ns();
-    DeviceGuard guard(c->device);
-    KArgs a;
-    esac_hip_params p0;
-    if (h_cams && p) {  // the inline fields carry record 0 (device_common.hpp:frame_view)
-        p0 = with_cam(*p, h_cams[0]);
-        p = &p0;
+// ---- the steps of a forward call (forward_impl strings them together)
+static double pin_status(const esac_hip_ctx* c, int b) { return c->h_pin[(size_t)b * ESAC_PIN_DOUBLES + ESAC_PIN_STATUS]; }
+// ESAC_FLAG_AUTO_EXACT: the guaranteed routes where they are free (include/esac_hip.h)
+static void apply_auto_exact(KArgs& a, int B) {
+    if ((a.flags & ESAC_FLAG_AUTO_EXACT) && B == 1 && a.E == 1 && (long long)a.N * a.H * a.W <= ESAC_AUTO_EXACT_MAX_WORK)
+        a.flags |= ESAC_FLAG_EXACT_SCORES | ESAC_FLAG_EXACT_SAMPLING;
+}
+// KArgs::fold_select of the serial route (a team that refines <= 256 hypotheses of one frame runs their selection in its prologue)
+static int serial_fold(const esac_hip_ctx* c, const KArgs& a) {
+    return !c->fold_select ? 0 : refine_folds_select(a) ? 1 : refine_folds_exact_stats(a) ? 2 : 0;
+}
+// Stage k of the serial route (0: sample, 1: score, 2: select, 3: refine); returns the name check_launch reports it under.
+// ESAC_FLAG_EXACT_SCORES: every hypothesis scored in the reference's arithmetic (esac_util.h:235-260), softmax
+// statistics from those scores -- the score vector, probability and entropy are then the reference's own values
+static inline const char* enqueue_serial_stage(esac_hip_ctx* c, const KArgs& a, int k, hipStream_t s) {
+    const bool exact = (a.flags & ESAC_FLAG_EXACT_SCORES) != 0;
+    switch (k) {
+        case 0: launch_sample(a, s); return "k_sample";
+        case 1: if (exact) launch_rescore_all(a, s); else launch_score(a, s); return exact ? "k_rescore(all)" : "k_score_fast";
+        case 2: if (exact) { if (a.fold_select != 2) launch_stats_exact(a, s); } else if (!a.fold_select) launch_select_rescore(a, s); return exact ? "k_stats_exact" : "k_select_rescore";
+        default: c->refine_tag = launch_refine(a, s); return "k_refine";
     }
+}
+// a team timed out: twice in a row and the context stops asking for teams (every call would pay the time-out first) until re-armed
+static void note_team_timeout(esac_hip_ctx* c) {
+    c->team_fallbacks++;
+    if (++c->team_strikes >= ESAC_TEAM_STRIKES && !c->team_latched_off) {
+        c->team_latched_off = true;
+        c->solo_since_latch = 0;
+    }
+}
+// A forward call up to its first launch (p carries record 0 of a per-frame camera table in its inline fields); *tm: the call is timed
+static int prepare_forward(esac_hip_ctx* c, const float* d_sc, long long sc_frame_stride, const int64_t* d_assign, const esac_hip_params* p,
+                           int B, hipStream_t s, const esac_hip_frame_cam* h_cams, double t_entry, KArgs* out, bool* tm) {
+    KArgs& a = *out;
     int rc = make_args(c, d_sc, d_assign, p, &a, B, sc_frame_stride, h_cams ? 0 : -1);
     if (rc) return rc;
     if (h_cams && B > 1) {  // (one frame: record 0 is the whole table)
-        if ((rc = stage_cams(c, p, h_cams, B, (hipStream_t)stream))) return rc;
+        if ((rc = stage_cams(c, p, h_cams, B, s))) return rc;
         a.cams = c->d_cams;
     }
     if (c->team_latched_off && ++c->solo_since_latch > ESAC_TEAM_REARM_CALLS) {  // (blocking or not: every forward call counts)
@@ -733,150 +753,186 @@ static int forward_impl(esac_hip_ctx* c, const float* d_sc, long long sc_frame_s
     forward_team(c, a);
     c->host_ns[6] = t_entry;
     c->host_ns[0] = now_ns() - t_entry;
-    hipStream_t s = (hipStream_t)stream;
-    a.scores_user = d_scores_out;
-    a.result_user = d_result_out;
-    a.result_pin = h_result_out ? c->d_pin : nullptr;
-    // ESAC_FLAG_AUTO_EXACT: the guaranteed routes where they are free (include/esac_hip.h)
-    if ((a.flags & ESAC_FLAG_AUTO_EXACT) && B == 1 && a.E == 1 && (long long)a.N * a.H * a.W <= ESAC_AUTO_EXACT_MAX_WORK)
-        a.flags |= ESAC_FLAG_EXACT_SCORES | ESAC_FLAG_EXACT_SAMPLING;
+    apply_auto_exact(a, B);
     // events and stamps cost GPU time themselves (an empty event pair reads ~5 us): sample every timing_period-th call
-    const bool tm = c->timing && (c->timing_calls++ % c->timing_period) == 0;
-    const bool exact = (a.flags & ESAC_FLAG_EXACT_SCORES) != 0;
+    *tm = c->timing && (c->timing_calls++ % c->timing_period) == 0;
     // device-side span stamps: only the per-hypothesis stream (k_score_fast) writes them, and k_select_rescore reduces them --
     // a call whose selection runs in the refinement kernel's prologue keeps ITS launch sequence under timing (the phase
     // events then bracket what an untimed call runs) and takes no stamps
-    if (!tm || a.partials || exact) a.tstamps = nullptr;
+    if (!*tm || a.partials || (a.flags & ESAC_FLAG_EXACT_SCORES)) a.tstamps = nullptr;
     if (a.tstamps) {
         KArgs probe = a;
         probe.tstamps = nullptr;
         if (c->fold_select && refine_folds_select(probe)) a.tstamps = nullptr;
     }
-    // Several experts: the sampler's straggler chain (wrong-expert hypotheses, which practically never win) runs BESIDE the scoring,
-    // selection and refinement of what the first pass settled (KArgs::spec_mode; k_spec_join makes the outputs the serial order's)
-    // (not where the selection runs in the refinement kernel's prologue -- a single frame of <= 256 hypotheses on a team: that
-    // route re-scores its contenders member by member, another summation order than k_select_rescore's and k_spec_join's)
-    const bool spec = !c->spec_off && B == 1 && !exact && sample_can_split(a) && !a.partials && (long long)a.H * a.W < 32768 &&
-                      !(c->fold_select && refine_folds_select(a));
+    return 0;
+}
+
+// Several experts: the sampler's straggler chain (wrong-expert hypotheses, which practically never win) runs BESIDE the scoring,
+// selection and refinement of what the first pass settled (KArgs::spec_mode; k_spec_join makes the outputs the serial order's)
+// (not where the selection runs in the refinement kernel's prologue -- a single frame of <= 256 hypotheses on a team: that
+// route re-scores its contenders member by member, another summation order than k_select_rescore's and k_spec_join's)
+static bool speculation_eligible(const esac_hip_ctx* c, const KArgs& a, int B, hipStream_t s) {
+    if (c->spec_off || B != 1 || (a.flags & ESAC_FLAG_EXACT_SCORES) || !sample_can_split(a) || a.partials || (long long)a.H * a.W >= 32768 ||
+        (c->fold_select && refine_folds_select(a)))
+        return false;
+    if (s == nullptr) return true;
+    // a stream that is being captured into a graph takes no launches on other streams beside it
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool plain = hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
+    (void)hipGetLastError();
+    return plain;
+}
+static int ensure_spec_streams(esac_hip_ctx* c) {
+    if (!c->side) HIP_OK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
+    if (!c->side2) HIP_OK(hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking));
+    if (!c->spec_ev) HIP_OK(hipEventCreateWithFlags(&c->spec_ev, hipEventDisableTiming));
+    return 0;
+}
+static int enqueue_speculative(esac_hip_ctx* c, KArgs& a, hipStream_t s, bool tm, double t_entry) {
+    c->spec_calls++;
+    c->last_spec_epoch = a.epoch;
+    a.tstamps = nullptr;
+    a.fold_select = 0;
+    a.spec_flag = c->ws.spec_flag;
+    KArgs chain;
+    int chain_waves = 0;
+    // The caller's stream may hold any amount of work ahead of this call (the expert networks that produce d_sc), and the
+    // context's own streams are ordered against it by nothing else: they wait for THIS event before anything of this call
+    // runs on them, so that their bounded waits for the hand-off words below start counting when the caller's stream has
+    // reached the call -- not when the host enqueued it.  (Recorded here, in front of the first pass: on an idle stream it
+    // is satisfied long before the two streams get their first launch, and their wait for it sits beside the first pass and
+    // the score kernel, off the critical path.)
+    HIP_OK(hipEventRecord(c->spec_ev, s));
+    launch_sample_split(a, s, &chain, &chain_waves);
+    if (int rc = check_launch("k_sample (first pass)")) return rc;
+    c->host_ns[1] = now_ns() - t_entry;
+    if (tm) HIP_OK(hipEventRecord(c->ev[1], s));
+    // WITHIN the call the streams hand over through WORDS in device memory (spec_state[3]: "the chain may start", [4]: "the
+    // chain is done"), not through events: an event between two streams costs the waiting side 8-13 us on this platform even
+    // when it is long satisfied (profiles/r06_ab_speculation.txt).  Whoever waits is enqueued BEHIND the launch it waits for
+    // (host order below), so that even two streams that share a hardware queue cannot wait for each other; every wait is
+    // bounded in wall time -- and begins behind spec_ev, i.e. when the caller's stream has reached this call.
+    KArgs as = a;  // the settled hypotheses: score, selection, refinement of their winner -- no record leaves the workspace
+    as.spec_mode = 1;
+    as.result_user = nullptr;
+    as.result_pin = nullptr;
+    launch_score(as, s);
+    if (int rc = check_launch("k_score_fast (settled)")) return rc;
+    c->host_ns[2] = now_ns() - t_entry;
+    if (tm) HIP_OK(hipEventRecord(c->ev[2], s));
+    // The chain starts when the speculative refinement has its CUs, not when the first pass is done: its thousands of
+    // single-wavefront workgroups fill every SIMD of the chip, and whatever the launch stream starts while it is in full
+    // swing finds no CU to run on until it has drained (measured: started behind the first pass, the selection took 27 us
+    // instead of 10; started behind the score kernel, the refinement's team waited 34 us for its CUs).
+    // The SELECTION among the settled hypotheses is not on the critical path either (round 6, second half).  The refinement starts
+    // from the fp32 argmax of the settled hypotheses (spec_mode 2: spec_pick_fast) right behind the score kernel; the selection
+    // kernel (band, exact re-scores) and the join behind it run on a second stream of the context's own, the join resident and
+    // waiting when the refinement and the chain finish ("the refinement is done": spec_state[6]); the gated second refinement
+    // on the caller's stream waits for the join's verdict ("the join is done": spec_state[7]).  Every waiter is enqueued
+    // behind what it waits for.  (With selection and join on the caller's stream, in front of and behind the refinement:
+    // cfg3 0.1404 ms against 0.1288, cfg4 0.1915 against 0.184, same box -- profiles/r06_ab_select_beside.txt.)
+    if (tm) HIP_OK(hipEventRecord(c->ev[3], s));
+    KArgs ar = as;
+    ar.spec_mode = 2;
+    ar.spec_debug = c->spec_second_best ? 1 : 0;
+    c->refine_tag = launch_refine(ar, s);  // (its first workgroup opens the chain: spec_open_chain)
+    c->refine_was_team = refine_team_members(ar) > 0;
+    if (int rc = check_launch("k_refine (speculative)")) return rc;
+    // (host order: the selection first -- the join waits behind it; a launch call is 3-4 us of host time, and the chain's five
+    // in front of it would hold the selection back by 20 us.  The JOIN is enqueued behind the chain it waits for.)
+    HIP_OK(hipStreamWaitEvent(c->side2, c->spec_ev, 0));
+    launch_spec_wait(a, 3, c->side2);
+    launch_select_rescore(as, c->side2);
+    if (int rc = check_launch("k_select_rescore (settled)")) return rc;
+    HIP_OK(hipStreamWaitEvent(c->side, c->spec_ev, 0));
+    launch_spec_wait(a, 3, c->side);
+    launch_sample_stragglers(chain, chain_waves, c->side);
+    if (!c->spec_lose_chain) launch_score_stragglers(a, c->side);  // behind the chain on the side stream; its last workgroup writes "the chain is done"
+    if (int rc = check_launch("straggler chain")) return rc;
+    launch_spec_join(a, c->side2);
+    if (int rc = check_launch("k_spec_join")) return rc;
+    // The second refinement is enqueued NOW and returns at once unless the join marked the speculation as failed
+    // (KArgs::spec_gate): a failed speculation then costs the refinement, not a host round trip on top of it (and an
+    // asynchronous call could not look at the join's verdict anyway); a speculation that held has delivered its record
+    // before the gate opens
+    KArgs ag = a;
+    ag.spec_gate = 1;
+    (void)launch_refine(ag, s);  // (esac_hip_check follows the speculative launch's tag: a team time-out there is the common case of the two)
+    if (int rc = check_launch("k_refine (gated)")) return rc;
+    c->host_ns[3] = now_ns() - t_entry;
+    return 0;
+}
+// Blocking call, after its record has landed.  The members of a team did not all become resident in time (a shared or partitioned
+// GPU, or the caller's own kernels on another stream holding the CUs): the same refinement(s) in ONE workgroup each -- the
+// hypotheses, scores and selection of this call are still in the workspace.  Then the slots to the caller's records, and the
+// status words as error codes.
+static int collect_records(esac_hip_ctx* c, KArgs& a, int B, hipStream_t s, double* h_result_out) {
+    bool team_failed = false, bad_assign = false, timed_out = false;
+    for (int b = 0; b < B; b++) team_failed |= pin_status(c, b) == ESAC_PIN_TEAM_TIMEOUT;
+    const bool was_team = refine_team_members(a) > 0;
+    if (team_failed && was_team) {
+        note_team_timeout(c);
+        a.epoch = c->epoch += 1.0;
+        a.team = 0; a.solo = 1;
+        if (a.fold_select) {  // the selection was that kernel's too
+            a.fold_select = 0;
+            enqueue_serial_stage(c, a, 2, s);
+        }
+        enqueue_serial_stage(c, a, 3, s);
+        if (int rc = check_launch("k_refine (one workgroup, after a team time-out)")) return rc;
+        if (int rc = wait_record(c, s, B, c->epoch, "esac_hip_forward: the refinement kernel")) return rc;
+    } else if (was_team) {
+        c->team_strikes = 0;
+    }
+    __sync_synchronize();
+    for (int b = 0; b < B; b++) {
+        memcpy(h_result_out + (size_t)b * ESAC_RES_DOUBLES, (const void*)(c->h_pin + (size_t)b * ESAC_PIN_DOUBLES),
+               ESAC_RES_DOUBLES * sizeof(double));
+        bad_assign |= pin_status(c, b) == ESAC_PIN_BAD_ASSIGN;
+        timed_out |= pin_status(c, b) == ESAC_PIN_TEAM_TIMEOUT;
+    }
+    if (timed_out) return fail(-12, "esac_hip_forward: the cooperating refinement workgroups could not synchronise (not all of them became resident)");
+    if (bad_assign)
+        return fail(-10, "hypAssignment holds a value outside [0,%d) (device-resident tensor; such hypotheses were scored against expert 0)", a.E);
+    return 0;
+}
+
+static int forward_impl(esac_hip_ctx* c, const float* d_sc, long long sc_frame_stride, const int64_t* d_assign,
+                        const esac_hip_params* p, int B, void* stream, double* d_scores_out, double* d_result_out,
+                        double* h_result_out, const esac_hip_frame_cam* h_cams = nullptr) {
+    if (!c) return fail(-1, "null context");
+    const double t_entry = now_ns();
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    esac_hip_params p0;
+    if (h_cams && p) {  // the inline fields carry record 0 (device_common.hpp:frame_view)
+        p0 = with_cam(*p, h_cams[0]);
+        p = &p0;
+    }
+    KArgs a;
+    bool tm = false;
+    int rc = prepare_forward(c, d_sc, sc_frame_stride, d_assign, p, B, s, h_cams, t_entry, &a, &tm);
+    if (rc) return rc;
+    a.scores_user = d_scores_out; a.result_user = d_result_out;
+    a.result_pin = h_result_out ? c->d_pin : nullptr;
     c->last_spec_epoch = 0;
-    bool spec_ok = spec;
-    if (spec_ok && s != nullptr) {  // a stream that is being captured into a graph takes no launches on other streams beside it
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) spec_ok = false;
-        (void)hipGetLastError();
-    }
-    if (spec_ok && !c->side) {
-        HIP_OK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-    }
-    if (spec_ok && !c->side2) {
-        HIP_OK(hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking));
-    }
-    if (spec_ok && !c->spec_ev) {
-        HIP_OK(hipEventCreateWithFlags(&c->spec_ev, hipEventDisableTiming));
-    }
+    const bool spec = speculation_eligible(c, a, B, s);
+    if (spec && (rc = ensure_spec_streams(c))) return rc;
     if (tm) HIP_OK(hipEventRecord(c->ev[0], s));
-    c->rt32_stale = false;
     mark_sampling(c, a);
-    if (spec_ok) {
-        c->spec_calls++;
-        c->last_spec_epoch = a.epoch;
-        a.tstamps = nullptr;
-        a.fold_select = 0;
-        a.spec_flag = c->ws.spec_flag;
-        KArgs chain;
-        int chain_waves = 0;
-        // The caller's stream may hold any amount of work ahead of this call (the expert networks that produce d_sc), and the
-        // context's own streams are ordered against it by nothing else: they wait for THIS event before anything of this call
-        // runs on them, so that their bounded waits for the hand-off words below start counting when the caller's stream has
-        // reached the call -- not when the host enqueued it.  (Recorded here, in front of the first pass: on an idle stream it
-        // is satisfied long before the two streams get their first launch, and their wait for it sits beside the first pass and
-        // the score kernel, off the critical path.)
-        HIP_OK(hipEventRecord(c->spec_ev, s));
-        launch_sample_split(a, s, &chain, &chain_waves);
-        if ((rc = check_launch("k_sample (first pass)"))) return rc;
-        c->host_ns[1] = now_ns() - t_entry;
-        if (tm) HIP_OK(hipEventRecord(c->ev[1], s));
-        // WITHIN the call the streams hand over through WORDS in device memory (spec_state[3]: "the chain may start", [4]: "the
-        // chain is done"), not through events: an event between two streams costs the waiting side 8-13 us on this platform even
-        // when it is long satisfied (profiles/r06_ab_speculation.txt).  Whoever waits is enqueued BEHIND the launch it waits for
-        // (host order below), so that even two streams that share a hardware queue cannot wait for each other; every wait is
-        // bounded in wall time -- and begins behind spec_ev, i.e. when the caller's stream has reached this call.
-        KArgs as = a;  // the settled hypotheses: score, selection, refinement of their winner -- no record leaves the workspace
-        as.spec_mode = 1;
-        as.result_user = nullptr;
-        as.result_pin = nullptr;
-        launch_score(as, s);
-        if ((rc = check_launch("k_score_fast (settled)"))) return rc;
-        c->host_ns[2] = now_ns() - t_entry;
-        if (tm) HIP_OK(hipEventRecord(c->ev[2], s));
-        // The chain starts when the speculative refinement has its CUs, not when the first pass is done: its thousands of
-        // single-wavefront workgroups fill every SIMD of the chip, and whatever the launch stream starts while it is in full
-        // swing finds no CU to run on until it has drained (measured: started behind the first pass, the selection took 27 us
-        // instead of 10; started behind the score kernel, the refinement's team waited 34 us for its CUs).
-        // The SELECTION among the settled hypotheses is not on the critical path either (round 6, second half).  The refinement starts
-        // from the fp32 argmax of the settled hypotheses (spec_mode 2: spec_pick_fast) right behind the score kernel; the selection
-        // kernel (band, exact re-scores) and the join behind it run on a second stream of the context's own, the join resident and
-        // waiting when the refinement and the chain finish ("the refinement is done": spec_state[6]); the gated second refinement
-        // on the caller's stream waits for the join's verdict ("the join is done": spec_state[7]).  Every waiter is enqueued
-        // behind what it waits for.  (With selection and join on the caller's stream, in front of and behind the refinement:
-        // cfg3 0.1404 ms against 0.1288, cfg4 0.1915 against 0.184, same box -- profiles/r06_ab_select_beside.txt.)
-        if (tm) HIP_OK(hipEventRecord(c->ev[3], s));
-        KArgs ar = as;
-        ar.spec_mode = 2;
-        ar.spec_debug = c->spec_second_best ? 1 : 0;
-        c->refine_tag = launch_refine(ar, s);  // (its first workgroup opens the chain: spec_open_chain)
-        c->refine_was_team = refine_team_members(ar) > 0;
-        if ((rc = check_launch("k_refine (speculative)"))) return rc;
-        // (host order: the selection first -- the join waits behind it; a launch call is 3-4 us of host time, and the chain's five
-        // in front of it would hold the selection back by 20 us.  The JOIN is enqueued behind the chain it waits for.)
-        HIP_OK(hipStreamWaitEvent(c->side2, c->spec_ev, 0));
-        launch_spec_wait(a, 3, c->side2);
-        launch_select_rescore(as, c->side2);
-        if ((rc = check_launch("k_select_rescore (settled)"))) return rc;
-        HIP_OK(hipStreamWaitEvent(c->side, c->spec_ev, 0));
-        launch_spec_wait(a, 3, c->side);
-        launch_sample_stragglers_on(chain, chain_waves, c->side);
-        if (!c->spec_lose_chain) launch_score_stragglers(a, c->side);  // behind the chain on the side stream; its last workgroup writes "the chain is done"
-        if ((rc = check_launch("straggler chain"))) return rc;
-        launch_spec_join(a, c->side2);
-        if ((rc = check_launch("k_spec_join"))) return rc;
-        {
-            // The second refinement is enqueued NOW and returns at once unless the join marked the speculation as failed
-            // (KArgs::spec_gate): a failed speculation then costs the refinement, not a host round trip on top of it (and an
-            // asynchronous call could not look at the join's verdict anyway); a speculation that held has delivered its record
-            // before the gate opens
-            KArgs ag = a;
-            ag.spec_gate = 1;
-            const unsigned long long tag2 = launch_refine(ag, s);
-            (void)tag2;  // (esac_hip_check follows the speculative launch's tag: a team time-out there is the common case of the two)
-            if ((rc = check_launch("k_refine (gated)"))) return rc;
-        }
-        c->host_ns[3] = now_ns() - t_entry;
+    if (spec) {
+        if ((rc = enqueue_speculative(c, a, s, tm, t_entry))) return rc;
     } else {
-        launch_sample(a, s);
-        if ((rc = check_launch("k_sample"))) return rc;
-        c->host_ns[1] = now_ns() - t_entry;
-        if (tm) HIP_OK(hipEventRecord(c->ev[1], s));
-        // ESAC_FLAG_EXACT_SCORES: every hypothesis scored in the reference's arithmetic (esac_util.h:235-260), softmax
-        // statistics from those scores -- the score vector, probability and entropy are then the reference's own values
-        if (exact) launch_rescore_all(a, s);
-        else       launch_score(a, s);
-        if ((rc = check_launch(exact ? "k_rescore(all)" : "k_score_fast"))) return rc;
-        c->host_ns[2] = now_ns() - t_entry;
-        if (tm) HIP_OK(hipEventRecord(c->ev[2], s));
-        // a single frame of <= 256 hypotheses that a team refines: the selection runs in that kernel's prologue
-        a.fold_select = !c->fold_select ? 0 : refine_folds_select(a) ? 1 : refine_folds_exact_stats(a) ? 2 : 0;
-        if (exact) {
-            if (a.fold_select != 2) launch_stats_exact(a, s);
-        } else if (!a.fold_select) {
-            launch_select_rescore(a, s);
+        constexpr int stamp[4] = {1, 2, 0, 3};  // the host_ns slot stamped behind stage k (the selection has none)
+        for (int k = 0; k < 4; k++) {
+            if (k == 2) a.fold_select = serial_fold(c, a);
+            const char* what = enqueue_serial_stage(c, a, k, s);
+            if (k == 3) c->refine_was_team = refine_team_members(a) > 0;
+            if ((rc = check_launch(what))) return rc;
+            if (stamp[k]) c->host_ns[stamp[k]] = now_ns() - t_entry;
+            if (tm && k < 3) HIP_OK(hipEventRecord(c->ev[k + 1], s));
         }
-        if ((rc = check_launch(exact ? "k_stats_exact" : "k_select_rescore"))) return rc;
-        if (tm) HIP_OK(hipEventRecord(c->ev[3], s));
-        c->refine_tag = launch_refine(a, s);
-        c->refine_was_team = refine_team_members(a) > 0;
-        if ((rc = check_launch("k_refine"))) return rc;
-        c->host_ns[3] = now_ns() - t_entry;
     }
     if (tm) {
         HIP_OK(hipEventRecord(c->ev[4], s));
@@ -887,10 +943,8 @@ static int forward_impl(esac_hip_ctx* c, const float* d_sc, long long sc_frame_s
         c->ev_valid = true;
     }
     if (h_result_out) {
-        // the refinement kernel stores the record and then the epoch word into pinned host memory
-        // (one ESAC_PIN_DOUBLES slot per frame: record, epoch word, status word)
         if ((rc = wait_record(c, s, B, c->epoch, "esac_hip_forward: the refinement kernel"))) return rc;
-        if (spec_ok && c->h_pin[33] == 5.0) {
+        if (spec && pin_status(c, 0) == ESAC_PIN_NO_CHAIN) {
             // the context's own stream never reported the straggler chain as done within 20 ms (it shares a hardware queue with
             // the caller's stream and something else is holding that queue, or its launch failed): no more speculation on this
             // context, and this call again -- the serial route
@@ -898,49 +952,11 @@ static int forward_impl(esac_hip_ctx* c, const float* d_sc, long long sc_frame_s
             HIP_OK(hipStreamSynchronize(c->side));
             if (c->side2) HIP_OK(hipStreamSynchronize(c->side2));
             HIP_OK(hipStreamSynchronize(s));
+            // (p, no h_cams: a speculative call is ONE frame, whose camera table is record 0 -- in p's inline fields already, and checked)
             return forward_impl(c, d_sc, sc_frame_stride, d_assign, p, B, stream, d_scores_out, d_result_out, h_result_out);
         }
         c->host_ns[4] = now_ns() - t_entry;
-        bool team_failed = false;
-        for (int b = 0; b < B; b++) team_failed |= c->h_pin[(size_t)b * ESAC_PIN_DOUBLES + 33] == 3.0;
-        const bool was_team = refine_team_members(a) > 0;
-        if (team_failed && was_team) {
-            // the members of a team did not all become resident in time (a shared or partitioned GPU, or the caller's own
-            // kernels on another stream holding the CUs): the same refinement(s) in ONE workgroup each -- the hypotheses, scores
-            // and selection of this call are still in the workspace.  Twice in a row and the context stops asking for teams
-            // (every call would pay the time-out first) until it is re-armed.
-            c->team_fallbacks++;
-            if (++c->team_strikes >= ESAC_TEAM_STRIKES && !c->team_latched_off) {
-                c->team_latched_off = true;
-                c->solo_since_latch = 0;
-            }
-            c->epoch += 1.0;
-            a.epoch = c->epoch;
-            a.team = 0;
-            a.solo = 1;
-            if (a.fold_select) {  // the selection was that kernel's too
-                if (a.fold_select == 2) launch_stats_exact(a, s);
-                else                    launch_select_rescore(a, s);
-                a.fold_select = 0;
-            }
-            c->refine_tag = launch_refine(a, s);
-            if ((rc = check_launch("k_refine (one workgroup, after a team time-out)"))) return rc;
-            if ((rc = wait_record(c, s, B, c->epoch, "esac_hip_forward: the refinement kernel"))) return rc;
-        } else if (was_team) {
-            c->team_strikes = 0;
-        }
-        __sync_synchronize();
-        bool bad_assign = false;
-        for (int b = 0; b < B; b++) {
-            memcpy(h_result_out + (size_t)b * ESAC_RES_DOUBLES, (const void*)(c->h_pin + (size_t)b * ESAC_PIN_DOUBLES),
-                   ESAC_RES_DOUBLES * sizeof(double));
-            bad_assign |= c->h_pin[(size_t)b * ESAC_PIN_DOUBLES + 33] == 1.0;
-        }
-        for (int b = 0; b < B; b++)
-            if (c->h_pin[(size_t)b * ESAC_PIN_DOUBLES + 33] == 3.0)
-                return fail(-12, "esac_hip_forward: the cooperating refinement workgroups could not synchronise (not all of them became resident)");
-        if (bad_assign)
-            return fail(-10, "hypAssignment holds a value outside [0,%d) (device-resident tensor; such hypotheses were scored against expert 0)", p->E);
+        if ((rc = collect_records(c, a, B, s, h_result_out))) return rc;
     }
     c->host_ns[5] = now_ns() - t_entry;
     if (h_result_out) {  // running sums (seven additions: the caller's timed loop is not touched by reading them later)
@@ -985,29 +1001,18 @@ extern "C" int esac_hip_time_stages(esac_hip_ctx* c, const float* d_sc, const in
     a.tstamps = nullptr;
     forward_team(c, a);
     hipStream_t s = (hipStream_t)stream;
-    c->rt32_stale = false;
     mark_sampling(c, a);
-    if ((a.flags & ESAC_FLAG_AUTO_EXACT) && a.E == 1 && (long long)a.N * a.H * a.W <= ESAC_AUTO_EXACT_MAX_WORK)
-        a.flags |= ESAC_FLAG_EXACT_SCORES | ESAC_FLAG_EXACT_SAMPLING;
-    const bool exact = (a.flags & ESAC_FLAG_EXACT_SCORES) != 0;
-    // as esac_hip_forward would run it: stage 2 is then part of stage 3 (reads 0)
-    a.fold_select = !c->fold_select ? 0 : refine_folds_select(a) ? 1 : refine_folds_exact_stats(a) ? 2 : 0;
-    auto stage = [&](int k) {
-        switch (k) {
-            case 0: launch_sample(a, s); break;
-            case 1: if (exact) launch_rescore_all(a, s); else launch_score(a, s); break;
-            case 2: if (exact) { if (a.fold_select != 2) launch_stats_exact(a, s); } else if (!a.fold_select) launch_select_rescore(a, s); break;
-            default: c->refine_tag = launch_refine(a, s); break;
-        }
-    };
-    for (int k = 0; k < 4; k++) stage(k);
+    apply_auto_exact(a, 1);
+    // the serial route of esac_hip_forward; where the refinement kernel runs the selection, stage 2 is part of stage 3 (reads 0)
+    a.fold_select = serial_fold(c, a);
+    for (int k = 0; k < 4; k++) enqueue_serial_stage(c, a, k, s);
     if ((rc = check_launch("forward chain"))) return rc;
     hipEvent_t ev[8];
     for (auto& e : ev) HIP_OK(hipEventCreate(&e));
     for (int k = 0; k < 4; k++) {
-        stage(k);  // one untimed launch: the timed ones then start from the same (warm) state
+        enqueue_serial_stage(c, a, k, s);  // one untimed launch: the timed ones then start from the same (warm) state
         HIP_OK(hipEventRecord(ev[2 * k], s));
-        for (int r = 0; r < reps; r++) stage(k);
+        for (int r = 0; r < reps; r++) enqueue_serial_stage(c, a, k, s);
         HIP_OK(hipEventRecord(ev[2 * k + 1], s));
     }
     if ((rc = check_launch("stage timing"))) return rc;
@@ -1050,10 +1055,10 @@ extern "C" int esac_hip_pick_record(esac_hip_ctx* c, const double* d_records, in
     }
     __sync_synchronize();
     memcpy(h_record_out, (const void*)c->h_pin, ESAC_RES_DOUBLES * sizeof(double));
-    if (c->h_pin[33] == 3.0)
+    if (pin_status(c, 0) == ESAC_PIN_TEAM_TIMEOUT)
         return fail(-12, "esac_hip_pick_record: the refinement team of at least one rank timed out (its record carries ESAC_RES_VALID = 3); "
                          "every rank sees the same records: run the frame again with ESAC_FLAG_REFINE_SOLO");
-    if (c->h_pin[33] == 2.0) return fail(-11, "esac_hip_pick_record: no rank produced a hypothesis");
+    if (pin_status(c, 0) == ESAC_PIN_NONE) return fail(-11, "esac_hip_pick_record: no rank produced a hypothesis");
     return 0;
 }
 
@@ -1228,7 +1233,6 @@ static int check_batch_call(const char* who, const esac_hip_ctx* c, const esac_h
 // single call sums it)
 static int enqueue_bwd_sampling(esac_hip_ctx* c, KArgs& a, hipStream_t s, bool per_frame_shape) {
     a.tstamps = nullptr;
-    c->rt32_stale = false;
     mark_sampling(c, a);
     launch_sample(a, s);                                        // esac.cpp:276; frame b of a batch: call p->call + b
     if (int rc = check_launch("k_sample")) return rc;
@@ -1538,11 +1542,7 @@ extern "C" int esac_hip_check(esac_hip_ctx* c) {
         // frame the 1 ms wait
         if (c->refine_was_team && c->checked_tag != c->refine_tag) {
             c->checked_tag = c->refine_tag;
-            c->team_fallbacks++;
-            if (++c->team_strikes >= ESAC_TEAM_STRIKES && !c->team_latched_off) {
-                c->team_latched_off = true;
-                c->solo_since_latch = 0;
-            }
+            note_team_timeout(c);
         }
         return fail(-12, "the cooperating refinement workgroups of the most recent call could not synchronise (not all of them became resident)");
     }

@@ -173,8 +173,6 @@ __device__ __forceinline__ void mark_pending(const KArgs& a, int h, int e, bool 
     a.samp_pending[base + __popcll(m & ((1ull << lane) - 1ull))] = (int)blockIdx.y * a.N + h;
     if (expert_stats_on(a)) atomicAdd(expert_stats(a, e) + 1, 1);
 }
-constexpr int FIRST_PHASE_TRIES = 32;  // tries per hypothesis before the screened chain takes over
-constexpr int ESAC_FIRST_WIDE_MAX = 8192;  // up to this many hypotheses: one pass, 32 lanes per hypothesis (else two passes of 16)
 
 // Throughput shape, first phase: a hypothesis on a usable map is accepted within its first few tries, so a whole
 // wavefront per hypothesis solves ~60 P3P problems nobody needs.  Here a wavefront serves SEVERAL hypotheses, TRIES tries
@@ -286,7 +284,6 @@ __global__ __launch_bounds__(1024) void k_pending_list(KArgs a) {
 // wide: a lone maybe would otherwise cost the whole wavefront a full fp64 solve.  The queue is flushed when it holds
 // SCREEN_FLUSH tries, when the screen itself sees a 4th point within tau (almost certainly the accepted try), and at
 // the end of the budget.
-constexpr int ESAC_CHAIN_WAVES = 8192;  // wavefronts of the screened search that work whatever the number of pending hypotheses is
 constexpr int ESAC_RESIDENT_WAVES = 2048;  // k_sample_prescreen: 256 CUs x 4 SIMDs x 2
 constexpr float SCREEN_MARGIN = 3.0f;  // pixels; the largest screen error of an fp64-accepted try in calibration: tau + 0.008
 constexpr int SCREEN_FLUSH = 8;
@@ -1585,7 +1582,7 @@ void launch_stats_exact(const KArgs& a, hipStream_t s) {
 }
 // the chain that finishes hypotheses left SAMPLE_PENDING at try b.first_try (see k_sample_prescreen); `waves` wavefronts
 // in all work through the list of pending hypotheses
-static void launch_sample_stragglers(const KArgs& b, int waves, hipStream_t s) {
+void launch_sample_stragglers(const KArgs& b, int waves, hipStream_t s) {
     const int gx = b.N < waves ? b.N : waves;  // (the shape only spreads the linear wavefront index over three dimensions)
     const int gz = (waves + gx * b.frames - 1) / (gx * b.frames);
     hipLaunchKernelGGL(k_sample_prescreen, dim3(gx, b.frames, gz < 1 ? 1 : gz), dim3(64), 0, s, b);
@@ -1594,124 +1591,48 @@ static void launch_sample_stragglers(const KArgs& b, int waves, hipStream_t s) {
     hipLaunchKernelGGL(k_sample_screened<true>, dim3(b.N, b.frames), dim3(64), 0, s, b);
 }
 
+// The sampler's launches are decided in ONE place (sample_plan.hpp, with the measurements behind every shape); what follows only
+// enqueues a plan.
+static SamplePlan plan_of(const KArgs& a) { return sample_plan(a.N, a.frames, a.E, a.max_tries, a.flags, a.first_try, a.sc4 != nullptr); }
+bool sample_can_split(const KArgs& a) { return plan_of(a).splittable; }
+// k_pack_cells, the plan's first pass and k_pending_list on `s`; returns the arguments of the tail
+static KArgs launch_sample_first(const SamplePlan& p, const KArgs& a, hipStream_t s) {
+    if (p.pack) hipLaunchKernelGGL(k_pack_cells, dim3(2048), dim3(256), 0, s, a);
+    KArgs b = a;
+    b.handover = p.handover;
+    const dim3 grid(p.grid_x, a.frames), block(p.block);
+    const bool strict = p.strict;
+    for (int pass = 0; pass < p.passes; pass++, b.first_try += p.pass_tries) {
+        switch (p.first) {
+            case SAMPLE_256x2:   hipLaunchKernelGGL((strict ? k_sample_strict<256, 2> : k_sample<256, 2>), grid, block, 0, s, b); break;
+            case SAMPLE_128x4:   hipLaunchKernelGGL((strict ? k_sample_strict<128, 4> : k_sample<128, 4>), grid, block, 0, s, b); break;
+            case SAMPLE_64x2:    hipLaunchKernelGGL((k_sample<64, 2>), grid, block, 0, s, b); break;  // (a hand-over shape: never strict)
+            case SAMPLE_128x1:   hipLaunchKernelGGL((strict ? k_sample_strict<128, 1> : k_sample<128, 1>), grid, block, 0, s, b); break;
+            case SAMPLE_FIRST32: hipLaunchKernelGGL((strict ? k_sample_first_strict<32> : k_sample_first<32>), grid, block, 0, s, b); break;
+            case SAMPLE_FIRST16: hipLaunchKernelGGL((strict ? k_sample_first_strict<16> : k_sample_first<16>), grid, block, 0, s, b); break;
+            case SAMPLE_FIRST_NONE: break;
+        }
+    }
+    b.first_try = p.tail_first_try;
+    if (p.pending_list) hipLaunchKernelGGL(k_pending_list, dim3((a.N + 1023) / 1024, a.frames), dim3(1024), 0, s, b);
+    return b;
+}
 void launch_sample(const KArgs& a, hipStream_t s) {
-    const long long total = (long long)a.N * a.frames;
-    if (a.sc4) hipLaunchKernelGGL(k_pack_cells, dim3(2048), dim3(256), 0, s, a);
-    // entries of the "maybe" list, hypotheses of the pending list (+ the per-expert counters behind them, see expert_stats)
-    // are zero between calls: the last kernel of the screened chain clears them (k_sample_screened<true>).  A fill in front
-    // of every sampling launch cost the headline call, which never appends to them, 5 us (0.2058 -> 0.2010 ms).
-    KArgs b = a;
-    b.handover = 0x7fffffff;
-    // Few hypotheses in flight: latency.  A workgroup per hypothesis (the candidates of a try on two or four lanes at first)
-    // settles a hypothesis of the right expert within its first round; with several experts the stragglers are handed to
-    // the spread, screened search after `handover` tries (every wavefront of that launch works, rounds handed out in order).  Beyond ~10^3
-    // hypotheses (several experts) a workgroup per hypothesis no longer fits the chip in one wave of workgroups: the
-    // first 32 tries run four hypotheses per wavefront and the screened chain finishes the rest.
-    // ESAC_FLAG_EXACT_SAMPLING: no screen anywhere -- every try is solved and decided by the fp64 route (k_sample walks a
-    // straggler's whole budget itself, one try per lane; the throughput shape finishes with k_sample<64> instead of the
-    // screened chain)
-    // ESAC_FLAG_STRICT_REFERENCE (implies the exact route): the same launches, the kernels with the reference's alignment
-    const bool strict = (a.flags & ESAC_FLAG_STRICT_REFERENCE_K) != 0;
-    const bool exact = strict || (a.flags & ESAC_FLAG_EXACT_SAMPLING_K) != 0;
-    const bool handover = a.E > 1 && a.max_tries > 1024 && !exact;
-constexpr int ESAC_LATENCY_MAX = 1024;
-constexpr int ESAC_HANDOVER = 32;  // (64: k_sample<128> 41 us + screened search 29 us at config 3; 32: 30 + 31 us)
-    // wavefronts of the screened chain: every one of them works whatever the number of pending hypotheses is (they take the
-    // 64-try rounds of the hypotheses on the list in order), so the launch is sized for the chip -- 2048 wavefronts are
-    // resident at two per SIMD -- with some slack for the tail; when (nearly) every hypothesis is pending, as in the
-    // 50-expert workloads, eight per hypothesis measured best (A/B on one box, config 5a: 4 / 8 / 32 per hypothesis ->
-    // 2.00 / 1.95 / 2.18 ms)
-constexpr int ESAC_CHAIN_PER_HYP = 8;
-    const long long w8 = (a.E == 1 ? 1LL : (long long)ESAC_CHAIN_PER_HYP) * total;
-    // (every pending hypothesis needs at least ONE wavefront: wavefront L serves list entry L % count, so a launch smaller
-    // than the list would leave its tail unscreened -- beyond 131072 hypotheses the launch grows with them)
-    const long long wcap = total > 131072 ? total : 131072;
-    const int waves = (int)(w8 < ESAC_CHAIN_WAVES ? ESAC_CHAIN_WAVES : (w8 > wcap ? wcap : w8));
-    if (total <= (handover ? ESAC_LATENCY_MAX : 1024)) {
-        if (handover) b.handover = ESAC_HANDOVER;
-        // up to 256 hypotheses: four wavefronts each, two lanes per try (128 tries per round, one workgroup per CU at this
-        // kernel's ~445 registers: the chip is full).  Beyond that the workgroups queue up behind each other (1024
-        // hypotheses: four ~12 us rounds back to back, 51 us measured): two wavefronts per hypothesis, four lanes per try
-        // (32 tries per round -- 93 % of the hypotheses of a usable map are settled in it) put two hypotheses on a CU at a
-        // time.
-        // 513 .. 1024 hypotheses that hand their stragglers over (round 6): ONE wavefront per hypothesis, two lanes per try -- the
-        // same 32 tries in one round, a chain of two candidates instead of one, and all 1024 wavefronts resident at once instead of
-        // 2048 in two waves of workgroups: 29.9 -> 25.4 us at config 3 (four lanes per try at one wavefront, two rounds of 16
-        // tries: 29.9 again).  Without a hand-over (one expert, ESAC_FLAG_EXACT_SAMPLING) a straggler walks its whole budget in this
-        // kernel, one try per lane: two wavefronts per hypothesis halve that tail (config 3 on the guaranteed routes: 0.56 ms
-        // against 0.89 with one)
-        if (total <= 256)                    hipLaunchKernelGGL((strict ? k_sample_strict<256, 2> : k_sample<256, 2>), dim3(a.N, a.frames), dim3(256), 0, s, b);
-        else if (total <= 512 || !handover)  hipLaunchKernelGGL((strict ? k_sample_strict<128, 4> : k_sample<128, 4>), dim3(a.N, a.frames), dim3(128), 0, s, b);
-        else                                 hipLaunchKernelGGL((k_sample<64, 2>), dim3(a.N, a.frames), dim3(64), 0, s, b);
-    } else if (total <= 4096 && !handover) {
-        hipLaunchKernelGGL((strict ? k_sample_strict<128, 1> : k_sample<128, 1>), dim3(a.N, a.frames), dim3(128), 0, s, b);
-    } else {  // throughput: passes of 16 tries with four hypotheses per wavefront, then the unaccepted rest by the screened chain
-        if (total <= ESAC_FIRST_WIDE_MAX) {
-            hipLaunchKernelGGL((strict ? k_sample_first_strict<32> : k_sample_first<32>), dim3((a.N + 1) / 2, a.frames), dim3(64), 0, s, b);
-            b.first_try += 32;
-        } else if (a.E > 1 && !exact) {
-            // tens of thousands of hypotheses over many experts (config 5: 16384 over 50, Dirichlet gating): nearly all of them
-            // sit on wrong experts, where 32 tries in full fp64 are 32 solves for nothing -- the screened chain takes them
-            // from try 0 (a hypothesis of the right expert costs it one screened round and a handful of fp64 decisions)
-        } else {
-            for (int pass = 0; pass < FIRST_PHASE_TRIES / 16 && b.first_try < a.max_tries; pass++) {
-                hipLaunchKernelGGL((strict ? k_sample_first_strict<16> : k_sample_first<16>), dim3((a.N + 3) / 4, a.frames), dim3(64), 0, s, b);
-                b.first_try += 16;
-            }
-        }
-        if (b.first_try < a.max_tries) {
-            if (exact) {
-                hipLaunchKernelGGL((strict ? k_sample_strict<64, 1> : k_sample<64, 1>), dim3(a.N, a.frames), dim3(64), 0, s, b);  // every try solved in full
-            } else {
-                hipLaunchKernelGGL(k_pending_list, dim3((a.N + 1023) / 1024, a.frames), dim3(1024), 0, s, b);
-                // (the list stays in hypothesis order: expert-major and dealt to the XCDs, the full-resolution workload's
-                // gathers hit L2 at 0.59 instead of 0.07 and fetch 4.8 GB instead of 11.1 GB per call -- and the kernel takes
-                // the same 1.7 ms: it does not wait for them.  profiles/r04_cfg5b_pending_order.txt, LAB_NOTES.md)
-                launch_sample_stragglers(b, waves, s);
-            }
-        }
-        return;
-    }
-    if (handover) {
-        b.first_try = b.handover;
-        launch_sample_stragglers(b, waves, s);
-    }
+    const SamplePlan p = plan_of(a);
+    const KArgs b = launch_sample_first(p, a, s);
+    if (p.tail == SAMPLE_TAIL_EXACT)
+        hipLaunchKernelGGL((p.strict ? k_sample_strict<64, 1> : k_sample<64, 1>), dim3(a.N, a.frames), dim3(64), 0, s, b);  // every try solved in full
+    else if (p.tail == SAMPLE_TAIL_CHAIN)
+        launch_sample_stragglers(b, p.chain_waves, s);
 }
-// ---- speculative forward: the sampler in two parts (see KArgs::spec_mode).  The shapes that have a FIRST PASS which settles
-// most hypotheses and a straggler chain behind it: several experts, a single frame, the screened route, at most
-// ESAC_FIRST_WIDE_MAX hypotheses (beyond that the chain takes every hypothesis from try 0: nothing is settled early).
-constexpr int ESAC_SPLIT_LATENCY_MAX = 1024, ESAC_SPLIT_HANDOVER = 32;  // = launch_sample's ESAC_LATENCY_MAX / ESAC_HANDOVER
-bool sample_can_split(const KArgs& a) {
-    return a.frames == 1 && a.E > 1 && a.max_tries > 1024 && !(a.flags & (ESAC_FLAG_EXACT_SAMPLING_K | ESAC_FLAG_STRICT_REFERENCE_K)) && a.N <= ESAC_FIRST_WIDE_MAX &&
-           a.first_try == 0;
+// speculative forward: the sampler in two parts (see KArgs::spec_mode; requires sample_can_split(a)).  Everything up to the tail
+// on `s`; the tail -- the straggler chain -- is left to the caller, who enqueues it on a stream of its own
+// (launch_sample_stragglers) with the arguments and the wavefront count that come back here.
+void launch_sample_split(const KArgs& a, hipStream_t s, KArgs* chain, int* chain_waves) {
+    const SamplePlan p = plan_of(a);
+    *chain = launch_sample_first(p, a, s);
+    *chain_waves = p.chain_waves;
 }
-// The first pass on `s` -- its last kernel completes `fork` (the kernel's own completion signal: hipExtLaunchKernelGGL; an event
-// recorded behind it costs the launch stream 5 us, scripts/dev/fork_join.hip) -- and the chain on `side` behind that event.
-// Exactly the kernels, arguments and order of launch_sample for these shapes.  Returns 0, or the hipError_t of the event wait.
-// The first pass on `s`; the chain's arguments (where it takes over, how many wavefronts) come back in `chain`.
-// Exactly the kernels, arguments and order of launch_sample for these shapes.
-int launch_sample_split(const KArgs& a, hipStream_t s, KArgs* chain, int* chain_waves) {
-    const long long total = a.N;
-    if (a.sc4) hipLaunchKernelGGL(k_pack_cells, dim3(2048), dim3(256), 0, s, a);
-    KArgs b = a;
-    b.handover = 0x7fffffff;
-    const long long w8 = (long long)8 * total;  // ESAC_CHAIN_PER_HYP (launch_sample)
-    *chain_waves = (int)(w8 < ESAC_CHAIN_WAVES ? ESAC_CHAIN_WAVES : (w8 > 131072 ? 131072 : w8));
-    if (total <= ESAC_SPLIT_LATENCY_MAX) {
-        b.handover = ESAC_SPLIT_HANDOVER;
-        if (total <= 256)      hipLaunchKernelGGL((k_sample<256, 2>), dim3(a.N, 1), dim3(256), 0, s, b);
-        else if (total <= 512) hipLaunchKernelGGL((k_sample<128, 4>), dim3(a.N, 1), dim3(128), 0, s, b);
-        else                   hipLaunchKernelGGL((k_sample<64, 2>), dim3(a.N, 1), dim3(64), 0, s, b);
-        b.first_try = b.handover;
-    } else {
-        hipLaunchKernelGGL(k_sample_first<32>, dim3((a.N + 1) / 2, 1), dim3(64), 0, s, b);
-        b.first_try += 32;
-        hipLaunchKernelGGL(k_pending_list, dim3((a.N + 1023) / 1024, 1), dim3(1024), 0, s, b);
-    }
-    *chain = b;
-    return 0;
-}
-void launch_sample_stragglers_on(const KArgs& chain, int waves, hipStream_t side) { launch_sample_stragglers(chain, waves, side); }
 // the side stream's last kernel (see k_score_stragglers): behind the chain
 void launch_score_stragglers(const KArgs& a, hipStream_t side) {
     KArgs b = a;

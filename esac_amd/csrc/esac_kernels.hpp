@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sample_plan.hpp"
+
 namespace esac {
 
 // mirrors of the ESAC_RES_* layout in include/esac_hip.h (checked by static_assert in esac_capi.hip)
@@ -26,6 +28,12 @@ constexpr int ESAC_TEAM_GRANULES = 2 * ESAC_REFINE_TEAM_MAX_K * 32;  // 16-byte 
 // refinement is ~0.1 ms): 8 ms
 constexpr long ESAC_TEAM_SPIN_LIMIT = 100000, ESAC_TEAM_SPIN_LIMIT_SLOTS = 800000;
 constexpr int ESAC_PIN_DOUBLES = 36;       // pinned host slot per frame: result record [32] + epoch word + status word + check word + pad
+// the status word (word 33 of the slot) as the host reads it
+constexpr int ESAC_PIN_STATUS = 33;
+constexpr double ESAC_PIN_BAD_ASSIGN = 1.0;    // this call's hypAssignment held an out-of-range value
+constexpr double ESAC_PIN_NONE = 2.0;          // esac_hip_pick_record: no rank produced a hypothesis
+constexpr double ESAC_PIN_TEAM_TIMEOUT = 3.0;  // the members of a shared refinement did not all become resident in time
+constexpr double ESAC_PIN_NO_CHAIN = 5.0;      // speculative forward: the straggler chain never reported
 // The pinned record is handed over WITHOUT a system-scope fence: the kernel stores the 34 words and a 35th that is a
 // checksum of them (one store instruction), the host accepts a slot once its epoch word is the call's and the check word
 // fits the other 34 -- whatever order the words arrive in across PCIe, a partly updated slot fails the check and is
@@ -47,8 +55,7 @@ __device__ __forceinline__ void pin_deliver(double* pin, double v) {
 }
 #endif
 constexpr int ESAC_FLAG_EXACT_SCORES_K = 1;  // = ESAC_FLAG_EXACT_SCORES (include/esac_hip.h)
-constexpr int ESAC_FLAG_EXACT_SAMPLING_K = 16, ESAC_FLAG_SCORES_BY_INDEX_K = 32;  // = ESAC_FLAG_* (checked in esac_capi.hip)
-constexpr int ESAC_FLAG_STRICT_REFERENCE_K = 256;  // the reference's rule wherever the default knowingly differs (include/esac_hip.h)
+constexpr int ESAC_FLAG_SCORES_BY_INDEX_K = 32;  // = ESAC_FLAG_* (checked in esac_capi.hip; the sampler's two: sample_plan.hpp)
 constexpr int ESAC_FLAG_STRICT_TRAINING_K = 512;   // the training path's strict mode: the C ABI turns it into the strict bit above + this one
 constexpr int ESAC_SELECT_SPLIT = 16;         // cell ranges (workgroups) per contender in k_select_rescore when H*W >= 32768
 constexpr int ESAC_CAND_DOUBLES = 26;          // record parked with an accepted entry of the "maybe" list: 6 + 9 + 6 + 4 doubles (+1 pad)
@@ -225,13 +232,13 @@ struct KArgs {
     BwdArgs bwd;                // training path only
 };
 
-void launch_sample(const KArgs& a, hipStream_t s);
-// speculative forward: can this call's sampler be split into a first pass and a straggler chain (several experts, a few thousand
-// hypotheses at most, the screened route)?  launch_sample_split: the first pass on `s` (its last kernel signals `fork`), the chain
-// on `side` behind that event
+void launch_sample(const KArgs& a, hipStream_t s);  // every launch of the call's SamplePlan (sample_plan.hpp) on `s`
+// speculative forward: can this call's sampler be split into a first pass and a straggler chain (SamplePlan::splittable: several
+// experts, a few thousand hypotheses at most, the screened route)?  launch_sample_split: the first pass on `s`; the chain's
+// arguments and wavefront count come back, for launch_sample_stragglers on a stream of the caller's choice
 bool sample_can_split(const KArgs& a);
-int launch_sample_split(const KArgs& a, hipStream_t s, KArgs* chain, int* chain_waves);
-void launch_sample_stragglers_on(const KArgs& chain, int waves, hipStream_t side);
+void launch_sample_split(const KArgs& a, hipStream_t s, KArgs* chain, int* chain_waves);
+void launch_sample_stragglers(const KArgs& chain, int waves, hipStream_t s);
 void launch_score_stragglers(const KArgs& a, hipStream_t side);  // fp32 scores of the stragglers + the "chain is done" word
 void launch_spec_join(const KArgs& a, hipStream_t s);
 // hand-offs between the two streams of a speculative call through words in device memory, not events: a one-wavefront kernel that

@@ -5,7 +5,7 @@
 // The including file defines ESAC_K_SAMPLE_FIRST, ESAC_K_SAMPLE (the kernels' names), ESAC_SAMPLE_ALIGN and
 // ESAC_SAMPLE_FIRST_ATTR (attributes of the first-pass kernel); no include guard on purpose.
 
-// Throughput shape, first phase (see esac_kernels.hip: FIRST_PHASE_TRIES)
+// Throughput shape, first phase (see sample_plan.hpp: FIRST_PHASE_TRIES)
 template <int TRIES>
 __global__ __launch_bounds__(64) ESAC_SAMPLE_FIRST_ATTR void ESAC_K_SAMPLE_FIRST(KArgs a) {
     constexpr int HPW = 64 / TRIES;  // hypotheses per wavefront

@@ -68,3 +68,15 @@ def build_filler(force=False):
         hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
         subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-result", FILLER_SRC, "-o", FILLER_LIB])
     return FILLER_LIB
+
+
+PLAN_SRC = os.path.join(HERE, "sample_plan_probe.cpp")
+PLAN_LIB = os.path.join(HERE, "libsample_plan_probe.so")
+
+
+def build_sample_plan_probe(force=False):
+    """Host build of the sampler's launch plan (sample_plan.hpp needs no HIP header: the host compiler alone)."""
+    deps = [PLAN_SRC, os.path.join(CSRC, "sample_plan.hpp")]
+    if force or not os.path.exists(PLAN_LIB) or any(os.path.getmtime(d) > os.path.getmtime(PLAN_LIB) for d in deps):
+        subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fPIC", "-shared", PLAN_SRC, "-o", PLAN_LIB])
+    return PLAN_LIB
