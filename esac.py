@@ -3,3 +3,4 @@ esac.cpp:513-516).  The MI355X-native implementation lives in esac_amd/ (HIP ker
 this shim only re-exports the reference's two entry points (and their batched companions) plus the RNG/diagnostic helpers."""
 from esac_amd.api import (backward, backward_batch, backward_batch_async, forward, forward_batch, get_rng_state, last_result, set_exact_sampling,  # noqa: F401
                           set_exact_scores, set_limits, set_seed, set_strict_reference, set_strict_training)
+from esac_amd.api import eval_batch, forward_batch_async  # noqa: F401  (the batched test loop: device records, on-device pose errors)

@@ -36,6 +36,11 @@ REFINE_TEAM_MAX, REFINE_TEAM_EIGHT, REFINE_TEAM_AUTO = 32, 8, -1
 REFINE_TEAM_DEFAULT = REFINE_TEAM_AUTO  # what a fresh context does: 8 members, or the smallest team <= 16 that lowers the cells per lane
 MAX_REF_STEPS = 100
 BWD_MAX_SLOTS = 1000
+MAX_BATCH = 1024
+RES_VALID = 31  # device records only: 1 a record, 3 the refinement team timed out, 0 none
+# one row of esac_hip_eval_batch (include/esac_hip.h: ESAC_EVAL_*)
+EVAL_ROT_DEG, EVAL_TRANS_CM, EVAL_POSE_OK, EVAL_CLASS_OK, EVAL_QUAT, EVAL_INV_T, EVAL_EXPERT, EVAL_HYP, EVAL_STATUS = 0, 1, 2, 3, 4, 8, 11, 12, 13
+EVAL_DOUBLES = 16
 
 ABI_SYMBOLS = [
     "esac_hip_abi_version", "esac_hip_last_error", "esac_hip_device_count", "esac_hip_create", "esac_hip_destroy",
@@ -48,6 +53,7 @@ ABI_SYMBOLS = [
     "esac_hip_host_turn_mean", "esac_hip_backward_batch",
     "esac_hip_forward_batch_cams", "esac_hip_backward_batch_cams",
     "esac_hip_backward_batch_dev",  # additive: the ABI version stays
+    "esac_hip_eval_batch",  # additive too
 ]
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
@@ -148,6 +154,7 @@ def load_library():
                                                      C.c_float, pp, vp, vp]
         lib.esac_hip_backward_batch_dev.argtypes = [vp, i32, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_float, C.c_float,
                                                     C.c_float, pp, vp, vp]
+        lib.esac_hip_eval_batch.argtypes = [vp, i32, vp, vp, vp, C.c_float, C.c_float, vp, vp]
         lib.esac_hip_read.argtypes = [vp, i32, vp, C.c_size_t]
         lib.esac_hip_write_hyps.argtypes = [vp, vp, i32]
         lib.esac_hip_phase_ms.argtypes = [vp, vp]
@@ -406,6 +413,45 @@ class Engine:
         if rc != 0:
             _check(rc, self.lib)
         self._keep = (sc, ha, out_gradients, gt, out)  # alive until the kernels have run
+        return out
+
+    def _upload(self, host, dtype):
+        """A host array / tensor onto this device through pinned staging, asynchronously on the launch stream (torch's caching
+        host allocator keeps the staging buffer until the copy has run: the caller's array is free when this returns)."""
+        host = host.detach() if isinstance(host, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(host))
+        pin = torch.empty(tuple(host.shape), dtype=dtype, pin_memory=True)
+        pin.copy_(host)
+        with torch.cuda.device(self.device):
+            return pin.to(self.device, non_blocking=True)
+
+    def eval_batch(self, records, gt_poses, gt_experts=None, rot_threshold_deg=5.0, trans_threshold_cm=5.0, out=None):
+        """The test loop's figures of B frames on the device (esac_hip_eval_batch): records = the device float64 [B,32] a forward
+        batch wrote through result_out, gt_poses float32 [B,4,4], gt_experts int64 [B] or None.  One launch on torch's current
+        stream, behind whatever wrote the records; nothing is waited for.  A host gt_poses / gt_experts is uploaded with
+        non_blocking=True on that stream.  Returns the device float64 tensor [B,16] of rows (`out` when given; columns: EVAL_*)."""
+        B = _check_eval_args("esac.eval_batch", records, gt_poses, gt_experts, rot_threshold_deg, trans_threshold_cm)
+        if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == torch.float64
+                                    and tuple(out.shape) == (B, EVAL_DOUBLES)):
+            raise RuntimeError("esac.eval_batch: out must be a dense float64 device tensor [B,%d]" % EVAL_DOUBLES)
+        if records.device != self.device:
+            raise RuntimeError("esac.eval_batch: records live on %s, this engine on %s" % (records.device, self.device))
+        gt = gt_poses if isinstance(gt_poses, torch.Tensor) and gt_poses.is_cuda else \
+            self._upload(gt_poses if isinstance(gt_poses, torch.Tensor) else np.asarray(gt_poses, np.float32), torch.float32)
+        gt = gt.contiguous()
+        ge = None
+        if gt_experts is not None:
+            ge = gt_experts if isinstance(gt_experts, torch.Tensor) and gt_experts.is_cuda else \
+                self._upload(gt_experts if isinstance(gt_experts, torch.Tensor) else np.asarray(gt_experts, np.int64), torch.int64)
+            ge = ge.contiguous()
+        if gt.device != self.device or (ge is not None and ge.device != self.device):
+            raise RuntimeError("esac.eval_batch: records, gtPoses and gtExperts must live on one device")
+        if out is None:
+            out = torch.empty((B, EVAL_DOUBLES), dtype=torch.float64, device=self.device)
+        rc = self.lib.esac_hip_eval_batch(self.ctx, B, records.data_ptr(), gt.data_ptr(), ge.data_ptr() if ge is not None else None,
+                                          float(rot_threshold_deg), float(trans_threshold_cm), self._stream(), out.data_ptr())
+        if rc != 0:
+            _check(rc, self.lib)
+        self._keep_eval = (records, gt, ge, out)  # alive until the kernel has run
         return out
 
     def read_frames(self, which, B):
@@ -999,3 +1045,102 @@ def backward_batch_async(sceneCoordinates, outGradients, hypAssignment, gtPoses,
     rec = eng.backward_batch_async(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLossRot, wLossTrans, lossCut, p, cams=cams)
     _state["last"] = {"backward": rec}
     return rec[:, 0]
+
+
+# ---------------------------------------------------------------- the batched test loop (asynchronous forward + on-device figures)
+def _check_eval_args(who, records, gtPoses, gtExperts, rotThreshold, transThreshold):
+    """Types, dtypes, shapes and batch sizes of an eval_batch call; returns B.  Raises RuntimeError naming the argument; touches
+    no device."""
+    if not isinstance(records, torch.Tensor):
+        raise RuntimeError("%s: records must be a torch.Tensor (the device records of a forward batch)" % who)
+    if records.dtype != torch.float64:
+        raise RuntimeError("%s: expected scalar type torch.float64 for records but found %s" % (who, records.dtype))
+    if records.dim() != 2 or records.size(1) != RES_DOUBLES or records.size(0) < 1:
+        raise RuntimeError("%s: records must be [B,%d], found %s" % (who, RES_DOUBLES, tuple(records.shape)))
+    B = int(records.size(0))
+    if B > MAX_BATCH:
+        raise RuntimeError("%s: records hold %d frames, at most %d per call" % (who, B, MAX_BATCH))
+    if isinstance(gtPoses, torch.Tensor):
+        if gtPoses.dtype != torch.float32:
+            raise RuntimeError("%s: expected scalar type torch.float32 for gtPoses but found %s" % (who, gtPoses.dtype))
+        shape = tuple(gtPoses.shape)
+    else:
+        try:
+            shape = tuple(np.asarray(gtPoses, np.float32).shape)
+        except (TypeError, ValueError):
+            raise RuntimeError("%s: gtPoses must be a tensor or an array of B 4x4 poses" % who)
+    if shape != (B, 4, 4):
+        raise RuntimeError("%s: gtPoses must be [B,4,4] with B = %d (records), found %s" % (who, B, shape))
+    if gtExperts is not None:
+        if isinstance(gtExperts, torch.Tensor):
+            if gtExperts.dtype != torch.int64:
+                raise RuntimeError("%s: expected scalar type torch.int64 for gtExperts but found %s" % (who, gtExperts.dtype))
+            shape = tuple(gtExperts.shape)
+        else:
+            try:
+                arr = np.asarray(gtExperts)
+            except (TypeError, ValueError):
+                raise RuntimeError("%s: gtExperts must be a tensor or a sequence of B integers" % who)
+            if arr.dtype.kind not in "iu":
+                raise RuntimeError("%s: gtExperts must hold integers, found dtype %s" % (who, arr.dtype))
+            shape = tuple(arr.shape)
+        if shape != (B,):
+            raise RuntimeError("%s: gtExperts must be [B] with B = %d (records), found %s" % (who, B, shape))
+    for name, v in (("rotThreshold", rotThreshold), ("transThreshold", transThreshold)):
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            raise RuntimeError("%s: %s must be a number" % (who, name))
+        if not (v >= 0.0 and v != float("inf")):
+            raise RuntimeError("%s: %s must be finite and not negative, found %r" % (who, name, v))
+    # (last: every other argument is judged the same way wherever the tensors live)
+    if not records.is_cuda or not records.is_contiguous():
+        raise RuntimeError("%s: records must be a dense device tensor (what forward_batch_async returns)" % who)
+    return B
+
+
+def eval_batch(records, gtPoses, gtExperts=None, rotThreshold=5.0, transThreshold=5.0):
+    """The numbers the test loop reports (test_esac.py:209-247) for the B frames of a forward batch, computed on the device
+    (esac_hip_eval_batch): records = the device tensor of `forward_batch_async`, gtPoses float32 [B,4,4], gtExperts int64 [B] or
+    None (host values are uploaded asynchronously).  Enqueued on torch's current stream behind the batch; no host synchronisation.
+    Returns a device float64 tensor [B,16]: EVAL_ROT_DEG, EVAL_TRANS_CM, EVAL_POSE_OK (strictly below both thresholds, cm / degrees),
+    EVAL_CLASS_OK (-1 without gtExperts), EVAL_QUAT qw qx qy qz and EVAL_INV_T tx ty tz of the inverted pose (one line of
+    poses_esac_*.txt), EVAL_EXPERT, EVAL_HYP, EVAL_STATUS (0 a record; 3 the frame's refinement team timed out: run it again,
+    harness.rerun_frames; 1 no record)."""
+    _check_eval_args("esac.eval_batch", records, gtPoses, gtExperts, rotThreshold, transThreshold)
+    return engine(records.device.index).eval_batch(records, gtPoses, gtExperts, rotThreshold, transThreshold)
+
+
+def forward_batch_async(sceneCoordinates, hypAssignment, shiftX, shiftY, focalLength, ppointX, ppointY,
+                        inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling):
+    """`forward_batch` without the host inside the call: the launches are enqueued on torch's current stream, the result records
+    stay on the device and nothing is waited for (device inputs; host tensors are uploaded first).  Arguments as forward_batch,
+    minus outPoses.  Returns dict(records = device float64 [B,32] -- RES_VALID 1: a record, 3: the frame's refinement team timed
+    out, run it again as a blocking call with refine_solo at call + b (harness.rerun_frames) --, scores = device float64 [B,N],
+    call = the call counter of frame 0, seed); last_result() returns the same dict.  Advances the call counter by B."""
+    who = "esac.forward_batch_async"
+    if not isinstance(hypAssignment, torch.Tensor) or hypAssignment.dim() != 2 or hypAssignment.dtype != torch.int64 or hypAssignment.numel() == 0:
+        raise RuntimeError("%s: hypAssignment must be a non-empty int64 [B,N]" % who)
+    if not isinstance(sceneCoordinates, torch.Tensor) or sceneCoordinates.dtype != torch.float32 or sceneCoordinates.dim() not in (4, 5) \
+            or sceneCoordinates.size(-3) != 3:
+        raise RuntimeError("%s: sceneCoordinates must be float32 [B,E,3,H,W] or [E,3,H,W]" % who)
+    B, N = hypAssignment.shape
+    if B > MAX_BATCH:
+        raise RuntimeError("%s: hypAssignment holds %d frames, at most %d per call" % (who, B, MAX_BATCH))
+    if sceneCoordinates.dim() == 5 and sceneCoordinates.size(0) != B:
+        raise RuntimeError("%s: batch sizes of sceneCoordinates and hypAssignment differ" % who)
+    (shiftX, shiftY, focalLength, ppointX, ppointY), cams = _per_frame_cams(who, B, shiftX, shiftY, focalLength, ppointX, ppointY)
+    eng = engine(sceneCoordinates.device.index if sceneCoordinates.is_cuda else None)
+    E, H, W = sceneCoordinates.shape[-4], sceneCoordinates.shape[-2], sceneCoordinates.shape[-1]
+    p = eng.make_params(E, H, W, N, shiftX, shiftY, focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha,
+                        inlierBeta, maxReproj, subSampling, seed=_state["seed"], call=_state["call"],
+                        max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"],
+                        strict_reference=_state["strict_reference"])
+    first = _state["call"]
+    _state["call"] += B
+    scores = torch.empty(B, N, dtype=torch.float64, device=eng.device)
+    # (zeros: a frame whose kernels never reach the record write reads RES_VALID = 0 -> EVAL_STATUS 1, not stale memory)
+    records = torch.zeros(B, RES_DOUBLES, dtype=torch.float64, device=eng.device)
+    eng.forward_batch(sceneCoordinates, hypAssignment, p, scores_out=scores, result_out=records, want_host=False, cams=cams)
+    _state["last"] = {"records": records, "scores": scores, "call": first, "seed": _state["seed"]}
+    return _state["last"]

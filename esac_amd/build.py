@@ -13,7 +13,8 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libesac_hip.so")
-SOURCES = ["esac_kernels.hip", "esac_score_tiled.hip", "esac_refine.hip", "esac_refine_team.hip", "esac_backward.hip", "esac_capi.hip"]
+SOURCES = ["esac_kernels.hip", "esac_score_tiled.hip", "esac_refine.hip", "esac_refine_team.hip", "esac_backward.hip", "esac_eval.hip",
+           "esac_capi.hip"]
 # every header under csrc/ (a new one must not be forgotten here: a stale library would be tested against new headers)
 HEADERS = sorted(os.path.basename(h) for h in glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join("..", "..", "include", "esac_hip.h")]
 # -ffp-contract=off: the fp64 "exact" kernels follow IEEE op-by-op like the CPU
@@ -52,7 +53,7 @@ OBJ_DIR = os.path.join(_HERE, "build")  # git-ignored; objects are keyed by (sou
 
 
 def _compile_and_link(out_path, extra_flags=(), force=False, verbose=False):
-    """One translation unit per hipcc process, side by side (the six sources are independent: a minute becomes the longest file's
+    """One translation unit per hipcc process, side by side (the sources are independent: a minute becomes the longest file's
     ~25 s), objects reused when neither the source, a header nor the flags changed; then one link."""
     from concurrent.futures import ThreadPoolExecutor
     os.makedirs(OBJ_DIR, exist_ok=True)

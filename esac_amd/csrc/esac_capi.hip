@@ -16,6 +16,7 @@
 
 #include "../../include/esac_hip.h"
 #include "esac_kernels.hpp"
+#include "eval_math.hpp"
 #include "gt_math.hpp"
 #include "pose_math.hpp"
 
@@ -1571,6 +1572,28 @@ extern "C" int esac_hip_shard_balanced(esac_hip_ctx* c, const int64_t* d_assign,
     DeviceGuard guard(c->device);
     launch_shard_balanced(d_assign, N, E, world, rank, expert_base, d_index_out, d_assign_out, d_info_out, (hipStream_t)stream);
     return check_launch("k_shard_balanced");
+}
+
+// The test loop's figures of a batch, on the device (esac_eval.hip; include/esac_hip.h): one launch on the caller's stream, no
+// workspace, no state of the context beyond its device.
+static_assert(ESAC_EVAL_ROT_DEG == ESAC_EVAL_ROT_DEG_K && ESAC_EVAL_TRANS_CM == ESAC_EVAL_TRANS_CM_K && ESAC_EVAL_POSE_OK == ESAC_EVAL_POSE_OK_K &&
+                  ESAC_EVAL_CLASS_OK == ESAC_EVAL_CLASS_OK_K && ESAC_EVAL_QUAT == ESAC_EVAL_QUAT_K && ESAC_EVAL_INV_T == ESAC_EVAL_INV_T_K &&
+                  ESAC_EVAL_EXPERT == ESAC_EVAL_EXPERT_K && ESAC_EVAL_HYP == ESAC_EVAL_HYP_K && ESAC_EVAL_STATUS == ESAC_EVAL_STATUS_K &&
+                  ESAC_EVAL_DOUBLES == ESAC_EVAL_DOUBLES_K && ESAC_RES_DOUBLES == ESAC_EVAL_REC_DOUBLES && ESAC_RES_HYP == ESAC_EVAL_REC_HYP &&
+                  ESAC_RES_EXPERT == ESAC_EVAL_REC_EXPERT && ESAC_RES_POSE == ESAC_EVAL_REC_POSE && ESAC_RES_VALID == ESAC_EVAL_REC_VALID,
+              "eval row / record layout drifted between include/esac_hip.h and eval_math.hpp");
+extern "C" int esac_hip_eval_batch(esac_hip_ctx* c, int B, const double* d_records, const float* d_gt_poses, const int64_t* d_gt_experts,
+                                   float rot_thresh_deg, float trans_thresh_cm, void* stream, double* d_out) {
+    if (!c) return fail(-1, "null context");
+    if (B < 1 || B > ESAC_MAX_BATCH) return fail(-4, "esac_hip_eval_batch: batch size %d outside [1,%d]", B, ESAC_MAX_BATCH);
+    if (!d_records || !d_gt_poses || !d_out)
+        return fail(-4, "esac_hip_eval_batch: null %s pointer", !d_records ? "d_records" : !d_gt_poses ? "d_gt_poses" : "d_out");
+    if (!(rot_thresh_deg >= 0.0f) || !(rot_thresh_deg <= FLT_MAX) || !(trans_thresh_cm >= 0.0f) || !(trans_thresh_cm <= FLT_MAX))
+        return fail(-4, "esac_hip_eval_batch: the thresholds must be finite and not negative (rotation %g deg, translation %g cm)",
+                    (double)rot_thresh_deg, (double)trans_thresh_cm);
+    DeviceGuard guard(c->device);
+    launch_eval_batch(B, d_records, d_gt_poses, d_gt_experts, (double)rot_thresh_deg, (double)trans_thresh_cm, d_out, (hipStream_t)stream);
+    return check_launch("k_eval_batch");
 }
 
 extern "C" int esac_hip_set_wait(esac_hip_ctx* c, int mode) {

@@ -256,6 +256,9 @@ void launch_stats_exact(const KArgs& a, hipStream_t s);
 void launch_pick_record(const double* records, int world, double* pin, double epoch, double* zero, int n_zero, hipStream_t s);
 void launch_shard_balanced(const int64_t* assign, int N, int E, int world, int rank, int expert_base, int32_t* index_out,
                            int64_t* assign_out, int32_t* info_out, hipStream_t s);
+// esac_eval.hip: records [B,32] + ground truth -> the test loop's figures [B,16] (eval_math.hpp), one lane per frame, in stream order
+void launch_eval_batch(int B, const double* records, const float* gt_poses, const int64_t* gt_experts, double rot_thresh_deg,
+                       double trans_thresh_cm, double* out, hipStream_t s);
 int refine_coop_capacity();              // resident workgroups of the cooperative refinement kernel on the current device
 int refine_coop_slice(const KArgs& a);  // cells per cooperating refinement workgroup, 0: one workgroup refines
 int refine_team_members(const KArgs& a);  // members of the team that refines a small grid, 0: one workgroup refines

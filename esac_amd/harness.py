@@ -52,8 +52,11 @@ def pose_errors_deg_cm(out_pose, gt_pose):
     return float(np.linalg.norm(r) * 180.0 / math.pi), t_err * 100.0
 
 
-def pose_file_line(name, out_pose):
-    """One line of poses_esac_<session>.txt: name qw qx qy qz tx ty tz of the INVERTED pose (test_esac.py:230-247)."""
+POSE_LINE_FORMAT = "%s %f %f %f %f %f %f %f\n"  # name qw qx qy qz tx ty tz
+
+
+def pose_file_values(out_pose):
+    """(qw, qx, qy, qz, tx, ty, tz) of the INVERTED pose: the seven numbers of a pose-file line (test_esac.py:230-247)."""
     inv = np.linalg.inv(np.asarray(out_pose, np.float64))
     t = inv[0:3, 3]
     rot = rodrigues_vector(inv[0:3, 0:3])
@@ -61,7 +64,28 @@ def pose_file_line(name, out_pose):
     axis = rot / angle if angle > 0 else np.array([1.0, 0.0, 0.0])
     q_w = math.cos(angle * 0.5)
     q_xyz = math.sin(angle * 0.5) * axis
-    return "%s %f %f %f %f %f %f %f\n" % (name, q_w, q_xyz[0], q_xyz[1], q_xyz[2], float(t[0]), float(t[1]), float(t[2]))
+    return q_w, q_xyz[0], q_xyz[1], q_xyz[2], float(t[0]), float(t[1]), float(t[2])
+
+
+def pose_file_line(name, out_pose):
+    """One line of poses_esac_<session>.txt: name qw qx qy qz tx ty tz of the INVERTED pose (test_esac.py:230-247)."""
+    return POSE_LINE_FORMAT % ((name,) + pose_file_values(out_pose))
+
+
+def eval_row_host(out_pose, gt_pose, expert, hyp, gt_expert=None, rot_threshold_deg=5.0, trans_threshold_cm=5.0):
+    """One row of esac.eval_batch (api.EVAL_*), computed by the host functions above: what the device row is held against, and
+    what `rerun_frames` puts in the place of a frame it ran again."""
+    row = np.zeros(api.EVAL_DOUBLES, np.float64)
+    r_err, t_err = pose_errors_deg_cm(out_pose, gt_pose)
+    row[api.EVAL_ROT_DEG], row[api.EVAL_TRANS_CM] = r_err, t_err
+    row[api.EVAL_POSE_OK] = float(t_err < trans_threshold_cm and r_err < rot_threshold_deg)
+    row[api.EVAL_CLASS_OK] = -1.0 if gt_expert is None else float(int(gt_expert) == int(expert))
+    try:
+        row[api.EVAL_QUAT:api.EVAL_QUAT + 7] = pose_file_values(out_pose)
+    except np.linalg.LinAlgError:  # a singular pose: no inverse to print
+        row[api.EVAL_QUAT:api.EVAL_QUAT + 7] = np.nan
+    row[api.EVAL_EXPERT], row[api.EVAL_HYP] = float(expert), float(hyp)
+    return row
 
 
 @torch.no_grad()
@@ -108,25 +132,154 @@ def localize(image, gating, experts, focal_length, hypotheses=256, threshold=10.
                 time_s=time.time() - start, prediction=prediction, hyp_assignment=e_hyps)
 
 
-def evaluate(samples, gating, experts, trans_threshold_cm=5.0, rot_threshold_deg=5.0, pose_log=None, **kw):
-    """The statistics block of test_esac.py:249-289 over `samples` = iterable of
-    (name, image, focal_length, gt_pose [4,4], gt_expert)."""
-    E = len(experts)
-    scenes_r, scenes_t, scenes_c = [[] for _ in range(E)], [[] for _ in range(E)], [[] for _ in range(E)]
-    avg_active = max_active = avg_time = n = 0
-    for name, image, focal, gt_pose, gt_expert in samples:
-        out = localize(image, gating, experts, focal, **kw)
-        r_err, t_err = pose_errors_deg_cm(out["pose"].numpy(), np.asarray(gt_pose))
-        scenes_r[gt_expert].append(r_err)
-        scenes_t[gt_expert].append(t_err)
-        scenes_c[gt_expert].append(int(gt_expert) == out["expert"])
-        avg_active += out["active_experts"]
-        max_active = max(max_active, out["active_experts"])
-        avg_time += out["time_s"]
-        n += 1
-        if pose_log is not None:
-            pose_log.write(pose_file_line(name, out["pose"].numpy()))
+def _focal_list(who, focal_lengths, B):
+    """B focal lengths from a number, a sequence, an array or a tensor."""
+    focals = [float(f) for f in (focal_lengths.tolist() if isinstance(focal_lengths, (torch.Tensor, np.ndarray)) and
+                                 getattr(focal_lengths, "ndim", 0) > 0 else
+                                 focal_lengths if isinstance(focal_lengths, (list, tuple)) else [focal_lengths] * B)]
+    if len(focals) != B:
+        raise RuntimeError("%s: focal_lengths must hold one value per image (%d), found %d" % (who, B, len(focals)))
+    return focals
 
+
+@torch.no_grad()
+def localize_batch(images, gating, experts, focal_lengths, gt_poses=None, gt_experts=None, hypotheses=256, threshold=10.0,
+                   inlier_alpha=100.0, inlier_beta=0.5, max_reprojection=100.0, subsample=8, e_hyps=None, expert_selection=False,
+                   oracle_experts=None, generator=None, asynchronous=False, all_experts=False, strict_reference=False,
+                   rot_threshold_deg=5.0, trans_threshold_cm=5.0):
+    """The test-loop counterpart of `train_batch`: B images of one size through ONE forward batch (`esac.forward_batch_async`) and,
+    when `gt_poses` is given, ONE `esac.eval_batch` that turns the records into the loop's figures on the device.
+
+    images [B,3,H,W]; focal_lengths: B numbers (or one for all), they travel as the call's per-frame camera table.
+    gating(images) -> log-probabilities [B,E]; experts[e](images) -> [B,3,H/s,W/s].  The gating runs once on the batch, every frame
+    gets its own multinomial row (or `e_hyps` [B,N]; expert_selection / oracle_experts: one expert per frame, a stride-0 row), and
+    every expert that is active in at least one frame runs once on the batch (rows of frames in which it is inactive are never
+    read).  all_experts: every expert runs and the `.cpu()` of the B x E activity flags is skipped.
+    gt_poses [B,4,4] and gt_experts [B] (tensors on either side, arrays, lists) feed eval_batch; host values are uploaded
+    asynchronously.  strict_reference: as in `localize`.
+    asynchronous=True with all_experts=True and device inputs: NO host synchronisation in this function; every result stays on
+    the device.  A frame whose refinement team timed out then carries EVAL_STATUS / RES_VALID = 3: `frames_to_rerun` finds
+    them in the host copy of `eval`, `rerun_frames` runs them again.
+    Returns dict(records [B,32] device, scores [B,N] device, eval [B,16] device or None, e_hyps [B,N] device, e_hist [B,E] device,
+    prediction [B,E,3,h,w] device, active_experts [B] device, call (frame 0's call counter; frame b ran at call + b), seed, time_s
+    and what `rerun_frames` needs).  Not asynchronous: also poses [B,4,4] float32 cpu, experts (list of B ints), records_host,
+    eval as a numpy array [B,16] (the device tensor stays under eval_device) and active_experts as a list; frames with status 3
+    have been run again already."""
+    dev = images.device
+    B, E = int(images.size(0)), len(experts)
+    pp_x = float(images.size(3) / 2)
+    pp_y = float(images.size(2) / 2)
+    pred_w = math.ceil(images.size(3) / subsample)
+    pred_h = math.ceil(images.size(2) / subsample)
+    focals = _focal_list("localize_batch", focal_lengths, B)
+    start = time.time()
+    if e_hyps is not None:
+        e_hyps = torch.as_tensor(e_hyps, dtype=torch.int64).to(dev)
+        if e_hyps.dim() != 2 or e_hyps.size(0) != B:
+            raise RuntimeError("localize_batch: e_hyps must be [B,N]")
+    else:
+        gating_probs = torch.exp(gating(images))  # [B,E], stays on the device
+        if oracle_experts is not None:
+            oracle = torch.as_tensor(oracle_experts, dtype=torch.int64).reshape(-1)
+            if oracle.numel() != B:
+                raise RuntimeError("localize_batch: oracle_experts must hold one expert per image (%d), found %d" % (B, oracle.numel()))
+            gating_probs = torch.zeros_like(gating_probs).scatter_(1, oracle.to(dev, non_blocking=True).unsqueeze(1), 1.0)
+        if expert_selection or oracle_experts is not None:
+            expert = torch.multinomial(gating_probs, 1, replacement=True, generator=generator)  # [B,1]
+            e_hyps = expert.expand((B, hypotheses))  # stride-0 rows, as in the reference
+        else:
+            e_hyps = torch.multinomial(gating_probs, hypotheses, replacement=True, generator=generator)  # one row of draws per frame
+    e_hist = torch.zeros((B, E), device=dev).scatter_add_(1, e_hyps, torch.ones(e_hyps.shape, device=dev))
+    active_count = (e_hist > 0).sum(dim=1)  # [B], device
+    if all_experts:
+        active_any = [True] * E  # no flags cross to the host: every expert runs
+    else:
+        active_any = (e_hist > 0).any(dim=0).cpu().tolist()  # E flags: all that reaches the host before the call
+    outputs = [experts[e](images) if on else torch.zeros((B, 3, pred_h, pred_w), device=dev) for e, on in enumerate(active_any)]
+    prediction = torch.stack(outputs, dim=1)  # [B,E,3,h,w]; rows of inactive experts are never read
+    e_hyps = e_hyps.contiguous()
+    strict_before = api._state["strict_reference"]
+    strict = bool(strict_before or strict_reference)
+    api.set_strict_reference(strict)
+    try:
+        fwd = api.forward_batch_async(prediction, e_hyps, 0, 0, focals, pp_x, pp_y, threshold, inlier_alpha, inlier_beta,
+                                      max_reprojection, subsample)
+    finally:
+        api.set_strict_reference(strict_before)
+    ev = None
+    if gt_poses is not None:
+        ev = api.eval_batch(fwd["records"], gt_poses, gt_experts, rot_threshold_deg, trans_threshold_cm)
+    out = dict(records=fwd["records"], scores=fwd["scores"], eval=ev, e_hyps=e_hyps, e_hist=e_hist, prediction=prediction,
+               active_experts=active_count, call=fwd["call"], seed=fwd["seed"], focals=focals, gt_poses=gt_poses, gt_experts=gt_experts,
+               solver=dict(pp_x=pp_x, pp_y=pp_y, threshold=threshold, inlier_alpha=inlier_alpha, inlier_beta=inlier_beta,
+                           max_reprojection=max_reprojection, subsample=subsample, strict_reference=strict,
+                           max_tries=api._state["max_tries"], max_ref_steps=api._state["max_ref_steps"],
+                           rot_threshold_deg=rot_threshold_deg, trans_threshold_cm=trans_threshold_cm))
+    if not asynchronous:
+        rec = fwd["records"].cpu().numpy()  # the one wait of the blocking form
+        out["records_host"] = rec
+        out["eval_device"] = ev
+        out["eval"] = ev.cpu().numpy() if ev is not None else None
+        out["poses"] = torch.from_numpy(rec[:, api.RES_POSE:api.RES_POSE + 16].astype(np.float32).reshape(B, 4, 4))
+        out["experts"] = [int(v) for v in rec[:, api.RES_EXPERT]]
+        out["active_experts"] = active_count.cpu().tolist()
+        again = [int(b) for b in np.flatnonzero(rec[:, api.RES_VALID] == 3.0)]
+        if again:
+            rerun_frames(out, again)
+    out["time_s"] = time.time() - start
+    return out
+
+
+def frames_to_rerun(eval_host):
+    """Indices of the rows of a host copy of `eval` ([n,16]) whose EVAL_STATUS is 3: frames of an asynchronous batch whose
+    refinement team timed out (include/esac_hip.h, ESAC_RES_VALID = 3).  A pure function."""
+    ev = np.asarray(eval_host, np.float64).reshape(-1, api.EVAL_DOUBLES)
+    return [int(i) for i in np.flatnonzero(ev[:, api.EVAL_STATUS] == 3.0)]
+
+
+def rerun_frames(batch_out, frames):
+    """Runs the named frames of a `localize_batch` result again, each as a BLOCKING single call at the frame's own key
+    (seed, call + b), with its own camera and the one-workgroup refinement (refine_solo) -- the rule of include/esac_hip.h for a
+    record with ESAC_RES_VALID = 3.  The module's call counter is not touched.  Returns {b: dict(record np.float64[32], pose
+    [4,4] float32 numpy, expert, eval np.float64[16] or None)}; the eval row is recomputed by the host functions (eval_row_host)
+    against the float32 ground truth the device row used.  Host-side entries of `batch_out` (records_host, poses, experts, eval as
+    numpy) are updated in place where they exist."""
+    pred, e_hyps, s = batch_out["prediction"], batch_out["e_hyps"], batch_out["solver"]
+    B, E, _, H, W = pred.shape
+    N = int(e_hyps.shape[1])
+    eng = api.engine(pred.device.index)
+    done = {}
+    for b in frames:
+        b = int(b)
+        if not 0 <= b < B:
+            raise RuntimeError("rerun_frames: frame %d outside the batch of %d" % (b, B))
+        p = eng.make_params(E, H, W, N, 0, 0, batch_out["focals"][b], s["pp_x"], s["pp_y"], s["threshold"], s["inlier_alpha"],
+                            s["inlier_beta"], s["max_reprojection"], s["subsample"], seed=batch_out["seed"], call=batch_out["call"] + b,
+                            max_tries=s["max_tries"], max_ref_steps=s["max_ref_steps"], refine_solo=True,
+                            strict_reference=s["strict_reference"])
+        rec = eng.forward_device(pred[b], e_hyps[b], p)
+        pose = rec[api.RES_POSE:api.RES_POSE + 16].astype(np.float32).reshape(4, 4)
+        row = None
+        if batch_out.get("gt_poses") is not None:
+            gt = batch_out["gt_poses"][b]
+            gt = gt.detach().cpu().numpy() if isinstance(gt, torch.Tensor) else np.asarray(gt)
+            ge = batch_out.get("gt_experts")
+            ge = None if ge is None else int(ge[b])
+            row = eval_row_host(pose, gt.astype(np.float32), int(rec[api.RES_EXPERT]), int(rec[api.RES_HYP]), ge,
+                                s["rot_threshold_deg"], s["trans_threshold_cm"])
+        done[b] = dict(record=rec, pose=pose, expert=int(rec[api.RES_EXPERT]), eval=row)
+        if "records_host" in batch_out:
+            batch_out["records_host"][b] = rec
+            batch_out["records_host"][b, api.RES_VALID] = 1.0
+            batch_out["poses"][b] = torch.from_numpy(pose)
+            batch_out["experts"][b] = int(rec[api.RES_EXPERT])
+        if isinstance(batch_out.get("eval"), np.ndarray) and row is not None:
+            batch_out["eval"][b] = row
+    return done
+
+
+def _statistics(E, scenes_r, scenes_t, scenes_c, trans_threshold_cm, rot_threshold_deg, avg_active, max_active, avg_time, n):
+    """The statistics block of test_esac.py:249-289 from the per-scene lists."""
     def median(values):
         if len(values) == 0:
             return 0
@@ -141,6 +294,94 @@ def evaluate(samples, gating, experts, trans_threshold_cm=5.0, rot_threshold_deg
                          median_rot_deg=median(scenes_r[s]), median_trans_cm=median(scenes_t[s])))
     return dict(scenes=rows, avg_active=avg_active / max(n, 1), max_active=max_active, avg_time_s=avg_time / max(n, 1),
                 images=n)
+
+
+def evaluate(samples, gating, experts, trans_threshold_cm=5.0, rot_threshold_deg=5.0, pose_log=None, batch_size=1,
+             asynchronous=False, **kw):
+    """The statistics block of test_esac.py:249-289 over `samples` = iterable of
+    (name, image, focal_length, gt_pose [4,4], gt_expert).
+    batch_size > 1: consecutive samples whose images have one shape are stacked, up to batch_size of them (a batch is cut where
+    the shape changes; the last one may be short), and each batch goes through `localize_batch` -- one forward batch and one
+    on-device evaluation instead of batch_size blocking calls with their copies.  The eval rows of all batches are copied to the
+    host ONCE, after the last batch; frames whose status is 3 are run again (`rerun_frames`); the statistics and the pose-log lines
+    (the format string of `pose_file_line` over the row's quaternion and translation) follow from the rows.  asynchronous: the
+    batches are enqueued without a host synchronisation (localize_batch(asynchronous=True, all_experts=True)), given device images.
+    `oracle_expert=k` in **kw applies to every image, as with batch_size 1."""
+    E = len(experts)
+    if int(batch_size) > 1:
+        return _evaluate_batched(samples, gating, experts, trans_threshold_cm, rot_threshold_deg, pose_log, int(batch_size),
+                                 asynchronous, kw)
+    scenes_r, scenes_t, scenes_c = [[] for _ in range(E)], [[] for _ in range(E)], [[] for _ in range(E)]
+    avg_active = max_active = avg_time = n = 0
+    for name, image, focal, gt_pose, gt_expert in samples:
+        out = localize(image, gating, experts, focal, **kw)
+        r_err, t_err = pose_errors_deg_cm(out["pose"].numpy(), np.asarray(gt_pose))
+        scenes_r[gt_expert].append(r_err)
+        scenes_t[gt_expert].append(t_err)
+        scenes_c[gt_expert].append(int(gt_expert) == out["expert"])
+        avg_active += out["active_experts"]
+        max_active = max(max_active, out["active_experts"])
+        avg_time += out["time_s"]
+        n += 1
+        if pose_log is not None:
+            pose_log.write(pose_file_line(name, out["pose"].numpy()))
+    return _statistics(E, scenes_r, scenes_t, scenes_c, trans_threshold_cm, rot_threshold_deg, avg_active, max_active, avg_time, n)
+
+
+def _evaluate_batched(samples, gating, experts, trans_threshold_cm, rot_threshold_deg, pose_log, batch_size, asynchronous, kw):
+    E = len(experts)
+    kw = dict(kw)
+    oracle_expert = kw.pop("oracle_expert", None)
+    if asynchronous:
+        kw.setdefault("all_experts", True)
+    start = time.time()
+    batches, names, gt_exp = [], [], []  # per batch: its localize_batch result; per image: name and true expert
+
+    def run(group):
+        images = torch.cat([g[1] for g in group])
+        gts = np.stack([np.asarray(g[3].detach().cpu() if isinstance(g[3], torch.Tensor) else g[3], np.float32) for g in group])
+        out = localize_batch(images, gating, experts, [float(g[2]) for g in group], gt_poses=gts,
+                             gt_experts=[int(g[4]) for g in group], asynchronous=asynchronous,
+                             oracle_experts=None if oracle_expert is None else [int(oracle_expert)] * len(group),
+                             rot_threshold_deg=rot_threshold_deg, trans_threshold_cm=trans_threshold_cm, **kw)
+        batches.append(out)
+        names.extend(g[0] for g in group)
+        gt_exp.extend(int(g[4]) for g in group)
+
+    group = []
+    for sample in samples:
+        if group and (len(group) == batch_size or tuple(sample[1].shape) != tuple(group[0][1].shape)):
+            run(group)
+            group = []
+        group.append(sample)
+    if group:
+        run(group)
+    n = len(names)
+    if n == 0:
+        return _statistics(E, [[] for _ in range(E)], [[] for _ in range(E)], [[] for _ in range(E)], trans_threshold_cm,
+                           rot_threshold_deg, 0, 0, 0, 0)
+    if asynchronous:
+        # one copy for the whole test set: the eval rows and the active-expert counts of every batch
+        both = torch.cat([torch.cat([b["eval"], b["active_experts"].to(torch.float64).unsqueeze(1)], dim=1) for b in batches]).cpu().numpy()
+        rows, active = both[:, :api.EVAL_DOUBLES].copy(), both[:, api.EVAL_DOUBLES]
+        first = 0
+        for b in batches:
+            size = int(b["records"].shape[0])
+            for f, redo in rerun_frames(b, frames_to_rerun(rows[first:first + size])).items():
+                rows[first + f] = redo["eval"]
+            first += size
+    else:
+        rows = np.concatenate([b["eval"] for b in batches])
+        active = np.concatenate([np.asarray(b["active_experts"], np.float64) for b in batches])
+    scenes_r, scenes_t, scenes_c = [[] for _ in range(E)], [[] for _ in range(E)], [[] for _ in range(E)]
+    for name, ge, row in zip(names, gt_exp, rows):
+        scenes_r[ge].append(float(row[api.EVAL_ROT_DEG]))
+        scenes_t[ge].append(float(row[api.EVAL_TRANS_CM]))
+        scenes_c[ge].append(bool(row[api.EVAL_CLASS_OK] == 1.0))
+        if pose_log is not None:
+            pose_log.write(POSE_LINE_FORMAT % ((name,) + tuple(float(v) for v in row[api.EVAL_QUAT:api.EVAL_QUAT + 7])))
+    return _statistics(E, scenes_r, scenes_t, scenes_c, trans_threshold_cm, rot_threshold_deg, float(active.sum()),
+                       int(active.max()), time.time() - start, n)
 
 
 # ---------------------------------------------------------------- training glue (train_esac.py:104-200)

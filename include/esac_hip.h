@@ -332,6 +332,38 @@ int esac_hip_shard_balanced(esac_hip_ctx* ctx, const int64_t* d_hyp_assign, int 
                             int expert_base, void* stream, int32_t* d_index_out, int64_t* d_assign_out, int32_t* d_info_out);
 
 /*
+ * The test loop's figures of a batch, computed on the device (new; test_esac.py:209-247): what a caller of the batched forward
+ * needs to report a test set without a host round trip per image.  Frame b takes its pose from ESAC_RES_POSE of record b -- the
+ * 16 values as FLOATS, the numbers esac.forward puts into outPose -- and its row of ESAC_EVAL_DOUBLES doubles holds, in fp64:
+ *   ESAC_EVAL_ROT_DEG   |axis-angle(out_R * gt_R^T)| * 180 / pi                (test_esac.py:213-216)
+ *   ESAC_EVAL_TRANS_CM  |gt_t - out_t| * 100                                    (test_esac.py:211)
+ *   ESAC_EVAL_POSE_OK   1 when TRANS_CM < trans_thresh_cm and ROT_DEG < rot_thresh_deg (strict), else 0
+ *   ESAC_EVAL_CLASS_OK  1 when ESAC_RES_EXPERT == d_gt_experts[b], else 0; -1 when d_gt_experts is NULL
+ *   ESAC_EVAL_QUAT      qw qx qy qz and ESAC_EVAL_INV_T tx ty tz of the INVERTED pose (general 4x4 inverse, then
+ *                       (cos(a/2), sin(a/2) * axis), axis (1,0,0) at angle 0): one line of poses_esac_*.txt (test_esac.py:230-247)
+ *   ESAC_EVAL_EXPERT, ESAC_EVAL_HYP   copied from the record
+ *   ESAC_EVAL_STATUS    0: a delivered record (ESAC_RES_VALID == 1); 3: ESAC_RES_VALID == 3, the refinement team of an
+ *                       asynchronous batch timed out -- run that frame again with ESAC_FLAG_REFINE_SOLO at call + b; 1: no record.
+ *                       With a status other than 0 the two errors, the quaternion and the translation are NaN and both flags 0
+ *                       (CLASS_OK stays -1 without d_gt_experts).
+ * A non-finite pose gives NaN figures and POSE_OK = 0 with status 0; a singular one a NaN quaternion and translation.
+ * The axis-angle step is the one of esac_amd/harness.py (rodrigues_vector), branch by branch: rows differ from the harness's host
+ * functions by libm's last bits.
+ * d_records    DEVICE [B,ESAC_RES_DOUBLES]: what esac_hip_forward_batch* wrote through d_result_out.
+ * d_gt_poses   DEVICE float [B,4,4]; d_gt_experts DEVICE int64 [B] or NULL; d_out DEVICE [B,ESAC_EVAL_DOUBLES].
+ * Asynchronous: one launch on `stream`, no allocation, no wait, no state of a forward call in flight is touched; everything is
+ * read in stream order, so the call may be enqueued right behind an asynchronous esac_hip_forward_batch*.
+ * -4 before any launch: B outside [1,ESAC_MAX_BATCH], a null d_records, d_gt_poses or d_out, a negative or non-finite threshold.
+ */
+#define ESAC_EVAL_DOUBLES 16
+enum { ESAC_EVAL_ROT_DEG = 0, ESAC_EVAL_TRANS_CM = 1, ESAC_EVAL_POSE_OK = 2, ESAC_EVAL_CLASS_OK = 3,
+       ESAC_EVAL_QUAT = 4 /* qw qx qy qz */, ESAC_EVAL_INV_T = 8 /* tx ty tz */, ESAC_EVAL_EXPERT = 11,
+       ESAC_EVAL_HYP = 12, ESAC_EVAL_STATUS = 13 /* 14, 15 reserved, written 0 */ };
+int esac_hip_eval_batch(esac_hip_ctx* ctx, int B, const double* d_records /* [B,ESAC_RES_DOUBLES] */,
+                        const float* d_gt_poses /* DEVICE [B,4,4] */, const int64_t* d_gt_experts /* DEVICE [B] or NULL */,
+                        float rot_thresh_deg, float trans_thresh_cm, void* stream, double* d_out /* DEVICE [B,ESAC_EVAL_DOUBLES] */);
+
+/*
  * esac_backward (esac.cpp:213-520): expected pose loss over the hypothesis distribution and its gradient wrt the
  * scene coordinates, everything on the device.
  * Status -10: hypAssignment held a value outside [0,E) (the reference reads out of bounds there).
