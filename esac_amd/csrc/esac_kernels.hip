@@ -29,6 +29,7 @@
 #include "rng.hpp"
 #include "esac_kernels.hpp"
 #include "device_common.hpp"
+#include "select_math.hpp"
 
 namespace esac {
 
@@ -853,13 +854,7 @@ __global__ __launch_bounds__(B) void k_select_rescore(KArgs a) {
     // max (NaN-ignoring)
     float m = -INFINITY;
     for (int i = threadIdx.x; i < a.N; i += B) m = fmaxf(m, fast_score(i));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = s_max[0];
-#pragma unroll
-    for (int k = 1; k < B / 64; k++) m = fmaxf(m, s_max[k]);
+    m = block_max<B>(m, s_max);
     const float band = m - a.margin;
 
     // large grids: gridDim.z workgroups share a contender, workgroup z sums the cells of range z; the last one to arrive
@@ -878,11 +873,8 @@ __global__ __launch_bounds__(B) void k_select_rescore(KArgs a) {
             const float fs = fast_score(blockIdx.x);  // workgroup-uniform
             nc = fs >= band ? 1 : 0;
             if (!nc && threadIdx.x == 0 && z == 0) {
-                if (!(spec && a.spec_flag[blockIdx.x])) {
-                    a.scores[blockIdx.x] = (double)fs;
-                    if (a.scores_user) a.scores_user[user_slot(a, blockIdx.x)] = (double)fs;
-                }
-                a.exact_flag[blockIdx.x] = 0;
+                if (spec && a.spec_flag[blockIdx.x]) a.exact_flag[blockIdx.x] = 0;
+                else store_score(a, blockIdx.x, (double)fs, 0);
             }
         } else {
             if (threadIdx.x == 0) s_nc = 0;
@@ -894,11 +886,8 @@ __global__ __launch_bounds__(B) void k_select_rescore(KArgs a) {
                 if (fs >= band) {
                     s_cont[atomicAdd(&s_nc, 1)] = h;  // at most B entries per pass
                 } else if (z == 0) {
-                    if (!(spec && a.spec_flag[h])) {
-                        a.scores[h] = (double)fs;
-                        if (a.scores_user) a.scores_user[user_slot(a, h)] = (double)fs;
-                    }
-                    a.exact_flag[h] = 0;
+                    if (spec && a.spec_flag[h]) a.exact_flag[h] = 0;
+                    else store_score(a, h, (double)fs, 0);
                 }
             }
             __syncthreads();
@@ -906,47 +895,25 @@ __global__ __launch_bounds__(B) void k_select_rescore(KArgs a) {
         }
         for (int ci = 0; ci < nc; ci++) {
             const int h = single ? (int)blockIdx.x : s_cont[ci];
-            const int e = expert_of(a, h);
-            const float* __restrict__ mx = a.sc + (size_t)e * 3 * P;
-            const double* hp = a.hyps + (size_t)h * 6;
-            const double t[3] = {hp[3], hp[4], hp[5]};
-            double R[9];  // rodrigues_vec2mat(rvec) as the sampler stored it (the reference re-expands rvec, esac_util.h:302)
-#pragma unroll
-            for (int k = 0; k < 9; k++) R[k] = a.hyps_R[(size_t)h * 9 + k];
-            double acc[1] = {0};
-            for (int i = c0 + threadIdx.x; i < c1; i += B) {
-                const int row = i / a.W, col = i - row * a.W;
-                float err = project_exact_err(R, t, cam, mx[i], mx[P + i], mx[2 * P + i], cell_px(a, col), cell_py(a, row));
-                err = err < a.max_reproj ? err : a.max_reproj;  // std::min(l, maxReproj), esac_util.h:358
-                acc[0] += soft_inlier_exact(err, a.tau, a.beta);
-            }
-            block_sum<1, B>(acc, s_part, s_tot);
+            double sum = block_exact_score<B, false>(a, h, cam, P, c0, c1, s_part, s_tot);
             if (nz > 1) {
                 if (threadIdx.x == 0) {
-                    __hip_atomic_store(a.sel_partials + (size_t)h * ESAC_SELECT_SPLIT + z, acc[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(a.sel_partials + (size_t)h * ESAC_SELECT_SPLIT + z, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                     const int arrived = atomicAdd(a.sel_arrived + h, 1);
                     s_last = arrived == nz - 1;
                     if (s_last) {
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                        double sum = 0;
+                        sum = 0;
                         for (int k = 0; k < nz; k++)
                             sum += __hip_atomic_load(a.sel_partials + (size_t)h * ESAC_SELECT_SPLIT + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        acc[0] = sum;
                         a.sel_arrived[h] = 0;  // ready for the next call
                     }
                 }
                 __syncthreads();
                 if (!s_last) continue;  // (workgroup-uniform)
             }
-            if (threadIdx.x == 0) {
-                const float scale = a.alpha / a.W / a.H;
-                double sc = acc[0];
-                sc *= scale;  // double *= float
-                a.scores[h] = sc;
-                if (a.scores_user) a.scores_user[user_slot(a, h)] = sc;
-                a.exact_flag[h] = 1;
-            }
+            if (threadIdx.x == 0) store_score(a, h, exact_score_scaled(sum, a.alpha, a.W, a.H), 1);
             __syncthreads();
         }
         if (!single) __syncthreads();
@@ -958,20 +925,11 @@ __global__ __launch_bounds__(B) void k_select_rescore(KArgs a) {
     for (int i = threadIdx.x; i < a.N; i += B) {
         if (spec && a.spec_flag[i]) continue;
         const float s = a.fast_scores[i];
-        const double d = (double)s - (double)m;
-        const double ex = exp(d);
-        acc[0] += ex;
-        acc[1] += ex * d;
+        softmax_add(acc[0], acc[1], (double)s, (double)m);
         acc[2] += (s >= band) ? 1.0 : 0.0;
     }
     block_sum<3, B>(acc, s_part, s_tot);
-    if (threadIdx.x == 0) {
-        a.n_contenders[0] = (int)acc[2];
-        a.stats[0] = (double)m;  // max
-        a.stats[1] = acc[0];     // sum exp(s - max)
-        // entropy = -sum p log2 p,  p = exp(d)/S  ->  log2(S) - (sum exp(d) d) / (S ln 2)
-        a.stats[2] = log2(acc[0]) - acc[1] / (acc[0] * 0.6931471805599453);
-    }
+    if (threadIdx.x == 0) write_stats(a, (int)acc[2], (double)m, acc[0], entropy_bits(acc[0], acc[1]));
     if (a.tstamps) {  // timing mode: span of the score kernel that just ran = max(end) - min(start)
         __shared__ long long s_lo[B / 64], s_hi[B / 64];
         long long lo = 0x7fffffffffffffffLL, hi = 0;
@@ -1006,7 +964,7 @@ __global__ __launch_bounds__(B) void k_select_rescore(KArgs a) {
 // The launch stream has scored the hypotheses the sampler's first pass SETTLED and refined the best of them (fp32 ranking); on a
 // second stream of the context's own the selection among the settled hypotheses (k_select_rescore, spec_mode 1) has run beside that
 // refinement, and this kernel behind it; on the first one the straggler chain and the stragglers' fp32 scores.  This kernel (ONE
-// workgroup, the arithmetic of k_select_rescore<1024, true> statement by statement, so that every number is the serial route's) is
+// workgroup; it calls the functions k_select_rescore<1024, true> calls -- select_math.hpp -- so every number is the serial route's) is
 // resident before refinement and chain are done, loads what the selection left, waits for their two "done" words, and completes the
 // selection over ALL hypotheses:
 //   * fp32 maximum and band over all of them; a settled hypothesis that was a contender of the narrower (settled-only) band but is
@@ -1087,13 +1045,7 @@ __global__ __launch_bounds__(B) void k_spec_join(KArgs a) {
     float m = -INFINITY;
 #pragma unroll
     for (int k = 0; k < K; k++) m = fmaxf(m, fs[k]);  // (-inf for the slots beyond N: fmaxf ignores them like the loop bound does)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = s_max[0];
-#pragma unroll
-    for (int k = 1; k < B / 64; k++) m = fmaxf(m, s_max[k]);
+    m = block_max<B>(m, s_max);
     const float band = m - a.margin;
     // the final band: stragglers inside it are listed for the exact re-score (practically never any); what is outside it and
     // holds an exact score of the narrower band -- or is a straggler -- gets its fp32 score
@@ -1107,9 +1059,7 @@ __global__ __launch_bounds__(B) void k_spec_join(KArgs a) {
                 if (pos < B) s_cont[pos] = h;  // (more than B of them: the overflow pass below)
             }
         } else if (strag[k] || exact[k]) {
-            a.scores[h] = (double)fs[k];
-            if (a.scores_user) a.scores_user[user_slot(a, h)] = (double)fs[k];
-            a.exact_flag[h] = 0;
+            store_score(a, h, (double)fs[k], 0);
             exact[k] = 0;
         }
     }
@@ -1133,29 +1083,8 @@ __global__ __launch_bounds__(B) void k_spec_join(KArgs a) {
         for (int ci = 0; ci < nc; ci++) {
             // (the order of the list is whatever the atomics made it: every entry is re-scored by the whole workgroup, one after the other)
             const int hc = s_cont[ci];
-            const int e = expert_of(a, hc);
-            const float* __restrict__ mx = a.sc + (size_t)e * 3 * P;
-            const double* hp = a.hyps + (size_t)hc * 6;
-            const double t[3] = {hp[3], hp[4], hp[5]};
-            double R[9];
-#pragma unroll
-            for (int k = 0; k < 9; k++) R[k] = a.hyps_R[(size_t)hc * 9 + k];
-            double acc[1] = {0};
-            for (int i = threadIdx.x; i < P; i += B) {
-                const int row = i / a.W, col = i - row * a.W;
-                float err = project_exact_err(R, t, cam, mx[i], mx[P + i], mx[2 * P + i], cell_px(a, col), cell_py(a, row));
-                err = err < a.max_reproj ? err : a.max_reproj;  // std::min(l, maxReproj), esac_util.h:358
-                acc[0] += soft_inlier_exact(err, a.tau, a.beta);
-            }
-            block_sum<1, B>(acc, s_part, s_tot);
-            if (threadIdx.x == 0) {
-                const float scale = a.alpha / a.W / a.H;
-                double sc = acc[0];
-                sc *= scale;  // double *= float
-                a.scores[hc] = sc;
-                if (a.scores_user) a.scores_user[user_slot(a, hc)] = sc;
-                a.exact_flag[hc] = 1;
-            }
+            const double sum = block_exact_score<B, false>(a, hc, cam, P, 0, P, s_part, s_tot);
+            if (threadIdx.x == 0) store_score(a, hc, exact_score_scaled(sum, a.alpha, a.W, a.H), 1);
             __syncthreads();
         }
     }
@@ -1165,74 +1094,32 @@ __global__ __launch_bounds__(B) void k_spec_join(KArgs a) {
         for (int k = 0; k < K; k++)
             if (strag[k] && fs[k] >= band) exact[k] = 1;
     }
-    // softmax statistics over ALL fp32-path scores (k_select_rescore's own loop and reduction)
+    // softmax statistics over ALL fp32-path scores (k_select_rescore's accumulation and reduction)
     double acc[3] = {0, 0, 0};
 #pragma unroll
     for (int k = 0; k < K; k++) {
         if ((int)threadIdx.x + k * B >= a.N) continue;
-        const float s = fs[k];
-        const double d = (double)s - (double)m;
-        const double ex = exp(d);
-        acc[0] += ex;
-        acc[1] += ex * d;
-        acc[2] += (s >= band) ? 1.0 : 0.0;
+        softmax_add(acc[0], acc[1], (double)fs[k], (double)m);
+        acc[2] += (fs[k] >= band) ? 1.0 : 0.0;
     }
     block_sum<3, B>(acc, s_part, s_tot);
-    const double entropy = log2(acc[0]) - acc[1] / (acc[0] * 0.6931471805599453);
-    if (threadIdx.x == 0) {
-        a.n_contenders[0] = (int)acc[2];
-        a.stats[0] = (double)m;
-        a.stats[1] = acc[0];
-        a.stats[2] = entropy;
-    }
-    // draw(probs, training=false): refine_pick_winner's rule over the final band
+    const double entropy = entropy_bits(acc[0], acc[1]);
+    if (threadIdx.x == 0) write_stats(a, (int)acc[2], (double)m, acc[0], entropy);
+    // draw(probs, training=false) over the final band
     double bs = -INFINITY;
-    int bi = 0x7fffffff, bg = 0x7fffffff;
+    int bi = BEST_NONE, bg = BEST_NONE;
 #pragma unroll
     for (int k = 0; k < K; k++) {
         const int h = (int)threadIdx.x + k * B;
         if (h >= a.N || !exact[k]) continue;
         const int g = global_hyp(a, h);
         const double s = strag[k] ? a.scores[h] : sc0[k];  // (a straggler inside the band: re-scored by this kernel)
-        if (s > bs || (s == bs && g < bg)) {
-            bs = s;
-            bi = h;
-            bg = g;
-        }
+        best_take(bs, bi, bg, s, h, g);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double os = __shfl_xor(bs, o);
-        const int oi = __shfl_xor(bi, o);
-        const int og = __shfl_xor(bg, o);
-        if (os > bs || (os == bs && og < bg)) {
-            bs = os;
-            bi = oi;
-            bg = og;
-        }
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_best[threadIdx.x >> 6] = bs;
-        s_besti[threadIdx.x >> 6] = bi;
-        s_bestg[threadIdx.x >> 6] = bg;
-    }
-    __syncthreads();
+    block_best<B, false>(bs, bi, bg, s_best, s_besti, s_bestg);
     if (threadIdx.x >= 64) return;
-    bs = s_best[0];
-    bi = s_besti[0];
-    bg = s_bestg[0];
-#pragma unroll
-    for (int w = 1; w < B / 64; w++) {
-        const double os = s_best[w];
-        const int og = s_bestg[w];
-        if (os > bs || (os == bs && og < bg)) {
-            bs = os;
-            bi = s_besti[w];
-            bg = og;
-        }
-    }
-    const int win = bi == 0x7fffffff ? 0 : bi;  // (no contender at all -- every score NaN: hypothesis 0, as refine_pick_winner)
-    const double win_score = bi == 0x7fffffff ? a.scores[0] : bs;
+    const int win = bi == BEST_NONE ? 0 : bi;  // (no contender at all -- every score NaN: hypothesis 0, as refine_pick_winner)
+    const double win_score = bi == BEST_NONE ? a.scores[0] : bs;
     const int lane = threadIdx.x;
     const double status = !chain_ok ? 5.0 : __shfl(rec_pre, 33);
     if (!chain_ok) {  // the other stream never reported: nothing here can be trusted -- the host runs the call again, serially (status 5)
@@ -1285,32 +1172,9 @@ __device__ __forceinline__ void rescore_body(KArgs& a) {
     const int n = a.N;
     const int P = a.H * a.W;
     const Cam cam = make_cam(a);
-    for (int c = blockIdx.x; c < n; c += gridDim.x) {
-        const int h = c;
-        const int e = expert_of(a, h);
-        const float* __restrict__ mx = a.sc + (size_t)e * 3 * P;
-        const double* hp = a.hyps + (size_t)h * 6;
-        const double t[3] = {hp[3], hp[4], hp[5]};
-        double R[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) R[k] = a.hyps_R[(size_t)h * 9 + k];
-        double acc[1] = {0};
-        for (int i = threadIdx.x; i < P; i += B) {
-            const int row = i / a.W, col = i - row * a.W;
-            float err = project_exact_err(R, t, cam, mx[i], mx[P + i], mx[2 * P + i], cell_px(a, col), cell_py(a, row));
-            if (STRICT) err = a.max_reproj < err ? a.max_reproj : err;  // std::min(l, maxReproj) = (maxReproj < l) ? maxReproj : l
-            else        err = err < a.max_reproj ? err : a.max_reproj;  // std::min(l, maxReproj), esac_util.h:358
-            acc[0] += soft_inlier_exact(err, a.tau, a.beta);
-        }
-        block_sum<1, B>(acc, s_part, s_tot);
-        if (threadIdx.x == 0) {
-            const float scale = a.alpha / a.W / a.H;
-            double s = acc[0];
-            s *= scale;  // double *= float
-            a.scores[h] = s;
-            if (a.scores_user) a.scores_user[user_slot(a, h)] = s;
-            a.exact_flag[h] = 1;
-        }
+    for (int h = blockIdx.x; h < n; h += gridDim.x) {
+        const double sum = block_exact_score<B, STRICT>(a, h, cam, P, 0, P, s_part, s_tot);
+        if (threadIdx.x == 0) store_score(a, h, exact_score_scaled(sum, a.alpha, a.W, a.H), 1);
         __syncthreads();
     }
 }
@@ -1326,51 +1190,22 @@ __global__ __launch_bounds__(B) void k_rescore_strict(KArgs a) {
 
 // softMax / entropy (esac_util.h:461-497) over the EXACT scores of all N hypotheses (ESAC_FLAG_EXACT_SCORES: k_rescore
 // has scored every hypothesis in reference arithmetic, all of them are contenders): max, sum exp(s - max), entropy.
-template <int B>
-__global__ __launch_bounds__(B) void k_stats_exact(KArgs a) {
-    __shared__ double s_part[2 * (B / 64)];
-    __shared__ double s_tot[2];
-    __shared__ double s_max[B / 64];
-    frame_view(a);
-    double m = -INFINITY;
-    for (int i = threadIdx.x; i < a.N; i += B) m = fmax(m, a.scores[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = s_max[0];
-#pragma unroll
-    for (int k = 1; k < B / 64; k++) m = fmax(m, s_max[k]);
-    double acc[2] = {0, 0};
-    for (int i = threadIdx.x; i < a.N; i += B) {
-        const double d = a.scores[i] - m;
-        const double ex = exp(d);
-        acc[0] += ex;
-        acc[1] += ex * d;
-    }
-    block_sum<2, B>(acc, s_part, s_tot);
-    if (threadIdx.x == 0) {
-        a.n_contenders[0] = a.N;
-        a.stats[0] = m;
-        a.stats[1] = acc[0];
-        a.stats[2] = log2(acc[0]) - acc[1] / (acc[0] * 0.6931471805599453);  // -sum p log2 p, p = exp(d) / S
-    }
-}
-
-// ESAC_FLAG_STRICT_REFERENCE: the same statistics, and the reference's behaviour when a score is NaN (k_rescore_strict lets a
-// non-finite coordinate through).  softMax (esac_util.h:461-481) then divides by a NaN sum: EVERY probability is NaN, whichever
-// hypothesis the NaN came from; entropy (`dist > 0` is false) is 0; draw (`prob < EPS` and `prob > maxProb` are false) keeps
-// index 0.  Here: stats = (NaN, NaN, 0), which makes the record's probability NaN, and hypothesis 0 is left as the only
+// STRICT (ESAC_FLAG_STRICT_REFERENCE): the same statistics, and the reference's behaviour when a score is NaN (k_rescore_strict
+// lets a non-finite coordinate through).  softMax (esac_util.h:461-481) then divides by a NaN sum: EVERY probability is NaN,
+// whichever hypothesis the NaN came from; entropy (`dist > 0` is false) is 0; draw (`prob < EPS` and `prob > maxProb` are false)
+// keeps index 0.  Here: stats = (NaN, NaN, 0), which makes the record's probability NaN, and hypothesis 0 is left as the only
 // contender (exact_flag), so that the refinement's argmax -- which never picks a NaN -- returns it.
-template <int B>
-__global__ __launch_bounds__(B) void k_stats_strict(KArgs a) {
+template <int B, bool STRICT>
+__device__ __forceinline__ void stats_body(KArgs& a) {
     __shared__ double s_part[2 * (B / 64)];
     __shared__ double s_tot[2];
     __shared__ double s_max[B / 64];
     __shared__ int s_nan;
     frame_view(a);
-    if (threadIdx.x == 0) s_nan = 0;
-    __syncthreads();
+    if (STRICT) {
+        if (threadIdx.x == 0) s_nan = 0;
+        __syncthreads();
+    }
     double m = -INFINITY;
     bool nan = false;
     for (int i = threadIdx.x; i < a.N; i += B) {
@@ -1378,37 +1213,25 @@ __global__ __launch_bounds__(B) void k_stats_strict(KArgs a) {
         nan |= sc != sc;
         m = fmax(m, sc);
     }
-    if (nan) s_nan = 1;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (s_nan) {  // (workgroup-uniform)
+    if (STRICT && nan) s_nan = 1;
+    m = block_max<B>(m, s_max);
+    if (STRICT && s_nan) {  // (workgroup-uniform)
         for (int i = threadIdx.x; i < a.N; i += B) a.exact_flag[i] = i == 0 ? 1 : 0;
-        if (threadIdx.x == 0) {
-            a.n_contenders[0] = a.N;
-            a.stats[0] = a.stats[1] = __builtin_nan("");
-            a.stats[2] = 0.0;
-        }
+        if (threadIdx.x == 0) write_stats(a, a.N, __builtin_nan(""), __builtin_nan(""), 0.0);
         return;
     }
-    m = s_max[0];
-#pragma unroll
-    for (int k = 1; k < B / 64; k++) m = fmax(m, s_max[k]);
     double acc[2] = {0, 0};
-    for (int i = threadIdx.x; i < a.N; i += B) {
-        const double d = a.scores[i] - m;
-        const double ex = exp(d);
-        acc[0] += ex;
-        acc[1] += ex * d;
-    }
+    for (int i = threadIdx.x; i < a.N; i += B) softmax_add(acc[0], acc[1], a.scores[i], m);
     block_sum<2, B>(acc, s_part, s_tot);
-    if (threadIdx.x == 0) {
-        a.n_contenders[0] = a.N;
-        a.stats[0] = m;
-        a.stats[1] = acc[0];
-        a.stats[2] = log2(acc[0]) - acc[1] / (acc[0] * 0.6931471805599453);  // -sum p log2 p, p = exp(d) / S
-    }
+    if (threadIdx.x == 0) write_stats(a, a.N, m, acc[0], entropy_bits(acc[0], acc[1]));
+}
+template <int B>
+__global__ __launch_bounds__(B) void k_stats_exact(KArgs a) {
+    stats_body<B, false>(a);
+}
+template <int B>
+__global__ __launch_bounds__(B) void k_stats_strict(KArgs a) {
+    stats_body<B, true>(a);
 }
 
 // Multi-GPU: the all-reduced exchange buffer ends with one 32-double record per rank (zero where a rank had no

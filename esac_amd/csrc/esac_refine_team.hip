@@ -257,39 +257,21 @@ __device__ __forceinline__ int team_select(const KArgs& a, const float fs, const
     const int P = a.H * a.W;
     // fp32 maximum (NaN-ignoring) and the band of contenders (fs: this thread's hypothesis' fp32 score, -inf beyond N -- loaded by the
     // caller with the first trip to memory of the kernel)
-    float m = fs;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    float* s_maxf = reinterpret_cast<float*>(s_best);
-    if (lane == 0) s_maxf[wave] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(s_maxf[0], s_maxf[1]), fmaxf(s_maxf[2], s_maxf[3]));
+    const float m = block_max<B>(fs, reinterpret_cast<float*>(s_best));
     const float band = m - a.margin;
     const bool cont = t < a.N && fs >= band;
     // softmax statistics (esac_util.h:461-497) from the fp32-path scores, in double; number of contenders
     double acc[3] = {0, 0, 0};
     if (t < a.N) {
-        const double d = (double)fs - (double)m;
-        const double ex = exp(d);
-        acc[0] = ex;
-        acc[1] = ex * d;
+        softmax_add(acc[0], acc[1], (double)fs, (double)m);
         acc[2] = cont ? 1.0 : 0.0;
     }
     block_sum<3, B>(acc, s_part, s_tot);
     const int nc = (int)acc[2];
     nc_out = nc;
-    const double entropy = log2(acc[0]) - acc[1] / (acc[0] * 0.6931471805599453);  // -sum p log2 p, p = exp(d) / S
-    if (writer && t == 0) {
-        a.n_contenders[0] = nc;
-        a.stats[0] = (double)m;
-        a.stats[1] = acc[0];
-        a.stats[2] = entropy;
-    }
-    if (writer && t < a.N && !cont) {
-        a.scores[t] = (double)fs;
-        if (a.scores_user) a.scores_user[user_slot(a, t)] = (double)fs;
-        a.exact_flag[t] = 0;
-    }
+    const double entropy = entropy_bits(acc[0], acc[1]);
+    if (writer && t == 0) write_stats(a, nc, (double)m, acc[0], entropy);
+    if (writer && t < a.N && !cont) store_score(a, t, (double)fs, 0);
     // the contenders, ascending
     int* s_wcnt = s_besti;
     const unsigned long long bal = __ballot(cont);
@@ -303,8 +285,7 @@ __device__ __forceinline__ int team_select(const KArgs& a, const float fs, const
     __syncthreads();
     // exact re-score, TEAM_SEL_CHUNK contenders per exchange: every member its cells, reference arithmetic op by op
     double bs = -INFINITY;
-    int bi = 0x7fffffff, bg = 0x7fffffff;
-    const float scale = a.alpha / a.W / a.H;  // float / int / int (esac_util.h:256)
+    int bi = BEST_NONE, bg = BEST_NONE;
     for (int c0 = 0; c0 < nc; c0 += TEAM_SEL_CHUNK) {
         const int cnt = nc - c0 < TEAM_SEL_CHUNK ? nc - c0 : TEAM_SEL_CHUNK;
         if (t < cnt * 12) {  // R as the sampler formed it (hyps_R), t: 12 values per contender
@@ -333,9 +314,7 @@ __device__ __forceinline__ int team_select(const KArgs& a, const float fs, const
                     X = mx[i]; Y = mx[P + i]; Z = mx[2 * P + i];
                     px = (float)cell_pxi(a, col); py = (float)cell_pyi(a, row);
                 }
-                float err = project_exact_err(R, tv, cam, X, Y, Z, px, py);
-                err = err < a.max_reproj ? err : a.max_reproj;  // std::min(l, maxReproj), esac_util.h:358
-                v += soft_inlier_exact(err, a.tau, a.beta);
+                v += exact_cell_term<false>(R, tv, cam, X, Y, Z, px, py, a.max_reproj, a.tau, a.beta);
             }
             v = wave_sum(v);
             if (lane == 0) s_part[wave * 28 + ci] = v;
@@ -347,59 +326,18 @@ __device__ __forceinline__ int team_select(const KArgs& a, const float fs, const
         if (co.dead) break;
         if (t < cnt) {
             const int h = s_list[c0 + t];
-            double sc = s_tot[t];
-            sc *= scale;  // double *= float
-            if (writer) {
-                a.scores[h] = sc;
-                if (a.scores_user) a.scores_user[user_slot(a, h)] = sc;
-                a.exact_flag[h] = 1;
-            }
-            const int g = global_hyp(a, h);
-            if (sc > bs || (sc == bs && g < bg)) {  // (one contender per thread and chunk: ascending h, so only `>` ever fires)
-                bs = sc;
-                bi = h;
-                bg = g;
-            }
+            const double sc = exact_score_scaled(s_tot[t], a.alpha, a.W, a.H);
+            if (writer) store_score(a, h, sc, 1);
+            best_take(bs, bi, bg, sc, h, global_hyp(a, h));  // (one contender per thread and chunk: ascending h, so only `>` ever fires)
         }
         __syncthreads();  // s_rt / s_part / s_tot are rewritten by the next chunk
     }
     // draw(probs, training=false): argmax of the exact scores, first (global) index on ties (esac_util.h:512-529)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double os = __shfl_xor(bs, o);
-        const int oi = __shfl_xor(bi, o);
-        const int og = __shfl_xor(bg, o);
-        if (os > bs || (os == bs && og < bg)) {
-            bs = os;
-            bi = oi;
-            bg = og;
-        }
-    }
-    __syncthreads();
-    if (lane == 0) {
-        s_best[wave] = bs;
-        s_besti[wave] = bi;
-        s_bestg[wave] = bg;
-    }
-    __syncthreads();
-    bs = s_best[0];
-    bi = s_besti[0];
-    bg = s_bestg[0];
-#pragma unroll
-    for (int w = 1; w < B / 64; w++) {
-        const double os = s_best[w];
-        const int oi = s_besti[w];
-        const int og = s_bestg[w];
-        if (os > bs || (os == bs && og < bg)) {
-            bs = os;
-            bi = oi;
-            bg = og;
-        }
-    }
-    const int win = bi == 0x7fffffff ? 0 : bi;
+    block_best<B, true>(bs, bi, bg, s_best, s_besti, s_bestg);
+    const int win = bi == BEST_NONE ? 0 : bi;
     // the winner's score: a contender's exact one; with no contender at all (every score NaN) what the selection kernel
     // leaves in scores[0]
-    win_score = bi == 0x7fffffff ? (double)a.fast_scores[0] : bs;
+    win_score = bi == BEST_NONE ? (double)a.fast_scores[0] : bs;
     rec_in = RecordInputs{exp(win_score - (double)m) / acc[0], entropy, a.status[0]};
     return win;
 }
@@ -411,70 +349,24 @@ __device__ __forceinline__ int team_select(const KArgs& a, const float fs, const
 __device__ __forceinline__ int team_select_exact(const KArgs& a, const double sc, bool writer, double* s_part, double* s_tot, double* s_best, int* s_besti,
                                                  int* s_bestg, double& win_score, int& nc_out, RecordInputs& rec_in) {
     constexpr int B = REFINE_B;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    double m = sc;  // (sc: this thread's hypothesis' exact score, -inf beyond N)  fmax ignores NaN, as k_stats_exact
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
-    if (lane == 0) s_best[wave] = m;
-    __syncthreads();
-    m = fmax(fmax(s_best[0], s_best[1]), fmax(s_best[2], s_best[3]));
+    const int t = threadIdx.x;
+    const double m = block_max<B>(sc, s_best);  // (sc: this thread's hypothesis' exact score, -inf beyond N)  NaN-ignoring, as k_stats_exact
     double acc[2] = {0, 0};
-    if (t < a.N) {
-        const double d = sc - m;
-        const double ex = exp(d);
-        acc[0] = ex;
-        acc[1] = ex * d;
-    }
+    if (t < a.N) softmax_add(acc[0], acc[1], sc, m);
     block_sum<2, B>(acc, s_part, s_tot);
-    const double entropy = log2(acc[0]) - acc[1] / (acc[0] * 0.6931471805599453);  // -sum p log2 p, p = exp(d) / S
+    const double entropy = entropy_bits(acc[0], acc[1]);
     nc_out = a.N;
-    if (writer && t == 0) {
-        a.n_contenders[0] = a.N;
-        a.stats[0] = m;
-        a.stats[1] = acc[0];
-        a.stats[2] = entropy;
-    }
+    if (writer && t == 0) write_stats(a, a.N, m, acc[0], entropy);
     double bs = t < a.N ? sc : -INFINITY;
-    int bi = t < a.N && sc > -INFINITY ? t : 0x7fffffff, bg = bi == 0x7fffffff ? 0x7fffffff : global_hyp(a, t);
+    int bi = t < a.N && sc > -INFINITY ? t : BEST_NONE, bg = bi == BEST_NONE ? BEST_NONE : global_hyp(a, t);
     if (!(bs > -INFINITY)) {  // NaN or -inf: never the maximum (refine_pick_winner: `s > bs` is false for it)
         bs = -INFINITY;
-        bi = bg = 0x7fffffff;
+        bi = bg = BEST_NONE;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double os = __shfl_xor(bs, o);
-        const int oi = __shfl_xor(bi, o);
-        const int og = __shfl_xor(bg, o);
-        if (os > bs || (os == bs && og < bg)) {
-            bs = os;
-            bi = oi;
-            bg = og;
-        }
-    }
-    __syncthreads();
-    if (lane == 0) {
-        s_best[wave] = bs;
-        s_besti[wave] = bi;
-        s_bestg[wave] = bg;
-    }
-    __syncthreads();
-    bs = s_best[0];
-    bi = s_besti[0];
-    bg = s_bestg[0];
-#pragma unroll
-    for (int w = 1; w < B / 64; w++) {
-        const double os = s_best[w];
-        const int oi = s_besti[w];
-        const int og = s_bestg[w];
-        if (os > bs || (os == bs && og < bg)) {
-            bs = os;
-            bi = oi;
-            bg = og;
-        }
-    }
-    const int win = bi == 0x7fffffff ? 0 : bi;
+    block_best<B, true>(bs, bi, bg, s_best, s_besti, s_bestg);
+    const int win = bi == BEST_NONE ? 0 : bi;
     // the winner's score: the maximum found (no second trip to memory); with no score above -inf at all what hypothesis 0 holds
-    win_score = bi == 0x7fffffff ? a.scores[0] : bs;
+    win_score = bi == BEST_NONE ? a.scores[0] : bs;
     rec_in = RecordInputs{exp(win_score - m) / acc[0], entropy, a.status[0]};
     return win;
 }

@@ -11,6 +11,7 @@
 #include "bwd_math.hpp"
 #include "lm_math.hpp"
 #include "pose_math.hpp"
+#include "select_math.hpp"
 
 namespace esac {
 
@@ -441,51 +442,14 @@ __device__ __forceinline__ void team_collect(double (&v)[NV], Coop& co, double* 
 // Every thread returns the winner's (local) hypothesis index; contains a workgroup barrier.
 template <int B>
 __device__ __forceinline__ int refine_pick_winner(const KArgs& a, double* s_best, int* s_besti, int* s_bestg) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double bs = -INFINITY;
-    int bi = 0x7fffffff, bg = 0x7fffffff;
+    int bi = BEST_NONE, bg = BEST_NONE;
     for (int h = threadIdx.x; h < a.N; h += B) {
         if (!a.exact_flag[h]) continue;  // contenders = the hypotheses that were re-scored exactly
-        const int g = global_hyp(a, h);
-        const double s = a.scores[h];
-        if (s > bs || (s == bs && g < bg)) {
-            bs = s;
-            bi = h;
-            bg = g;
-        }
+        best_take(bs, bi, bg, a.scores[h], h, global_hyp(a, h));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double os = __shfl_xor(bs, o);
-        const int oi = __shfl_xor(bi, o);
-        const int og = __shfl_xor(bg, o);
-        if (os > bs || (os == bs && og < bg)) {
-            bs = os;
-            bi = oi;
-            bg = og;
-        }
-    }
-    if (lane == 0) {
-        s_best[wave] = bs;
-        s_besti[wave] = bi;
-        s_bestg[wave] = bg;
-    }
-    __syncthreads();
-    bs = s_best[0];
-    bi = s_besti[0];
-    bg = s_bestg[0];
-#pragma unroll
-    for (int w = 1; w < B / 64; w++) {
-        const double os = s_best[w];
-        const int oi = s_besti[w];
-        const int og = s_bestg[w];
-        if (os > bs || (os == bs && og < bg)) {
-            bs = os;
-            bi = oi;
-            bg = og;
-        }
-    }
-    return bi == 0x7fffffff ? 0 : bi;
+    block_best<B, false>(bs, bi, bg, s_best, s_besti, s_bestg);
+    return bi == BEST_NONE ? 0 : bi;
 }
 
 // ---- speculative forward (KArgs::spec_mode, esac_kernels.hip: k_spec_join)
@@ -538,59 +502,21 @@ __device__ __forceinline__ bool spec_nothing_to_refine(const KArgs& a, int win, 
 // near-equal scores differently).  Every thread returns the (local) index, 0x7fffffff: none.  Contains a workgroup barrier.
 template <int B>
 __device__ __forceinline__ int spec_pick_fast_but(const KArgs& a, int skip, double* s_best, int* s_besti, int* s_bestg) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float bs = -INFINITY;
-    int bi = 0x7fffffff, bg = 0x7fffffff;
+    int bi = BEST_NONE, bg = BEST_NONE;
     for (int h = threadIdx.x; h < a.N; h += B) {
         if (a.spec_flag[h] || h == skip) continue;
-        const float s = a.fast_scores[h];
-        const int g = global_hyp(a, h);
-        if (s > bs || (s == bs && g < bg)) {  // (NaN: never)
-            bs = s;
-            bi = h;
-            bg = g;
-        }
+        best_take(bs, bi, bg, a.fast_scores[h], h, global_hyp(a, h));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float os = __shfl_xor(bs, o);
-        const int oi = __shfl_xor(bi, o);
-        const int og = __shfl_xor(bg, o);
-        if (os > bs || (os == bs && og < bg)) {
-            bs = os;
-            bi = oi;
-            bg = og;
-        }
-    }
-    __syncthreads();  // (s_best may still be read: a second pick)
-    if (lane == 0) {
-        s_best[wave] = (double)bs;
-        s_besti[wave] = bi;
-        s_bestg[wave] = bg;
-    }
-    __syncthreads();
-    double ds = s_best[0];
-    bi = s_besti[0];
-    bg = s_bestg[0];
-#pragma unroll
-    for (int w = 1; w < B / 64; w++) {
-        const double os = s_best[w];
-        const int oi = s_besti[w];
-        const int og = s_bestg[w];
-        if (os > ds || (os == ds && og < bg)) {
-            ds = os;
-            bi = oi;
-            bg = og;
-        }
-    }
+    block_best<B, true>(bs, bi, bg, s_best, s_besti, s_bestg);  // (s_best may still be read: a second pick)
     return bi;
 }
 template <int B>
 __device__ __forceinline__ int spec_pick_fast(const KArgs& a, double* s_best, int* s_besti, int* s_bestg) {
     int win = spec_pick_fast_but<B>(a, -1, s_best, s_besti, s_bestg);
-    if (a.spec_debug == 1 && win != 0x7fffffff) {  // ESAC_DEBUG_SPEC_SECOND_BEST (tests): the runner-up, if there is one
+    if (a.spec_debug == 1 && win != BEST_NONE) {  // ESAC_DEBUG_SPEC_SECOND_BEST (tests): the runner-up, if there is one
         const int second = spec_pick_fast_but<B>(a, win, s_best, s_besti, s_bestg);
-        if (second != 0x7fffffff) win = second;
+        if (second != BEST_NONE) win = second;
     }
     return win;
 }

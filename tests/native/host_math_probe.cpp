@@ -5,6 +5,7 @@
 #include "../../esac_amd/csrc/lm_math.hpp"
 #include "../../esac_amd/csrc/bwd_math.hpp"
 #include "../../esac_amd/csrc/lm_lanes.hpp"
+#include "../../esac_amd/csrc/select_math.hpp"
 using namespace esac;
 extern "C" {
 int probe_p3p(const double* obj, const double* img, double fx, double fy, double cx, double cy, double* rvec, double* tvec, double* Rout) {
@@ -143,4 +144,34 @@ int probe_norm_jac_row(const double* rvec, const double* t, float focal, float p
 }
 int probe_inv_spd6(const double* U21, double* Ainv) { return inv_spd6(U21, Ainv) ? 1 : 0; }
 void probe_pinv_sym6(const double* U21, double* Ainv) { pinv_sym6_jacobi(U21, Ainv); }
+// ---- the selection arithmetic (select_math.hpp)
+double probe_exact_cell_term(int strict, const double* R, const double* t, double fx, double fy, double cx, double cy, float X, float Y, float Z,
+                             float px, float py, float max_reproj, float tau, float beta) {
+    Cam cam{fx, fy, cx, cy};
+    double Rm[9], tv[3];
+    for (int k = 0; k < 9; k++) Rm[k] = R[k];
+    for (int k = 0; k < 3; k++) tv[k] = t[k];
+    return strict ? exact_cell_term<true>(Rm, tv, cam, X, Y, Z, px, py, max_reproj, tau, beta)
+                  : exact_cell_term<false>(Rm, tv, cam, X, Y, Z, px, py, max_reproj, tau, beta);
+}
+double probe_exact_score_scaled(double sum, float alpha, int W, int H) { return exact_score_scaled(sum, alpha, W, H); }
+double probe_soft_inlier_exact(float err, float tau, float beta) { return soft_inlier_exact(err, tau, beta); }
+void probe_best_take(double* bs, int* bi, int* bg, double os, int oi, int og) { best_take(*bs, *bi, *bg, os, oi, og); }
+// statistics of n scores around m through softmax_add / entropy_bits; out = (S, T, entropy)
+void probe_softmax_stats(const double* s, int n, double m, double* out) {
+    double S = 0, T = 0;
+    for (int i = 0; i < n; i++) softmax_add(S, T, s[i], m);
+    out[0] = S; out[1] = T; out[2] = entropy_bits(S, T);
+}
+// the same accumulation written out, as every kernel carried it before the helpers existed (the test's reference)
+void probe_softmax_stats_inline(const double* s, int n, double m, double* out) {
+    double acc[2] = {0, 0};
+    for (int i = 0; i < n; i++) {
+        const double d = s[i] - m;
+        const double ex = exp(d);
+        acc[0] += ex;
+        acc[1] += ex * d;
+    }
+    out[0] = acc[0]; out[1] = acc[1]; out[2] = log2(acc[0]) - acc[1] / (acc[0] * 0.6931471805599453);
+}
 }
