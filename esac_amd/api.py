@@ -32,6 +32,7 @@ BUF_REFINE_INFO = 19
 BUF_BWD_TEAM_INFO = 20
 BUF_SPEC_INFO = 21
 BUF_SPEC_FLAGS = 22
+BUF_BWD_MAPS = 23
 REFINE_TEAM_MAX, REFINE_TEAM_EIGHT, REFINE_TEAM_AUTO = 32, 8, -1
 REFINE_TEAM_DEFAULT = REFINE_TEAM_AUTO  # what a fresh context does: 8 members, or the smallest team <= 16 that lowers the cells per lane
 MAX_REF_STEPS = 100
@@ -509,6 +510,14 @@ class Engine:
         _, H, W = self._shape
         out = np.zeros((int(k), 3, H, W), np.float64)
         _check(self.lib.esac_hip_read(self.ctx, which, out.ctypes.data_as(C.c_void_p), out.nbytes), self.lib)
+        return out
+
+    def read_maps(self, k):
+        """Both inlier-map buffers [k,2,H*W] (uint8, cells as y * W + x) of the first k slots of the last blocking backward call
+        (BUF_BWD_MAPS); BUF_BWD_SLOT_INFO[s][0] names the one holding slot s's last accepted inlier set (-1: neither)."""
+        _, H, W = self._shape
+        out = np.zeros((int(k), 2, H * W), np.uint8)
+        _check(self.lib.esac_hip_read(self.ctx, BUF_BWD_MAPS, out.ctypes.data_as(C.c_void_p), out.nbytes), self.lib)
         return out
 
     def read(self, which):

@@ -1684,6 +1684,17 @@ extern "C" int esac_hip_read(esac_hip_ctx* c, int which, void* h_dst, size_t byt
             want = bytes;
             break;
         }
+        case ESAC_BUF_BWD_MAPS: {
+            // [slots,2,P] bytes: both map buffers of each slot, read in whole slots like the slabs (k = bytes / (2 P))
+            const size_t pair = 2 * P;
+            const size_t cap = c->last_bwd_batch_cap > 0 ? (size_t)c->last_bwd_batch_cap : (size_t)c->bslots;
+            src = c->bws.maps;
+            if (!src || pair == 0) return fail(-6, "esac_hip_read: buffer %d is empty (no backward call has run yet)", which);
+            if (bytes == 0 || bytes % pair || bytes / pair > cap)
+                return fail(-7, "esac_hip_read: buffer %d is read in whole slots of %zu bytes, at most %zu", which, pair, cap);
+            want = bytes;
+            break;
+        }
         default: return fail(-5, "esac_hip_read: unknown buffer id %d", which);
     }
     // after a batched training call the per-frame buffers above hold its (last chunk's) frames frame-major: B x the size reads them all

@@ -209,6 +209,9 @@ enum {
                                       the true winner), [2] 1 when the most recent forward call was speculative, [3] 1 when its
                                       speculation failed */
     ESAC_BUF_SPEC_FLAGS = 22,      /* uint8[N] after a speculative call: 1 where the sampler's first pass left the hypothesis to the straggler chain */
+    ESAC_BUF_BWD_MAPS = 23,        /* uint8[k,2,H*W] the two inlier-map buffers of the first k slots of the most recent blocking
+                                      esac_hip_backward, cells as y * W + x; ESAC_BUF_BWD_SLOT_INFO[s][0] names the one that holds the
+                                      last accepted inlier set of slot s (-1: neither); k = bytes / (2*H*W) <= #slots             */
     ESAC_BUF_REFINE_INFO = 19      /* int32[8] how the most recent winner refinement ran (refineHyp, esac_util.h:378-454):
                                       [0] 0 one workgroup, 1 cooperating workgroups (grids beyond one LDS list), 2 a team on
                                       one XCD (small grids); [1] workgroups sharing it; [2] XCD census of a team: byte x = members

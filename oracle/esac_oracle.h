@@ -102,10 +102,46 @@ typedef struct esac_oracle_bwd_args {
     double* out_entropy;       /* [1] */
     double* out_grad_path1;    /* [N,H*W,3] gradients[h] before the probability weight (esac.cpp:456-463) */
     double* out_grad_path2;    /* [N,H*W,3] dLoss_dScore_dObjs[h] (esac.cpp:472-486) */
+    /* of the upstream stages (esac_oracle_backward only) */
+    double* out_scores;        /* [N] */
+    uint8_t* out_maps;         /* [N,H*W] inlier map of the last accepted re-fit, (y,x); zero where none        */
+    uint8_t* out_have_map;     /* [N] 1 where a re-fit was accepted (inlierMaps[h] is not an empty Mat)          */
+    int32_t* out_ref_steps;    /* [N] accepted re-fits                                                           */
+    int32_t* out_ref_inliers;  /* [N] inliers of the last accepted re-fit (0: none)                              */
+    int32_t* out_ref_lm_iters; /* [N] LM iterations over all re-fits                                             */
+    /* of the two gradient paths (esac_oracle_backward and esac_oracle_backward_paths) */
+    int32_t* out_path1_state;  /* [N] -1 p < PROB_THRESH, 0 computed, 1 no map, 2 fewer than 4 inliers, 3 dropped: |jacobeanR| > 10 */
+    double* out_jtj;           /* [N,36] J^T J of path I (states 0 and 3 only)                                   */
+    double* out_jr_max;        /* [N] largest |jacobeanR| entry BEFORE the clamp (states 0 and 3 only)           */
+    int32_t* out_dpnp_state;   /* [N] -1 p < PROB_THRESH, 0 kept, 1 dropped: a solve failed / NaN, 2 dropped: an entry > 10 */
+    double* out_dpnp;          /* [N,72] the 6x12 dPNP matrix as path II used it (zero when dropped)             */
+    double* out_dpnp_max;      /* [N] its largest |entry| BEFORE the clamp                                       */
+    double* out_grad_direct;   /* [N,H*W,3] path II without the support terms of the four sampled cells          */
+    double* out_support;       /* [N,12] those support terms, (sampled point, axis)                              */
+    double* out_support_raw;   /* [N,12] what they would be had the > 10 clamp not dropped the dPNP matrix       */
 } esac_oracle_bwd_args;
 
 /* returns the expected loss (>= 0) or -1 on argument error */
 double esac_oracle_backward(esac_oracle_bwd_args* b);
+
+/* The upstream stages of esac_backward that its two gradient paths and the assembly read (esac.cpp:276-362). */
+typedef struct esac_oracle_bwd_stages {
+    const double* init_hyps;   /* [N,6] */
+    const double* ref_hyps;    /* [N,6] */
+    const int32_t* sample_xy;  /* [N,4,2] */
+    const double* probs;       /* [N] */
+    const double* losses;      /* [N] */
+    const uint8_t* have_map;   /* [N] */
+    const uint8_t* maps;       /* [N,H*W] */
+    /* optional: values to use INSTEAD of the ones this text derives from the stages above (a replay of another
+     * implementation's stages isolates one kernel at a time); out_score_grads still reports the derived value */
+    const double* score_grads; /* [N] feeds path II */
+    const double* dloss;       /* [N,6] feeds path I */
+} esac_oracle_bwd_stages;
+
+/* Path I, path II and the assembly (esac.cpp:375-508) on GIVEN stages: the second half of esac_oracle_backward, the same text.
+ * `b`: inputs, ground truth, out_gradients (+=) and the optional outputs of the paths.  returns 0, or -1 on argument error */
+int esac_oracle_backward_paths(esac_oracle_bwd_args* b, const esac_oracle_bwd_stages* st);
 
 /* ---- building blocks exported for known-answer tests ---- */
 void esac_oracle_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
@@ -134,6 +170,7 @@ void esac_oracle_pinv_sym6(const double A[36], double Ainv[36]);
 double esac_oracle_pose_loss(const double pose[6], const double gt_trans[16], double wRot, double wTrans, double cut);
 void esac_oracle_pose_dloss(const double est[6], const double gt_pose[6], double wRot, double wTrans, double cut, double jac[6]);
 void esac_oracle_trans2pose(const double T[16], double pose[6]);
+void esac_oracle_soft_max(const double* scores, int n, double* probs); /* softMax (esac_util.h), as esac_backward calls it */
 void esac_oracle_dproject_dobj(float ptx, float pty, float ox, float oy, float oz, const double rvec[3], const double t[3],
                                float focal, float ppx, float ppy, float maxReproj, double out[3]);
 int esac_oracle_norm_jac_row(const double rvec[3], const double t[3], float focal, float ppx, float ppy, float X, float Y,

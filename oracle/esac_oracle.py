@@ -178,29 +178,25 @@ class _BwdArgs(C.Structure):
         ("out_ref_hyps", C.c_void_p), ("out_score_grads", C.c_void_p), ("out_dloss", C.c_void_p),
         ("out_sample_xy", C.c_void_p), ("out_entropy", C.c_void_p), ("out_grad_path1", C.c_void_p),
         ("out_grad_path2", C.c_void_p),
+        ("out_scores", C.c_void_p), ("out_maps", C.c_void_p), ("out_have_map", C.c_void_p), ("out_ref_steps", C.c_void_p),
+        ("out_ref_inliers", C.c_void_p), ("out_ref_lm_iters", C.c_void_p),
+        ("out_path1_state", C.c_void_p), ("out_jtj", C.c_void_p), ("out_jr_max", C.c_void_p), ("out_dpnp_state", C.c_void_p),
+        ("out_dpnp", C.c_void_p), ("out_dpnp_max", C.c_void_p), ("out_grad_direct", C.c_void_p), ("out_support", C.c_void_p),
+        ("out_support_raw", C.c_void_p),
     ]
 
 
-def backward(scene_coords, out_gradients, hyp_assign, gt_pose, w_rot=1.0, w_trans=100.0, loss_cut=100.0,
-             shift_x=0, shift_y=0, focal=525.0, ppx=320.0, ppy=240.0, inlier_thresh=10.0, inlier_alpha=100.0,
-             inlier_beta=0.5, max_reproj=100.0, sub_sampling=8, seed=1305, call=0, max_tries=0, max_ref_steps=-1,
-             num_threads=0, irand=None, hyp_index=None, want_paths=False):
-    """Oracle restatement of esac.backward (esac.cpp:213-230): accumulates into `out_gradients` (float32 ndarray
-    [E,3,H,W], +=) and returns a dict with the expected loss and the stage outputs."""
-    sc = np.asarray(scene_coords)
-    ha = np.asarray(hyp_assign)
-    og = out_gradients
-    gt = np.ascontiguousarray(gt_pose, np.float32).reshape(16)
+class _BwdStages(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("init_hyps", "ref_hyps", "sample_xy", "probs", "losses", "have_map", "maps",
+                                          "score_grads", "dloss")]
+
+
+def _bwd_args(sc, og, ha, gt, w_rot, w_trans, loss_cut, shift_x, shift_y, focal, ppx, ppy, inlier_thresh, inlier_alpha,
+              inlier_beta, max_reproj, sub_sampling, seed, call, max_tries, max_ref_steps, num_threads, irand, hyp_index):
+    """The argument block shared by backward and backward_paths; returns it with the objects that must outlive the call."""
     assert sc.dtype == np.float32 and sc.ndim == 4 and og.dtype == np.float32 and og.shape == sc.shape
     assert ha.dtype == np.int64 and ha.ndim == 1
     E, _, H, W = sc.shape
-    N = ha.shape[0]
-    out = dict(probs=np.zeros(N), losses=np.zeros(N), init_hyps=np.zeros((N, 6)), ref_hyps=np.zeros((N, 6)),
-               score_grads=np.zeros(N), dloss=np.zeros((N, 6)), sample_xy=np.zeros((N, 4, 2), np.int32),
-               entropy=np.zeros(1))
-    if want_paths:
-        out["grad_path1"] = np.zeros((N, H * W, 3))
-        out["grad_path2"] = np.zeros((N, H * W, 3))
     b = _BwdArgs()
     a = b.fwd
     a.scene_coords = _p(sc)
@@ -210,7 +206,7 @@ def backward(scene_coords, out_gradients, hyp_assign, gt_pose, w_rot=1.0, w_tran
     a.E, a.H, a.W = E, H, W
     a.hyp_assign = _p(ha)
     a.assign_stride = ha.strides[0] // 8
-    a.N = N
+    a.N = ha.shape[0]
     a.shift_x, a.shift_y = int(shift_x), int(shift_y)
     a.focal, a.ppx, a.ppy = float(focal), float(ppx), float(ppy)
     a.inlier_thresh, a.inlier_alpha = float(inlier_thresh), float(inlier_alpha)
@@ -230,6 +226,41 @@ def backward(scene_coords, out_gradients, hyp_assign, gt_pose, w_rot=1.0, w_tran
     b.gt_pose = _p(gt)
     b.w_rot, b.w_trans, b.loss_cut = float(w_rot), float(w_trans), float(loss_cut)
     b.out_gradients = _p(og)
+    return b, (cb, hi, gt)
+
+
+def _path_outputs(N, P):
+    """The optional per-path outputs (want_paths): slabs, the split of path II, and what decided the workgroup-uniform branches."""
+    return dict(grad_path1=np.zeros((N, P, 3)), grad_path2=np.zeros((N, P, 3)), grad_direct=np.zeros((N, P, 3)),
+                support=np.zeros((N, 4, 3)), support_raw=np.zeros((N, 4, 3)), path1_state=np.zeros(N, np.int32), jtj=np.zeros((N, 6, 6)), jr_max=np.zeros(N),
+                dpnp_state=np.zeros(N, np.int32), dpnp=np.zeros((N, 6, 12)), dpnp_max=np.zeros(N))
+
+
+def backward(scene_coords, out_gradients, hyp_assign, gt_pose, w_rot=1.0, w_trans=100.0, loss_cut=100.0,
+             shift_x=0, shift_y=0, focal=525.0, ppx=320.0, ppy=240.0, inlier_thresh=10.0, inlier_alpha=100.0,
+             inlier_beta=0.5, max_reproj=100.0, sub_sampling=8, seed=1305, call=0, max_tries=0, max_ref_steps=-1,
+             num_threads=0, irand=None, hyp_index=None, want_paths=False, want_stages=False):
+    """Oracle restatement of esac.backward (esac.cpp:213-230): accumulates into `out_gradients` (float32 ndarray
+    [E,3,H,W], +=) and returns a dict with the expected loss and the stage outputs.
+    want_paths: also the two gradient paths per hypothesis, the split of path II and the branch each path took.
+    want_stages: also scores, the inlier maps (uint8 [N,H*W]), have_map, accepted re-fits, inliers of the last accepted
+    re-fit and LM iterations per hypothesis -- everything backward_paths takes."""
+    sc = np.asarray(scene_coords)
+    ha = np.asarray(hyp_assign)
+    og = out_gradients
+    gt = np.ascontiguousarray(gt_pose, np.float32).reshape(16)
+    b, keep = _bwd_args(sc, og, ha, gt, w_rot, w_trans, loss_cut, shift_x, shift_y, focal, ppx, ppy, inlier_thresh, inlier_alpha,
+                        inlier_beta, max_reproj, sub_sampling, seed, call, max_tries, max_ref_steps, num_threads, irand, hyp_index)
+    E, _, H, W = sc.shape
+    N = ha.shape[0]
+    out = dict(probs=np.zeros(N), losses=np.zeros(N), init_hyps=np.zeros((N, 6)), ref_hyps=np.zeros((N, 6)),
+               score_grads=np.zeros(N), dloss=np.zeros((N, 6)), sample_xy=np.zeros((N, 4, 2), np.int32),
+               entropy=np.zeros(1))
+    if want_paths:
+        out.update(_path_outputs(N, H * W))
+    if want_stages:
+        out.update(scores=np.zeros(N), maps=np.zeros((N, H * W), np.uint8), have_map=np.zeros(N, np.uint8),
+                   ref_steps=np.zeros(N, np.int32), ref_inliers=np.zeros(N, np.int32), ref_lm_iters=np.zeros(N, np.int32))
     for k in out:
         setattr(b, "out_" + k, _p(out[k]))
     L = lib()
@@ -240,6 +271,48 @@ def backward(scene_coords, out_gradients, hyp_assign, gt_pose, w_rot=1.0, w_tran
         raise RuntimeError("esac_oracle_backward failed")
     out["loss"] = float(loss)
     out["entropy"] = float(out["entropy"][0])
+    return out
+
+
+def backward_paths(scene_coords, out_gradients, hyp_assign, gt_pose, stages, w_rot=1.0, w_trans=100.0, loss_cut=100.0,
+                   shift_x=0, shift_y=0, focal=525.0, ppx=320.0, ppy=240.0, inlier_thresh=10.0, inlier_alpha=100.0,
+                   inlier_beta=0.5, max_reproj=100.0, sub_sampling=8, num_threads=0):
+    """Path I, path II and the assembly of esac_backward on GIVEN upstream stages (esac_oracle_backward_paths: the second
+    half of `backward`, the same text).  stages: dict with init_hyps [N,6], ref_hyps [N,6], sample_xy [N,4,2], probs [N],
+    losses [N], have_map [N], maps [N,H*W]; optional score_grads [N] and dloss [N,6] replace the values derived from
+    them as the inputs of path II / path I.  Accumulates into out_gradients; returns the outputs of `want_paths` plus
+    score_grads and dloss (as derived here)."""
+    sc = np.asarray(scene_coords)
+    ha = np.asarray(hyp_assign)
+    og = out_gradients
+    gt = np.ascontiguousarray(gt_pose, np.float32).reshape(16)
+    b, keep = _bwd_args(sc, og, ha, gt, w_rot, w_trans, loss_cut, shift_x, shift_y, focal, ppx, ppy, inlier_thresh, inlier_alpha,
+                        inlier_beta, max_reproj, sub_sampling, 0, 0, 0, -1, num_threads, None, None)
+    E, _, H, W = sc.shape
+    N = ha.shape[0]
+    kinds = dict(init_hyps=((N, 6), np.float64), ref_hyps=((N, 6), np.float64), sample_xy=((N, 4, 2), np.int32),
+                 probs=((N,), np.float64), losses=((N,), np.float64), have_map=((N,), np.uint8), maps=((N, H * W), np.uint8),
+                 score_grads=((N,), np.float64), dloss=((N, 6), np.float64))
+    st = _BwdStages()
+    held = []
+    for k, (shape, dt) in kinds.items():
+        v = stages.get(k)
+        if v is None:
+            assert k in ("score_grads", "dloss"), k
+            continue
+        v = np.ascontiguousarray(v, dt)
+        assert v.shape == shape, (k, v.shape, shape)
+        held.append(v)
+        setattr(st, k, _p(v))
+    out = dict(score_grads=np.zeros(N), dloss=np.zeros((N, 6)))
+    out.update(_path_outputs(N, H * W))
+    for k in out:
+        setattr(b, "out_" + k, _p(out[k]))
+    L = lib()
+    L.esac_oracle_backward_paths.argtypes = [C.POINTER(_BwdArgs), C.POINTER(_BwdStages)]
+    L.esac_oracle_backward_paths.restype = C.c_int
+    if L.esac_oracle_backward_paths(C.byref(b), C.byref(st)) != 0:
+        raise RuntimeError("esac_oracle_backward_paths failed")
     return out
 
 
@@ -309,6 +382,14 @@ def trans2pose(T):
     pose = np.zeros(6)
     lib().esac_oracle_trans2pose(_p(T), _p(pose))
     return pose
+
+
+def soft_max(scores):
+    s = np.ascontiguousarray(scores, np.float64)
+    out = np.zeros_like(s)
+    lib().esac_oracle_soft_max.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib().esac_oracle_soft_max(_p(s), len(s), _p(out))
+    return out
 
 
 def dproject_dobj(pt, obj, rvec, tvec, focal, ppx, ppy, max_reproj):

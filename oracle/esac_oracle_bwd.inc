@@ -207,7 +207,7 @@ static void trans2pose_fn(const double T[16], double pose[6]) {
 }
 
 /* dPNP for the 4-point P3P case (esac_derivative.h:128-185): 6x12, last three columns zero */
-static void dpnp_p3p(const ctx_t* c, const float img[8], const float obj_in[12], double J[72]) {
+static int dpnp_p3p(const ctx_t* c, const float img[8], const float obj_in[12], double J[72]) {
     const float eps = 0.001f;
     float obj[12];
     memcpy(obj, obj_in, sizeof(obj));
@@ -219,10 +219,10 @@ static void dpnp_p3p(const ctx_t* c, const float img[8], const float obj_in[12],
             double od[12], f[6], b[6];
             obj[3 * i + j] += eps;
             for (int k = 0; k < 12; k++) od[k] = obj[k];
-            if (!esac_oracle_p3p(od, imgd, c->fx, c->fy, c->cx, c->cy, f, f + 3)) { memset(J, 0, 72 * sizeof(double)); return; }
+            if (!esac_oracle_p3p(od, imgd, c->fx, c->fy, c->cx, c->cy, f, f + 3)) { memset(J, 0, 72 * sizeof(double)); return 0; }
             obj[3 * i + j] -= 2 * eps;
             for (int k = 0; k < 12; k++) od[k] = obj[k];
-            if (!esac_oracle_p3p(od, imgd, c->fx, c->fy, c->cx, c->cy, b, b + 3)) { memset(J, 0, 72 * sizeof(double)); return; }
+            if (!esac_oracle_p3p(od, imgd, c->fx, c->fy, c->cx, c->cy, b, b + 3)) { memset(J, 0, 72 * sizeof(double)); return 0; }
             obj[3 * i + j] += eps;
             const double den = (double)(2 * eps);
             for (int k = 0; k < 6; k++) {
@@ -230,8 +230,9 @@ static void dpnp_p3p(const ctx_t* c, const float img[8], const float obj_in[12],
                 J[k * 12 + i * 3 + j] = g;
             }
             for (int k = 0; k < 6; k++)
-                if (J[k * 12 + i * 3 + j] != J[k * 12 + i * 3 + j]) { memset(J, 0, 72 * sizeof(double)); return; }
+                if (J[k * 12 + i * 3 + j] != J[k * 12 + i * 3 + j]) { memset(J, 0, 72 * sizeof(double)); return 0; }
         }
+    return 1; /* (0: a solve failed or an entry is NaN -- the matrix is all zero, esac_derivative.h:150-181) */
 }
 
 /* exported for the oracle/_ref shim: (J^T J).inv(DECOMP_SVD) and cv::projectPoints' Jacobian columns 0..5 */
@@ -253,90 +254,63 @@ static double get_max_abs(const double* m, size_t n) { /* esac_util.h:599-613 */
     return mx;
 }
 
-double esac_oracle_backward(esac_oracle_bwd_args* b) {
-    esac_oracle_args* a = &b->fwd;
-    if (!a->scene_coords || !a->hyp_assign || a->N <= 0 || a->H < 3 || a->W < 3 || a->E <= 0 || !b->gt_pose || !b->out_gradients)
-        return -1.0;
+/* Path I, path II and the assembly of esac_backward (esac.cpp:375-508) as a function of GIVEN upstream stages: the second half of
+ * esac_oracle_backward, which runs it on its own stages, and -- exported as esac_oracle_backward_paths -- the replay that tests
+ * run on another implementation's stages.  errs / JH: the reprojection errors and Jacobian rows of the initial hypotheses
+ * (getReproErrs, esac.cpp:295-305), computed here from init_hyps when NULL. */
+static void backward_paths(const ctx_t* cp, esac_oracle_bwd_args* b, const esac_oracle_bwd_stages* st_in, const float* errs_in,
+                           const double* JH_in, int nthreads) {
+    const ctx_t c = *cp;
+    const esac_oracle_args* a = c.a;
     const int N = a->N, H = a->H, W = a->W, P = H * W;
-    const int max_tries = a->max_tries > 0 ? a->max_tries : ESAC_ORACLE_MAX_TRIES;
-    const int max_ref = a->max_ref_steps >= 0 ? a->max_ref_steps : ESAC_ORACLE_MAX_REF_STEPS;
-#ifdef _OPENMP
-    int nthreads = a->num_threads > 0 ? a->num_threads : omp_get_max_threads();
-    if (a->rng_mode == ESAC_RNG_CALLBACK) nthreads = 1;
-#else
-    int nthreads = 1;
-#endif
     (void)nthreads;
-    ctx_t c;
-    c.a = a;
-    c.fx = c.fy = (double)a->focal; c.cx = (double)a->ppx; c.cy = (double)a->ppy;
     const double wRot = (double)b->w_rot, wTrans = (double)b->w_trans, cut = (double)b->loss_cut;
     double gtT[16];
     for (int i = 0; i < 16; i++) gtT[i] = (double)b->gt_pose[i];
-
-    double* initHyps = (double*)calloc((size_t)N * 6, sizeof(double));
-    double* refHyps = (double*)calloc((size_t)N * 6, sizeof(double));
-    int32_t* sxy = (int32_t*)calloc((size_t)N * 8, sizeof(int32_t));
-    float* errs = (float*)malloc((size_t)N * P * sizeof(float));
-    double* JH = (double*)malloc((size_t)N * P * 6 * sizeof(double));
-    uint8_t* maps = (uint8_t*)calloc((size_t)N * P, 1);
-    uint8_t* have_map = (uint8_t*)calloc((size_t)N, 1);
-    double* scores = (double*)calloc((size_t)N, sizeof(double));
-    double* probs = (double*)calloc((size_t)N, sizeof(double));
-    double* losses = (double*)calloc((size_t)N, sizeof(double));
+    const double* initHyps = st_in->init_hyps;
+    const double* refHyps = st_in->ref_hyps;
+    const int32_t* sxy = st_in->sample_xy;
+    const double* probs = st_in->probs;
+    const double* losses = st_in->losses;
+    const uint8_t* have_map = st_in->have_map;
+    const uint8_t* maps = st_in->maps;
+    float* errs_own = NULL;
+    double* JH_own = NULL;
+    if (!errs_in || !JH_in) {
+        errs_own = (float*)malloc((size_t)N * P * sizeof(float));
+        JH_own = (double*)malloc((size_t)N * P * 6 * sizeof(double));
+#pragma omp parallel for schedule(static) num_threads(nthreads)
+        for (int h = 0; h < N; h++)
+            repro_errs_jac(&c, initHyps + 6 * h, (int)assign_at(a, h), errs_own + (size_t)h * P, JH_own + (size_t)h * P * 6);
+    }
+    const float* errs = errs_own ? errs_own : errs_in;
+    const double* JH = JH_own ? JH_own : JH_in;
     double* gradI = (double*)calloc((size_t)N * P * 3, sizeof(double));   /* gradients[h], 1 x 3P, idx*3+c */
     double* gradII = (double*)calloc((size_t)N * P * 3, sizeof(double));  /* dLoss_dScore_dObjs[h], (y*W+x, c) */
     double* sgrad = (double*)calloc((size_t)N, sizeof(double));
     double* dl_all = (double*)calloc((size_t)N * 6, sizeof(double));
+    if (b->out_path1_state) for (int h = 0; h < N; h++) b->out_path1_state[h] = -1;
+    if (b->out_dpnp_state) for (int h = 0; h < N; h++) b->out_dpnp_state[h] = -1;
+    if (b->out_score_grads) memset(b->out_score_grads, 0, (size_t)N * sizeof(double));
 
-    /* ---- sampleHypotheses (esac.cpp:276) ---- */
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
-    for (int h = 0; h < N; h++) {
-        int expert = (int)assign_at(a, h);
-        for (int t = 0; t < max_tries; t++)
-            if (sample_try(&c, h, expert, (uint32_t)t, sxy + 8 * h, initHyps + 6 * h)) break;
-    }
-    /* ---- reprojection errors + Jacobians, scores, softmax (esac.cpp:295-319) ---- */
-#pragma omp parallel for schedule(static) num_threads(nthreads)
-    for (int h = 0; h < N; h++)
-        repro_errs_jac(&c, initHyps + 6 * h, (int)assign_at(a, h), errs + (size_t)h * P, JH + (size_t)h * P * 6);
-#pragma omp parallel for schedule(static) num_threads(nthreads)
-    for (int h = 0; h < N; h++) scores[h] = hyp_score_from_errs(a, errs + (size_t)h * P);
-    soft_max(scores, N, probs);
-    const double ent = entropy(probs, N);
-
-    /* ---- refine every hypothesis with prob >= PROB_THRESH (esac.cpp:328-347) ---- */
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
-    for (int h = 0; h < N; h++) {
-        memcpy(refHyps + 6 * h, initHyps + 6 * h, 6 * sizeof(double));
-        if (probs[h] < PROB_THRESH_REF) continue;
-        int acc = refine_hyp(&c, errs + (size_t)h * P, (int)assign_at(a, h), max_ref, refHyps + 6 * h, maps + (size_t)h * P, NULL, NULL);
-        have_map[h] = acc > 0; /* inlierMaps[h] stays an empty Mat when no re-fit was accepted */
-    }
-    /* ---- expected loss (esac.cpp:354-362) ---- */
-    double expectedLoss = 0;
-    for (int h = 0; h < N; h++) {
-        double T[16];
-        esac_oracle_pose2trans(refHyps + 6 * h, T);
-        losses[h] = loss_fn(T, gtT, wRot, wTrans, cut);
-        expectedLoss += probs[h] * losses[h];
-    }
-
-    /* ---- path I: pose -> coordinates through the last re-fit (esac.cpp:375-463) ---- */
     double hypGT[6];
     trans2pose_fn(gtT, hypGT);
+    /* ---- path I: pose -> coordinates through the last re-fit (esac.cpp:375-463) ---- */
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
     for (int h = 0; h < N; h++) {
         if (probs[h] < PROB_THRESH_REF) continue;
         const int expert = (int)assign_at(a, h);
         double* g = gradI + (size_t)h * P * 3;
         double dL[6];
-        dloss_fn(refHyps + 6 * h, hypGT, wRot, wTrans, cut, dL);
+        if (st_in->dloss) memcpy(dL, st_in->dloss + 6 * h, sizeof(dL)); /* a replay: the caller's own dLoss */
+        else dloss_fn(refHyps + 6 * h, hypGT, wRot, wTrans, cut, dL);
         memcpy(dl_all + 6 * h, dL, sizeof(dL));
+        if (b->out_path1_state) b->out_path1_state[h] = 1;
         if (!have_map[h]) continue;
         /* inliers of the last accepted refinement step, x outer / y inner */
         int n = 0;
         for (int i = 0; i < P; i++) n += maps[(size_t)h * P + i];
+        if (b->out_path1_state) b->out_path1_state[h] = 2;
         if (n < 4) continue;
         double* JR = (double*)malloc((size_t)n * 6 * sizeof(double));
         int* cell = (int*)malloc((size_t)n * sizeof(int));
@@ -362,6 +336,7 @@ double esac_oracle_backward(esac_oracle_bwd_args* b) {
                 A[i * 6 + j] = s;
             }
         pinv_sym6(A, Ainv);
+        if (b->out_jtj) memcpy(b->out_jtj + 36 * (size_t)h, A, sizeof(A));
         double* PI6 = (double*)malloc((size_t)n * 6 * sizeof(double)); /* column q of jacobeanR */
         for (int q = 0; q < n; q++)
             for (int i = 0; i < 6; i++) {
@@ -369,6 +344,8 @@ double esac_oracle_backward(esac_oracle_bwd_args* b) {
                 for (int j = 0; j < 6; j++) s += -Ainv[i * 6 + j] * JR[(size_t)q * 6 + j];
                 PI6[(size_t)q * 6 + i] = s;
             }
+        if (b->out_jr_max) b->out_jr_max[h] = get_max_abs(PI6, (size_t)n * 6);
+        if (b->out_path1_state) b->out_path1_state[h] = get_max_abs(PI6, (size_t)n * 6) > 10 ? 3 : 0;
         if (get_max_abs(PI6, (size_t)n * 6) > 10) memset(PI6, 0, (size_t)n * 6 * sizeof(double)); /* clamping for stability */
         for (int q = 0; q < n; q++) {
             const int y = cell[q] / W, x = cell[q] % W;
@@ -393,6 +370,8 @@ double esac_oracle_backward(esac_oracle_bwd_args* b) {
         double s = probs[i] * losses[i];
         for (int j = 0; j < N; j++) s -= probs[i] * probs[j] * losses[j];
         sgrad[i] = s;
+        if (b->out_score_grads) b->out_score_grads[i] = s;
+        if (st_in->score_grads) sgrad[i] = st_in->score_grads[i]; /* a replay: the caller's own d E / d score feeds path II */
     }
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
     for (int h = 0; h < N; h++) {
@@ -408,8 +387,14 @@ double esac_oracle_backward(esac_oracle_bwd_args* b) {
             for (int k = 0; k < 3; k++) obj[3 * j + k] = sc_at(a, expert, k, y, x);
         }
         double dHdO[72];
-        dpnp_p3p(&c, img, obj, dHdO);
+        const int solved = dpnp_p3p(&c, img, obj, dHdO);
+        if (b->out_dpnp_max) b->out_dpnp_max[h] = get_max_abs(dHdO, 72);
+        if (b->out_dpnp_state) b->out_dpnp_state[h] = !solved ? 1 : get_max_abs(dHdO, 72) > 10 ? 2 : 0;
+        double dHdO_raw[72], support_raw[12]; /* (out_support_raw only: what the support terms would be WITHOUT the clamp) */
+        memcpy(dHdO_raw, dHdO, sizeof(dHdO));
+        memset(support_raw, 0, sizeof(support_raw));
         if (get_max_abs(dHdO, 72) > 10) memset(dHdO, 0, sizeof(dHdO));
+        if (b->out_dpnp) memcpy(b->out_dpnp + 72 * (size_t)h, dHdO, sizeof(dHdO));
         const double* pose = initHyps + 6 * h;
         double R[9];
         esac_oracle_rodrigues_vec2mat(pose, R, NULL);
@@ -436,7 +421,16 @@ double esac_oracle_backward(esac_oracle_bwd_args* b) {
                     for (int k = 0; k < 6; k++) s += tmp[k] * dHdO[k * 12 + m];
                     support[m] += s;
                 }
+                if (b->out_support_raw)
+                    for (int m = 0; m < 12; m++) {
+                        double s = 0;
+                        for (int k = 0; k < 6; k++) s += tmp[k] * dHdO_raw[k * 12 + m];
+                        support_raw[m] += s;
+                    }
             }
+        if (b->out_grad_direct) memcpy(b->out_grad_direct + (size_t)h * P * 3, g2, (size_t)P * 3 * sizeof(double));
+        if (b->out_support) memcpy(b->out_support + 12 * (size_t)h, support, sizeof(support));
+        if (b->out_support_raw) memcpy(b->out_support_raw + 12 * (size_t)h, support_raw, sizeof(support_raw));
         for (int j = 0; j < 4; j++) {
             const int x = sxy[8 * h + 2 * j], y = sxy[8 * h + 2 * j + 1];
             for (int cc = 0; cc < 3; cc++) g2[(size_t)(y * W + x) * 3 + cc] += support[3 * j + cc];
@@ -456,19 +450,125 @@ double esac_oracle_backward(esac_oracle_bwd_args* b) {
         }
     }
 
+
+    if (b->out_dloss) memcpy(b->out_dloss, dl_all, (size_t)N * 6 * sizeof(double));
+    if (b->out_grad_path1) memcpy(b->out_grad_path1, gradI, (size_t)N * P * 3 * sizeof(double));
+    if (b->out_grad_path2) memcpy(b->out_grad_path2, gradII, (size_t)N * P * 3 * sizeof(double));
+    free(errs_own); free(JH_own); free(gradI); free(gradII); free(sgrad); free(dl_all);
+}
+
+static int bwd_threads(const esac_oracle_args* a) {
+#ifdef _OPENMP
+    int nthreads = a->num_threads > 0 ? a->num_threads : omp_get_max_threads();
+    if (a->rng_mode == ESAC_RNG_CALLBACK) nthreads = 1;
+    return nthreads;
+#else
+    (void)a;
+    return 1;
+#endif
+}
+
+int esac_oracle_backward_paths(esac_oracle_bwd_args* b, const esac_oracle_bwd_stages* st) {
+    esac_oracle_args* a = &b->fwd;
+    if (!a->scene_coords || !a->hyp_assign || a->N <= 0 || a->H < 3 || a->W < 3 || a->E <= 0 || !b->gt_pose || !b->out_gradients)
+        return -1;
+    if (!st || !st->init_hyps || !st->ref_hyps || !st->sample_xy || !st->probs || !st->losses || !st->have_map || !st->maps) return -1;
+    ctx_t c;
+    c.a = a;
+    c.fx = c.fy = (double)a->focal; c.cx = (double)a->ppx; c.cy = (double)a->ppy;
+    backward_paths(&c, b, st, NULL, NULL, bwd_threads(a));
+    return 0;
+}
+
+double esac_oracle_backward(esac_oracle_bwd_args* b) {
+    esac_oracle_args* a = &b->fwd;
+    if (!a->scene_coords || !a->hyp_assign || a->N <= 0 || a->H < 3 || a->W < 3 || a->E <= 0 || !b->gt_pose || !b->out_gradients)
+        return -1.0;
+    const int N = a->N, H = a->H, W = a->W, P = H * W;
+    const int max_tries = a->max_tries > 0 ? a->max_tries : ESAC_ORACLE_MAX_TRIES;
+    const int max_ref = a->max_ref_steps >= 0 ? a->max_ref_steps : ESAC_ORACLE_MAX_REF_STEPS;
+    const int nthreads = bwd_threads(a);
+    (void)nthreads;
+    ctx_t c;
+    c.a = a;
+    c.fx = c.fy = (double)a->focal; c.cx = (double)a->ppx; c.cy = (double)a->ppy;
+    const double wRot = (double)b->w_rot, wTrans = (double)b->w_trans, cut = (double)b->loss_cut;
+    double gtT[16];
+    for (int i = 0; i < 16; i++) gtT[i] = (double)b->gt_pose[i];
+
+    double* initHyps = (double*)calloc((size_t)N * 6, sizeof(double));
+    double* refHyps = (double*)calloc((size_t)N * 6, sizeof(double));
+    int32_t* sxy = (int32_t*)calloc((size_t)N * 8, sizeof(int32_t));
+    float* errs = (float*)malloc((size_t)N * P * sizeof(float));
+    double* JH = (double*)malloc((size_t)N * P * 6 * sizeof(double));
+    uint8_t* maps = (uint8_t*)calloc((size_t)N * P, 1);
+    uint8_t* have_map = (uint8_t*)calloc((size_t)N, 1);
+    double* scores = (double*)calloc((size_t)N, sizeof(double));
+    double* probs = (double*)calloc((size_t)N, sizeof(double));
+    double* losses = (double*)calloc((size_t)N, sizeof(double));
+    int32_t* ref_steps = (int32_t*)calloc((size_t)N, sizeof(int32_t));
+    int32_t* ref_inliers = (int32_t*)calloc((size_t)N, sizeof(int32_t));
+    int32_t* ref_lm = (int32_t*)calloc((size_t)N, sizeof(int32_t));
+
+    /* ---- sampleHypotheses (esac.cpp:276) ---- */
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
+    for (int h = 0; h < N; h++) {
+        int expert = (int)assign_at(a, h);
+        for (int t = 0; t < max_tries; t++)
+            if (sample_try(&c, h, expert, (uint32_t)t, sxy + 8 * h, initHyps + 6 * h)) break;
+    }
+    /* ---- reprojection errors + Jacobians, scores, softmax (esac.cpp:295-319) ---- */
+#pragma omp parallel for schedule(static) num_threads(nthreads)
+    for (int h = 0; h < N; h++)
+        repro_errs_jac(&c, initHyps + 6 * h, (int)assign_at(a, h), errs + (size_t)h * P, JH + (size_t)h * P * 6);
+#pragma omp parallel for schedule(static) num_threads(nthreads)
+    for (int h = 0; h < N; h++) scores[h] = hyp_score_from_errs(a, errs + (size_t)h * P);
+    soft_max(scores, N, probs);
+    const double ent = entropy(probs, N);
+
+    /* ---- refine every hypothesis with prob >= PROB_THRESH (esac.cpp:328-347) ---- */
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
+    for (int h = 0; h < N; h++) {
+        memcpy(refHyps + 6 * h, initHyps + 6 * h, 6 * sizeof(double));
+        if (probs[h] < PROB_THRESH_REF) continue;
+        int32_t* counts = (int32_t*)calloc((size_t)max_ref + 1, sizeof(int32_t));
+        int acc = refine_hyp(&c, errs + (size_t)h * P, (int)assign_at(a, h), max_ref, refHyps + 6 * h, maps + (size_t)h * P, counts, ref_lm + h);
+        have_map[h] = acc > 0; /* inlierMaps[h] stays an empty Mat when no re-fit was accepted */
+        ref_steps[h] = acc;
+        ref_inliers[h] = acc > 0 ? counts[acc - 1] : 0; /* the inlier set the last accepted re-fit ran on */
+        free(counts);
+    }
+    /* ---- expected loss (esac.cpp:354-362) ---- */
+    double expectedLoss = 0;
+    for (int h = 0; h < N; h++) {
+        double T[16];
+        esac_oracle_pose2trans(refHyps + 6 * h, T);
+        losses[h] = loss_fn(T, gtT, wRot, wTrans, cut);
+        expectedLoss += probs[h] * losses[h];
+    }
+
+    /* ---- path I, path II, assemble (esac.cpp:375-508): a function of the stages above ---- */
+    esac_oracle_bwd_stages st;
+    memset(&st, 0, sizeof(st));
+    st.init_hyps = initHyps; st.ref_hyps = refHyps; st.sample_xy = sxy; st.probs = probs; st.losses = losses;
+    st.have_map = have_map; st.maps = maps;
+    backward_paths(&c, b, &st, errs, JH, nthreads);
+
     if (b->out_probs) memcpy(b->out_probs, probs, (size_t)N * sizeof(double));
     if (b->out_losses) memcpy(b->out_losses, losses, (size_t)N * sizeof(double));
     if (b->out_init_hyps) memcpy(b->out_init_hyps, initHyps, (size_t)N * 6 * sizeof(double));
     if (b->out_ref_hyps) memcpy(b->out_ref_hyps, refHyps, (size_t)N * 6 * sizeof(double));
-    if (b->out_score_grads) memcpy(b->out_score_grads, sgrad, (size_t)N * sizeof(double));
-    if (b->out_dloss) memcpy(b->out_dloss, dl_all, (size_t)N * 6 * sizeof(double));
     if (b->out_sample_xy) memcpy(b->out_sample_xy, sxy, (size_t)N * 8 * sizeof(int32_t));
     if (b->out_entropy) *b->out_entropy = ent;
-    if (b->out_grad_path1) memcpy(b->out_grad_path1, gradI, (size_t)N * P * 3 * sizeof(double));
-    if (b->out_grad_path2) memcpy(b->out_grad_path2, gradII, (size_t)N * P * 3 * sizeof(double));
+    if (b->out_scores) memcpy(b->out_scores, scores, (size_t)N * sizeof(double));
+    if (b->out_maps) memcpy(b->out_maps, maps, (size_t)N * P);
+    if (b->out_have_map) memcpy(b->out_have_map, have_map, (size_t)N);
+    if (b->out_ref_steps) memcpy(b->out_ref_steps, ref_steps, (size_t)N * sizeof(int32_t));
+    if (b->out_ref_inliers) memcpy(b->out_ref_inliers, ref_inliers, (size_t)N * sizeof(int32_t));
+    if (b->out_ref_lm_iters) memcpy(b->out_ref_lm_iters, ref_lm, (size_t)N * sizeof(int32_t));
 
     free(initHyps); free(refHyps); free(sxy); free(errs); free(JH); free(maps); free(have_map); free(scores);
-    free(probs); free(losses); free(gradI); free(gradII); free(sgrad); free(dl_all);
+    free(probs); free(losses); free(ref_steps); free(ref_inliers); free(ref_lm);
     return expectedLoss;
 }
 
@@ -482,6 +582,7 @@ void esac_oracle_pose_dloss(const double est[6], const double gt_pose[6], double
     dloss_fn(est, gt_pose, wRot, wTrans, cut, jac);
 }
 void esac_oracle_trans2pose(const double T[16], double pose[6]) { trans2pose_fn(T, pose); }
+void esac_oracle_soft_max(const double* scores, int n, double* probs) { soft_max(scores, n, probs); }
 void esac_oracle_dproject_dobj(float ptx, float pty, float ox, float oy, float oz, const double rvec[3], const double t[3],
                                float focal, float ppx, float ppy, float maxReproj, double out[3]) {
     esac_oracle_args a;

@@ -122,6 +122,31 @@ int main(int argc, char** argv) {
         fprintf(stderr, "backward failed: %s\n", p_esac_hip_last_error());
         return 15;
     }
+    {
+        /* the per-slot tables of that call: the buffer ESAC_BUF_BWD_SLOT_INFO names holds as many inliers as it says */
+        typedef char maps_id_is_23[ESAC_BUF_BWD_MAPS == 23 ? 1 : -1];
+        (void)sizeof(maps_id_is_23);
+        const int n = (int)out[1];
+        int32_t info[N][4];
+        unsigned char* maps = (unsigned char*)malloc((size_t)(n > 0 ? n : 1) * 2 * P);
+        if (n < 1 || n > N || p_esac_hip_read(ctx, ESAC_BUF_BWD_SLOT_INFO, info, sizeof(info)) != 0) return 40;
+        if (p_esac_hip_read(ctx, ESAC_BUF_BWD_MAPS, maps, (size_t)n * 2 * P) != 0) {
+            fprintf(stderr, "reading the slot maps failed: %s\n", p_esac_hip_last_error());
+            return 41;
+        }
+        if (p_esac_hip_read(ctx, ESAC_BUF_BWD_MAPS, maps, (size_t)P) != -7) return 42; /* whole slots only */
+        for (int s = 0; s < n; s++) {
+            if (info[s][0] < 0) continue;
+            if (info[s][0] > 1) return 43;
+            int count = 0;
+            for (int i = 0; i < P; i++) count += maps[((size_t)s * 2 + info[s][0]) * P + i] != 0;
+            if (count != info[s][1]) {
+                fprintf(stderr, "slot %d: map holds %d inliers, the slot table says %d\n", s, count, info[s][1]);
+                return 44;
+            }
+        }
+        free(maps);
+    }
     printf("backward ok: expected loss %.3e over %d refined hypotheses\n", out[0], (int)out[1]);
     if (argc > 3 && strcmp(argv[3], "time") == 0) {
         /* where the host's time of a blocking call goes WITHOUT Python or torch in the process (scripts/dev/host_turn.py is

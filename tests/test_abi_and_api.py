@@ -26,6 +26,17 @@ def test_header_and_binding_agree():
     assert sorted(api.ABI_SYMBOLS) == names
 
 
+def test_buffer_ids_of_header_and_binding_agree():
+    """Every ESAC_BUF_* id of the header has the same value in esac_amd/api.py, and no two buffers share one."""
+    src = open(os.path.join(ROOT, "include", "esac_hip.h")).read()
+    ids = {m.group(1): int(m.group(2)) for m in re.finditer(r"\bESAC_(BUF_\w+)\s*=\s*(\d+)", src)}
+    assert len(ids) == 24 and len(set(ids.values())) == len(ids), ids
+    assert ids["BUF_BWD_MAPS"] == 23
+    for name, value in ids.items():
+        assert getattr(api, name) == value, name
+    assert callable(api.Engine.read_maps)
+
+
 def test_library_exports_every_declared_symbol():
     path = build.build_hip()
     lib = C.CDLL(path)

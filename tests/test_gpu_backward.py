@@ -2,9 +2,12 @@
 restatement of esac_backward (esac.cpp:213-520), itself pinned bit-for-bit to the reference sources by
 tests/test_oracle_vs_ref.py.  Same inputs, same Philox key.
 
-Bars: index work (sampled cells, the set of hypotheses with p >= PROB_THRESH, accepted refinement steps, inlier
-counts) bit-exact; probabilities, losses, poses and gradients to the floating-point tolerances written below
-(the reference's own arithmetic is fp64 with float stores; the kernels reduce in a different, fixed order).
+Bars: index work (sampled cells, the set of hypotheses with p >= PROB_THRESH) bit-exact; probabilities, losses, poses and
+gradients to the floating-point tolerances written below (the reference's own arithmetic is fp64 with float stores; the
+kernels reduce in a different, fixed order).  These are END-TO-END bars: the oracle's expected values come from the
+oracle's own hypotheses, refined poses and inlier sets, so they absorb upstream differences.  The per-slot index work
+(accepted refinement steps, inlier counts, LM iterations, the accepted inlier map) is held bit-exact, and every gradient
+kernel is held to a bar of its own against a replay of the device's own stages, in tests/test_gpu_backward_stages.py.
 """
 import numpy as np
 import pytest
@@ -161,6 +164,18 @@ def test_backward_path_slabs(engine, oracle):
     sel = np.nonzero(ref["probs"] >= 1e-3)[0]
     assert any(np.abs(ref["grad_path1"][h]).max() > 0 for h in sel)
     assert all(np.abs(ref["grad_path2"][h]).max() > 0 for h in sel)
+    # ... and so are the DEVICE's slabs, each within its own kernel's bar of the replay of the device's stages
+    from tests import bwd_replay as R
+    c = R.case_of(f, ha, gt, np.zeros_like(f["coords"]), 3.0, 1305, 3)
+    stages, dev = R.device_stages(engine, api, c, out[1])
+    np.testing.assert_array_equal(dev["slots"], sel)
+    assert any(dev["slab1"][s].any() for s in range(len(sel))) and all(dev["slab2"][s].any() for s in range(len(sel)))
+    rp = R.replay_with_inputs(oracle, c, stages)
+    for s, h in enumerate(sel):
+        assert dev["slab1"][s].any() == rp["grad_path1"][h].any()
+    direct, path1, n_p1 = R.slab_ratios(c, stages, dev, rp)
+    print("path slabs: path II direct term %.3g of its bar, path I %.3g of its bar over %d slots" % (direct, path1, n_p1))
+    assert n_p1 >= 1 and direct <= 1.0 and path1 <= 1.0, (direct, path1, n_p1)
 
 
 def test_backward_accumulates_into_existing_gradients(engine, oracle):
