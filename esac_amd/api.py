@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     "esac_hip_forward_batch_cams", "esac_hip_backward_batch_cams",
     "esac_hip_backward_batch_dev",  # additive: the ABI version stays
     "esac_hip_eval_batch",  # additive too
+    "esac_hip_set_bwd_pose_records",  # additive too
 ]
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
@@ -156,6 +157,7 @@ def load_library():
         lib.esac_hip_backward_batch_dev.argtypes = [vp, i32, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_float, C.c_float,
                                                     C.c_float, pp, vp, vp]
         lib.esac_hip_eval_batch.argtypes = [vp, i32, vp, vp, vp, C.c_float, C.c_float, vp, vp]
+        lib.esac_hip_set_bwd_pose_records.argtypes = [vp, vp, i32]
         lib.esac_hip_read.argtypes = [vp, i32, vp, C.c_size_t]
         lib.esac_hip_write_hyps.argtypes = [vp, vp, i32]
         lib.esac_hip_phase_ms.argtypes = [vp, vp]
@@ -190,6 +192,28 @@ def _check(rc, lib):
         raise RuntimeError("esac (HIP): %s [status %d]" % (lib.esac_hip_last_error().decode(), rc))
 
 
+def _check_pose_records(who, name, records, B, device_only, device=None):
+    """The pose-record argument of a training call (esac_hip_set_bwd_pose_records): a float64 tensor [32] (B is None: a single
+    call) or [B,32], filled in place.  device_only: the asynchronous call -- a contiguous device tensor; otherwise a CPU tensor
+    (any strides) or a contiguous device tensor.  device: the device the call's tensors live on (None: not known yet).
+    Raises RuntimeError naming the argument; touches no device."""
+    if not isinstance(records, torch.Tensor):
+        raise RuntimeError("%s: %s must be a torch.Tensor" % (who, name))
+    if records.dtype != torch.float64:
+        raise RuntimeError("%s: expected scalar type torch.float64 for %s but found %s" % (who, name, records.dtype))
+    want = (RES_DOUBLES,) if B is None else (int(B), RES_DOUBLES)
+    if tuple(records.shape) != want:
+        raise RuntimeError("%s: %s must be %s, found %s" % (who, name, list(want), list(records.shape)))
+    if records.device.type not in ("cpu", "cuda"):
+        raise RuntimeError("%s: %s lives on %s: a CPU or a GPU tensor is required" % (who, name, records.device))
+    if device_only and not records.is_cuda:
+        raise RuntimeError("%s: %s must be a device tensor (an asynchronous call cannot copy back into host storage)" % (who, name))
+    if records.is_cuda and not records.is_contiguous():
+        raise RuntimeError("%s: %s must be contiguous on the device (the kernel writes it in place)" % (who, name))
+    if records.is_cuda and device is not None and records.device != device:
+        raise RuntimeError("%s: %s lives on %s, the call runs on %s" % (who, name, records.device, device))
+
+
 class Engine:
     """One device context (esac_hip_ctx): workspaces + stage entry points for one GPU."""
 
@@ -210,6 +234,7 @@ class Engine:
         self._host_np = np.frombuffer(self._host_buf, dtype=np.float64)
         self._comm = None  # (nranks, rank) once comm_init has run
         self._comm_key = None  # the process group (its ranks) the communicator mirrors (distributed.native_comm)
+        self._pose_arm = None  # arm_pose_records: the record tensor of the next training call
 
     def _call(self, fn, *args):
         """One C-ABI call with this engine's device current (the library calls hipSetDevice itself; the context
@@ -318,16 +343,45 @@ class Engine:
         self._keep = (sc, ha)
         return host
 
+    def arm_pose_records(self, records):
+        """Arms the NEXT training call of this engine (backward_device, backward_batch, backward_batch_async) with `records`, as
+        their pose_record(s) argument does -- the route for backward_batch_async, whose parameter list is fixed.  One-shot: taken
+        by that call whether it runs or raises; None disarms.  Checked against that call's frames when it is made."""
+        if records is not None:
+            B = records.shape[0] if isinstance(records, torch.Tensor) and records.dim() == 2 else None
+            _check_pose_records("Engine.arm_pose_records", "records", records, B, False, self.device)
+        self._pose_arm = records
+
+    def _take_pose_arm(self, given):
+        """The records of this call: its own argument, else what arm_pose_records left (consumed either way)."""
+        armed, self._pose_arm = self._pose_arm, None
+        return given if given is not None else armed
+
+    def _arm_pose_records(self, who, name, records, B, device_only):
+        """Arms the next training call (esac_hip_set_bwd_pose_records) with `records` -- or, for a CPU tensor, with a device
+        staging tensor the caller copies back from after the call's own wait.  Returns the device tensor the kernel writes."""
+        _check_pose_records(who, name, records, B, device_only, self.device)
+        dev = records if records.is_cuda else torch.empty(tuple(records.shape), dtype=torch.float64, device=self.device)
+        self._call(self.lib.esac_hip_set_bwd_pose_records, dev.data_ptr(), 1 if B is None else int(B))
+        return dev
+
     def backward_device(self, scene_coords, out_gradients, hyp_assign, gt_pose, w_rot, w_trans, loss_cut, params,
-                        want_host=True):
+                        want_host=True, pose_record=None):
         """Training path on this device. out_gradients: float32 [E,3,H,W] on this device, contiguous, accumulated into.
-        gt_pose: 16 floats (4x4 camera pose). Returns np.float64[4] = expected loss, #refined hypotheses, entropy, 0."""
+        gt_pose: 16 floats (4x4 camera pose). Returns np.float64[4] = expected loss, #refined hypotheses, entropy, 0.
+        pose_record: None, or a float64 tensor [32] filled in place with the forward-format record (RES_*) of the call's argmax
+        hypothesis, refined (esac_hip_set_bwd_pose_records; RES_VALID 0 and a NaN pose when it holds no slot).  A device tensor
+        is written in stream order; a CPU tensor needs want_host (it is copied after the call's own wait)."""
+        pose_record = self._take_pose_arm(pose_record)
+        if pose_record is not None:
+            _check_pose_records("esac.backward", "poseRecord", pose_record, None, not want_host, self.device)
         sc, ha = self._dev_inputs(scene_coords, hyp_assign)
         if not (out_gradients.is_cuda and out_gradients.is_contiguous() and out_gradients.dtype == torch.float32
                 and tuple(out_gradients.shape) == tuple(sc.shape)):
             raise RuntimeError("esac.backward: the gradient tensor must be a dense float32 device tensor shaped like sceneCoordinates")
         gt = np.ascontiguousarray(np.asarray(gt_pose, np.float32).reshape(16))
         host = np.zeros(4, np.float64) if want_host else None
+        rec_dev = self._arm_pose_records("esac.backward", "poseRecord", pose_record, None, not want_host) if pose_record is not None else None
         # (the library makes the context's GPU current itself: no torch device guard on the call path, as in forward_device)
         rc = self.lib.esac_hip_backward(
             self.ctx, sc.data_ptr(), out_gradients.data_ptr(), ha.data_ptr(), gt.ctypes.data,
@@ -335,7 +389,9 @@ class Engine:
             host.ctypes.data if want_host else None)
         if rc != 0:
             _check(rc, self.lib)
-        self._keep = (sc, ha, out_gradients)
+        self._keep = (sc, ha, out_gradients, rec_dev)
+        if rec_dev is not None and rec_dev is not pose_record:
+            pose_record.copy_(rec_dev)  # (the call has waited for its last kernel: the record is there)
         return host
 
     def _batch_inputs(self, who, scene_coords, out_gradients, hyp_assign):
@@ -350,28 +406,36 @@ class Engine:
             raise RuntimeError("%s: the gradient tensor must be a dense float32 device tensor [B,E,3,H,W]" % who)
         return sc, ha, B, int(sc.stride(0)) if sc.dim() == 5 else 0
 
-    def backward_batch(self, scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, cams=None):
+    def backward_batch(self, scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, cams=None,
+                       pose_records=None):
         """Training path over B frames in one set of launches (esac_hip_backward_batch). scene_coords [B,E,3,H,W] (or [E,3,H,W]
         shared by all frames), out_gradients float32 [B,E,3,H,W] on this device, contiguous, accumulated into; hyp_assign [B,N];
         gt_poses [B,4,4]. `params` describes one frame, frame b uses call + b. Returns np.float64 [B,4] (one record per frame).
         An out-of-range device assignment raises after every frame has run; the exception's `records` holds the [B,4] records.
-        cams: None or B per-frame camera records (make_cams), as in forward_batch (esac_hip_backward_batch_cams)."""
+        cams: None or B per-frame camera records (make_cams), as in forward_batch (esac_hip_backward_batch_cams).
+        pose_records: None, or a float64 tensor [B,32] (this device, contiguous; or CPU) filled in place: row b = the
+        forward-format record of frame b's argmax hypothesis, as backward_device's pose_record."""
+        pose_records = self._take_pose_arm(pose_records)
         sc, ha, B, sc_stride = self._batch_inputs("esac.backward_batch", scene_coords, out_gradients, hyp_assign)
         gt = np.ascontiguousarray(np.asarray(gt_poses, np.float32).reshape(-1))
         if gt.size != 16 * B:
             raise RuntimeError("esac.backward_batch: gtPoses must hold B 4x4 poses")
         host = np.zeros((B, 4), np.float64)
+        if cams is not None:
+            cams = _cams_arg(cams, B, "esac.backward_batch")
+        rec_dev = self._arm_pose_records("esac.backward_batch", "poseRecords", pose_records, B, False) if pose_records is not None else None
         if cams is None:
             rc = self.lib.esac_hip_backward_batch(
                 self.ctx, B, sc.data_ptr(), sc_stride, out_gradients.data_ptr(), int(out_gradients.stride(0)), ha.data_ptr(),
                 gt.ctypes.data, float(w_rot), float(w_trans), float(loss_cut), C.byref(params), self._stream(), host.ctypes.data)
         else:
-            cams = _cams_arg(cams, B, "esac.backward_batch")
             rc = self.lib.esac_hip_backward_batch_cams(
                 self.ctx, B, sc.data_ptr(), sc_stride, out_gradients.data_ptr(), int(out_gradients.stride(0)), ha.data_ptr(),
                 gt.ctypes.data, cams.ctypes.data, float(w_rot), float(w_trans), float(loss_cut), C.byref(params), self._stream(),
                 host.ctypes.data)
-        self._keep = (sc, ha, out_gradients)
+        self._keep = (sc, ha, out_gradients, rec_dev)
+        if rec_dev is not None and rec_dev is not pose_records and rc in (0, -10):  # (-10: raised after every frame has run)
+            pose_records.copy_(rec_dev)
         if rc != 0:
             err = RuntimeError("esac (HIP): %s [status %d]" % (self.lib.esac_hip_last_error().decode(), rc))
             err.records = host
@@ -385,8 +449,14 @@ class Engine:
         device (the point of the call), or a host array / tensor, uploaded with non_blocking=True on the launch stream.
         Returns the device float64 tensor [B,4] of records (`out` when given).  A singular ground-truth pose or an out-of-range
         assignment is a per-frame outcome (record[3] = 2 / 1): check() after a synchronisation raises for it.
-        cams: None or B per-frame camera records (make_cams), copied before the call returns."""
+        cams: None or B per-frame camera records (make_cams), copied before the call returns.
+        Pose records: arm_pose_records(t) before the call, t a contiguous float64 tensor [B,32] on this device, written in
+        stream order: row b = the forward-format record of frame b's argmax hypothesis (RES_VALID 0 and a NaN pose for a frame
+        that selected nothing, a singular ground truth among them); eval_batch may be enqueued right behind the call."""
+        pose_records = self._take_pose_arm(None)
         sc, ha, B, sc_stride = self._batch_inputs("esac.backward_batch_async", scene_coords, out_gradients, hyp_assign)
+        if pose_records is not None:
+            _check_pose_records("esac.backward_batch_async", "poseRecords", pose_records, B, True, self.device)
         if isinstance(gt_poses, torch.Tensor) and gt_poses.is_cuda:
             gt = gt_poses
         else:
@@ -407,13 +477,15 @@ class Engine:
         table = None
         if cams is not None:
             table = _cams_arg(cams, B, "esac.backward_batch_async")
+        if pose_records is not None:
+            self._arm_pose_records("esac.backward_batch_async", "poseRecords", pose_records, B, True)
         rc = self.lib.esac_hip_backward_batch_dev(
             self.ctx, B, sc.data_ptr(), sc_stride, out_gradients.data_ptr(), int(out_gradients.stride(0)), ha.data_ptr(),
             gt.data_ptr(), table.ctypes.data if table is not None else None, float(w_rot), float(w_trans), float(loss_cut),
             C.byref(params), self._stream(), out.data_ptr())
         if rc != 0:
             _check(rc, self.lib)
-        self._keep = (sc, ha, out_gradients, gt, out)  # alive until the kernels have run
+        self._keep = (sc, ha, out_gradients, gt, out, pose_records)  # alive until the kernels have run
         return out
 
     def _upload(self, host, dtype):
@@ -684,7 +756,8 @@ class Engine:
 # The reference keeps a static RNG whose state advances from call to call
 # (thread_rand.cpp:4-5); here that state is (seed, call counter).
 _state = {"seed": 1305, "call": 0, "engines": {}, "last": None, "max_tries": 0, "max_ref_steps": -1, "fwd_cache": {},
-          "exact_scores": None, "exact_sampling": False, "strict_reference": False, "strict_training": False}
+          "exact_scores": None, "exact_sampling": False, "strict_reference": False, "strict_training": False,
+          "pose_records": None}
 
 
 def set_seed(seed, call=0):
@@ -731,6 +804,23 @@ def set_strict_training(on):
     non-finite scene coordinates (the call returns a NaN loss and NaN gradients instead of raising), the plain CvLevMarq trial
     test in the slot refinement, the SVD pseudo-inverse on every slot.  A verification route; forward() ignores it."""
     _state["strict_training"] = bool(on)
+
+
+def set_pose_records(records):
+    """Arms the NEXT training call of this module (backward, backward_batch, backward_batch_async): a float64 tensor [32] (backward)
+    or [B,32] (the batched calls), filled in place with the forward-format record (RES_*) of each frame's argmax hypothesis, as the
+    batched calls' poseRecords argument does -- `backward` keeps the reference's parameter list, so this is its route.  One-shot:
+    taken by that call whether it runs or raises; None disarms.  Shape and device are checked again by the call."""
+    if records is not None:
+        B = records.shape[0] if isinstance(records, torch.Tensor) and records.dim() == 2 else None
+        _check_pose_records("esac.set_pose_records", "records", records, B, False)
+    _state["pose_records"] = records
+
+
+def _take_pose_records(given):
+    """The record tensor of this call: its own argument, else what set_pose_records left (consumed either way)."""
+    armed, _state["pose_records"] = _state["pose_records"], None
+    return given if given is not None else armed
 
 
 def _no_strict_training(who):
@@ -930,7 +1020,12 @@ def backward(sceneCoordinates, outGradients, hypAssignment, gtPose, wLossRot, wL
     zeros: train_esac.py:148). Returns the expected loss as a Python float.
 
     Tensors may live on the CPU (as train_esac.py:152-155 passes them) or on the GPU; with device tensors nothing
-    but the ground-truth pose and the loss value crosses PCIe."""
+    but the ground-truth pose and the loss value crosses PCIe.
+    Pose record (new; the parameter list is the reference's and stays): `set_pose_records(t)` before the call, t a float64 tensor
+    [32], CPU or device, filled in place with the forward-format record (RES_*) of the call's argmax hypothesis -- the pose
+    `forward` with the same counter returns, refined by the training call itself.  RES_VALID 0 and a NaN pose: the winner's
+    probability was below 1e-3 (possible from N > 1000) or nothing was selected."""
+    poseRecord = _take_pose_records(None)
     _no_strict_training("esac.backward")
     if sceneCoordinates.dtype != torch.float32 or sceneCoordinates.dim() != 4 or sceneCoordinates.size(1) != 3:
         raise RuntimeError("esac.backward: sceneCoordinates must be float32 [E,3,H,W]")
@@ -940,6 +1035,9 @@ def backward(sceneCoordinates, outGradients, hypAssignment, gtPose, wLossRot, wL
         raise RuntimeError("esac.backward: hypAssignment must be a non-empty int64 [N]")
     if gtPose.dtype != torch.float32 or tuple(gtPose.shape) != (4, 4):
         raise RuntimeError("esac.backward: gtPose must be float32 [4,4]")
+    if poseRecord is not None:
+        _check_pose_records("esac.backward", "poseRecord", poseRecord, None, False,
+                            sceneCoordinates.device if sceneCoordinates.is_cuda else None)
     dev = sceneCoordinates.device.index if sceneCoordinates.is_cuda else None
     eng = engine(dev)
     E, _, H, W = sceneCoordinates.shape
@@ -956,7 +1054,7 @@ def backward(sceneCoordinates, outGradients, hypAssignment, gtPose, wLossRot, wL
     in_place = outGradients.is_cuda and outGradients.is_contiguous() and outGradients.device == eng.device
     grads = outGradients if in_place else outGradients.to(eng.device).contiguous()
     out = eng.backward_device(sceneCoordinates, grads, hypAssignment, gtPose.detach().cpu().numpy(), wLossRot, wLossTrans,
-                              lossCut, p)
+                              lossCut, p, pose_record=poseRecord)
     if not in_place:
         outGradients.copy_(grads)  # the accumulated tensor back into the caller's (CPU or strided) storage
     _state["last"] = {"backward": out}
@@ -988,16 +1086,22 @@ def _check_batch_tensors(who, sceneCoordinates, outGradients, hypAssignment, gtP
 
 
 def backward_batch(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLossRot, wLossTrans, lossCut, shiftX, shiftY,
-                   focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling):
+                   focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling, *, poseRecords=None):
     """Batched companion of `backward` (new API): sceneCoordinates [B,E,3,H,W] (or [E,3,H,W] shared by all frames),
     outGradients float32 [B,E,3,H,W] accumulated into in place, hypAssignment [B,N] int64, gtPoses [B,4,4] float32.  Returns
     the list of the B expected losses.  Frame b is what the b-th of B consecutive `backward` calls would compute (the same
     hypotheses, slots and losses; the gradient bit for bit when the single calls refine their slots with one workgroup each:
     include/esac_hip.h).  Advances the call counter by B.
     Each of shiftX, shiftY, focalLength, ppointX, ppointY is a scalar (the whole batch) or a length-B sequence / 1-D tensor /
-    numpy array: frame b uses element b (a training mini-batch: one random shift and one focal length per image)."""
+    numpy array: frame b uses element b (a training mini-batch: one random shift and one focal length per image).
+    poseRecords (keyword only; or `set_pose_records` before the call): a float64 tensor [B,32], CPU or device, filled in place:
+    row b is frame b's record as `backward` describes it."""
+    poseRecords = _take_pose_records(poseRecords)
     _no_strict_training("esac.backward_batch")
     B, N, E, H, W = _check_batch_tensors("esac.backward_batch", sceneCoordinates, outGradients, hypAssignment, gtPoses, name_each=False)
+    if poseRecords is not None:
+        _check_pose_records("esac.backward_batch", "poseRecords", poseRecords, B, False,
+                            sceneCoordinates.device if sceneCoordinates.is_cuda else None)
     if not hypAssignment.is_cuda:
         lo, hi = int(hypAssignment.min()), int(hypAssignment.max())
         if lo < 0 or hi >= E:
@@ -1013,7 +1117,7 @@ def backward_batch(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLoss
     in_place = outGradients.is_cuda and outGradients.is_contiguous() and outGradients.device == eng.device
     grads = outGradients if in_place else outGradients.to(eng.device).contiguous()
     out = eng.backward_batch(sceneCoordinates, grads, hypAssignment, gtPoses.detach().cpu().numpy(), wLossRot, wLossTrans,
-                             lossCut, p, cams=cams)
+                             lossCut, p, cams=cams, pose_records=poseRecords)
     if not in_place:
         outGradients.copy_(grads)  # the accumulated tensors back into the caller's (CPU or strided) storage
     _state["last"] = {"backward": out}
@@ -1021,7 +1125,8 @@ def backward_batch(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLoss
 
 
 def backward_batch_async(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLossRot, wLossTrans, lossCut, shiftX, shiftY,
-                         focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling):
+                         focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling, *,
+                         poseRecords=None):
     """`backward_batch` without a host round trip (esac_hip_backward_batch_dev): the call returns once its launches are enqueued on
     torch's current stream and reads its inputs in stream order, so the networks that produce them may still be running and the
     autograd backward can be enqueued behind it at once.  sceneCoordinates, hypAssignment and a contiguous outGradients must be
@@ -1029,10 +1134,16 @@ def backward_batch_async(sceneCoordinates, outGradients, hypAssignment, gtPoses,
     or on the host (uploaded asynchronously).  Returns the [B] DEVICE tensor of expected losses (float64; column 0 of the
     record); last_result()["backward"] holds the [B,4] device record.  A singular ground-truth pose or an out-of-range
     assignment is a per-frame outcome (record[b,3] = 2 / 1, engine().check() raises after a synchronisation).
-    Advances the call counter by B.  The camera arguments are host values, as in backward_batch."""
+    Advances the call counter by B.  The camera arguments are host values, as in backward_batch.
+    poseRecords (keyword only; or `set_pose_records` before the call): a contiguous DEVICE float64 tensor [B,32], written in
+    stream order: row b is frame b's record as `backward` describes it (RES_VALID 0 for a frame with a singular ground truth);
+    `eval_batch` may be enqueued right behind the call."""
     who = "esac.backward_batch_async"
+    poseRecords = _take_pose_records(poseRecords)
     _no_strict_training(who)
     B, N, E, H, W = _check_batch_tensors(who, sceneCoordinates, outGradients, hypAssignment, gtPoses, name_each=True)
+    if poseRecords is not None:
+        _check_pose_records(who, "poseRecords", poseRecords, B, True, sceneCoordinates.device if sceneCoordinates.is_cuda else None)
     (shiftX, shiftY, focalLength, ppointX, ppointY), cams = _per_frame_cams(who, B, shiftX, shiftY, focalLength, ppointX, ppointY)
     if not outGradients.is_contiguous():
         raise RuntimeError("%s: outGradients must be contiguous (an asynchronous call cannot copy back into strided storage)" % who)
@@ -1051,6 +1162,7 @@ def backward_batch_async(sceneCoordinates, outGradients, hypAssignment, gtPoses,
                         max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"],
                         strict_training=_state["strict_training"])
     _state["call"] += B
+    eng.arm_pose_records(poseRecords)
     rec = eng.backward_batch_async(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLossRot, wLossTrans, lossCut, p, cams=cams)
     _state["last"] = {"backward": rec}
     return rec[:, 0]

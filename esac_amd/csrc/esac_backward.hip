@@ -9,6 +9,7 @@
 //   K8 k_bwd_path2       score -> scene coordinates (direct + via the 4 sampled points)        esac_derivative.h:205-330
 //   K9 k_bwd_accumulate  outGradients += p_h * pathI_h + pathII_h, hypotheses in order          esac.cpp:491-508
 //      k_bwd_gt_prepare  per-frame ground truth of the asynchronous batch, on the device          esac_util.h:555-568
+//      k_bwd_pose_record the argmax hypothesis' refined pose as a forward-format record (armed calls)  esac.cpp:153-187
 //
 // The reference allocates per-hypothesis (1 x 3P) and (P x 3) double matrices on the host heap for ALL N
 // hypotheses and adds them into the float tensor one hypothesis after the other.  Here only the <= 1000
@@ -20,10 +21,12 @@
 #include <stdint.h>
 
 #include "bwd_math.hpp"
+#include "bwd_record_math.hpp"
 #include "device_common.hpp"
 #include "esac_kernels.hpp"
 #include "gt_math.hpp"
 #include "pose_math.hpp"
+#include "select_math.hpp"
 
 namespace esac {
 
@@ -208,6 +211,40 @@ __global__ __launch_bounds__(64) void k_bwd_gt_prepare(const float* __restrict__
     for (int k = 0; k < 16; k++) g[k] = ok ? gt[k] : __builtin_nan("");
     for (int k = 0; k < 6; k++) g[16 + k] = ok ? gt_pose[k] : __builtin_nan("");
     status[b] = ok ? 0 : 2;
+}
+
+// ================================================================= the winner's refined pose as a forward record
+// esac_hip_set_bwd_pose_records armed this call: frame b's ESAC_RES_* record of its ARGMAX hypothesis -- the hypothesis the forward
+// call with the same (seed, call) refines -- from what the selection and the slot refinement left in the workspace.  One workgroup
+// per frame, directly behind the slot refinement; reads only, beside the record itself.  The argmax is draw's (select_math.hpp:
+// highest score, first global index on ties, a NaN never wins, hypothesis 0 when nothing can win -- refine_pick_winner's rule
+// through the same two functions; every score of a training call is exact).  A winner without a slot gets the no-slot record
+// (bwd_record_math.hpp).  All 32 doubles are written on every pass, so the rerun after a slot overflow or a slot-team time-out
+// overwrites what the aborted pass left.
+static_assert(BWD_REC_SCORE == ESAC_RES_SCORE_K && BWD_REC_HYP == ESAC_RES_HYP_K && BWD_REC_EXPERT == ESAC_RES_EXPERT_K &&
+              BWD_REC_RVEC == ESAC_RES_RVEC_K && BWD_REC_POSE == ESAC_RES_POSE_K && BWD_REC_REF_STEPS == ESAC_RES_REF_STEPS_K &&
+              BWD_REC_INLIERS == ESAC_RES_INLIERS_K && BWD_REC_PROB == ESAC_RES_PROB_K && BWD_REC_ENTROPY == ESAC_RES_ENTROPY_K &&
+              BWD_REC_CONTENDERS == ESAC_RES_CONTENDERS_K && BWD_REC_LM_ITERS == ESAC_RES_LM_ITERS_K, "record layout");
+template <int B>
+__global__ __launch_bounds__(B) void k_bwd_pose_record(KArgs a) {
+    __shared__ double s_best[B / 64];
+    __shared__ int s_besti[B / 64], s_bestg[B / 64];
+    // (both indexed by the frame of the launch, not moved by the frame's view)
+    double* const rec = a.bwd.pose_rec + (size_t)blockIdx.y * BWD_REC_DOUBLES;
+    const bool dead = a.bwd.frame_status && a.bwd.frame_status[blockIdx.y] == 2;  // singular ground truth: k_bwd_loss reports entropy 0
+    frame_view(a);
+    bwd_frame_view(a, (int)blockIdx.y);
+    double bs = -INFINITY;
+    int bi = BEST_NONE, bg = BEST_NONE;
+    for (int h = threadIdx.x; h < a.N; h += B) best_take(bs, bi, bg, a.scores[h], h, global_hyp(a, h));
+    block_best<B, false>(bs, bi, bg, s_best, s_besti, s_bestg);
+    if (threadIdx.x != 0) return;
+    const int win = bi == BEST_NONE ? 0 : bi;
+    // the slots were refined by teams and one of them timed out: ref_hyps / map_info are not to be trusted (the host refines again)
+    const bool team_failed = a.bwd.team && __hip_atomic_load(a.coop_counter + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.bwd.team_tag;
+    const BwdRecordHead head{a.scores[win], global_hyp(a, win), expert_of(a, win) + a.expert_base, a.bwd.probs[win],
+                             dead ? 0.0 : a.stats[2], a.N};
+    bwd_record_frame(head, win, a.bwd.sel, a.bwd.n_sel[0] /* = min(n_sel, cap) */, !team_failed, a.bwd.ref_hyps, a.bwd.map_info, rec);
 }
 
 // ================================================================= K7: path I
@@ -600,6 +637,9 @@ void launch_bwd_paths(const KArgs& a, hipStream_t s) {
 }
 void launch_bwd_gt_prepare(const float* d_gt_poses, int B, double* gt_frames, int* status, hipStream_t s) {
     hipLaunchKernelGGL(k_bwd_gt_prepare, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, d_gt_poses, B, gt_frames, status);
+}
+void launch_bwd_pose_record(const KArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_bwd_pose_record<256>, dim3(1, a.frames), dim3(256), 0, s, a);
 }
 void launch_bwd_accumulate(const KArgs& a, hipStream_t s) {
     const int per_expert = 3 * a.H * a.W;

@@ -126,6 +126,9 @@ struct esac_hip_ctx {
     double* d_gt_dev = nullptr;               // [ESAC_MAX_BATCH,22] written by k_bwd_gt_prepare in stream order
     int* d_frame_status = nullptr;            // [ESAC_MAX_BATCH] per-frame outcome of the most recent such call (BwdArgs::frame_status)
     int last_dev_batch = 0;                   // its B while it is the most recent call on the context (esac_hip_check reads that many words)
+    // esac_hip_set_bwd_pose_records: what the NEXT training call writes its forward-format records to (one-shot: take_pose_arm)
+    double* pose_rec = nullptr;               // DEVICE [pose_rec_frames, ESAC_RES_DOUBLES], null: not armed
+    int pose_rec_frames = 0;
     // per-frame cameras of a batch (esac_hip_forward_batch_cams / esac_hip_backward_batch_cams)
     FrameCam* h_cams = nullptr;               // pinned staging [ESAC_MAX_BATCH]: the caller's array is free when the call returns
     FrameCam* d_cams = nullptr;               // ... and the table the kernels read (KArgs::cams)
@@ -1264,7 +1267,30 @@ struct BwdCall {
     bool batch = false;                // the batch-wide overflow word (BwdArgs::sel_max)
     int* frame_status = nullptr;       // asynchronous batch only: [B] per-frame outcomes and
     double* rec_dev = nullptr;         // [B,4] the caller's device records
+    double* pose_rec = nullptr;        // [B,ESAC_RES_DOUBLES] the caller's device records of the winners' refined poses (an armed call)
 };
+
+// esac_hip_set_bwd_pose_records armed the context for the NEXT training call: every training entry point takes the arming when
+// it is entered, whatever becomes of the call (one-shot, consumed by a rejected call too).
+struct PoseArm {
+    double* rec = nullptr;
+    int frames = 0;
+};
+static PoseArm take_pose_arm(esac_hip_ctx* c) {
+    PoseArm arm;
+    if (!c) return arm;
+    arm.rec = c->pose_rec;
+    arm.frames = c->pose_rec_frames;
+    c->pose_rec = nullptr;
+    c->pose_rec_frames = 0;
+    return arm;
+}
+// ... and checks it against the call's frames before anything is launched
+static int check_pose_arm(const char* who, const PoseArm& arm, int B) {
+    if (arm.rec && arm.frames < B)
+        return fail(-4, "%s: esac_hip_set_bwd_pose_records armed %d frame(s), the call has %d", who, arm.frames, B);
+    return 0;
+}
 
 // a.bwd of one selection .. accumulation pass over `frames` frames from frame b0 of the call, `cap` slots each, in the context's
 // slot workspace (which ensure_bws has sized).  Every field a route does not use is null / 0 here, in this one place.
@@ -1289,6 +1315,7 @@ static void fill_bwd(esac_hip_ctx* c, KArgs& a, const BwdCall& call, int b0, int
     if (!call.batch) a.bwd.sel_max = nullptr;
     a.bwd.frame_status = call.frame_status ? call.frame_status + b0 : nullptr;
     a.bwd.rec_dev = call.rec_dev ? call.rec_dev + (size_t)b0 * 4 : nullptr;
+    a.bwd.pose_rec = call.pose_rec ? call.pose_rec + (size_t)b0 * ESAC_RES_DOUBLES : nullptr;
 }
 
 // Selection .. accumulation of a.bwd's frames on `s`: enqueues and returns; a caller that wants the outcome waits for it.
@@ -1309,6 +1336,10 @@ static int enqueue_bwd_chain(esac_hip_ctx* c, KArgs& a, hipStream_t s, double* r
     }
     launch_refine_slots(a, s);                                  // one workgroup per slot otherwise
     if ((rc = check_launch("k_refine(slots)"))) return rc;
+    if (a.bwd.pose_rec) {                                       // an armed call: the winner's refined pose as a forward record
+        launch_bwd_pose_record(a, s);
+        if ((rc = check_launch("k_bwd_pose_record"))) return rc;
+    }
     launch_bwd_loss(a, s);                                      // esac.cpp:354-362 + dLoss + softmax derivative (+ rec_dev)
     if ((rc = check_launch("k_bwd_loss"))) return rc;
     launch_bwd_paths(a, s);                                     // esac.cpp:375-463 (path I) and :470-488 (path II), side by side
@@ -1319,9 +1350,19 @@ static int enqueue_bwd_chain(esac_hip_ctx* c, KArgs& a, hipStream_t s, double* r
     return check_launch("k_bwd_accumulate");
 }
 
+// Arms the next training call on the context (include/esac_hip.h): a pointer and a count, nothing is launched or waited for.
+extern "C" int esac_hip_set_bwd_pose_records(esac_hip_ctx* c, double* d_records, int frames) {
+    if (!c) return fail(-1, "null context");
+    if (d_records && frames < 1) return fail(-4, "esac_hip_set_bwd_pose_records: frames = %d (at least 1 with a record buffer)", frames);
+    c->pose_rec = d_records;
+    c->pose_rec_frames = d_records ? frames : 0;
+    return 0;
+}
+
 extern "C" int esac_hip_backward(esac_hip_ctx* c, const float* d_sc, float* d_out_gradients, const int64_t* d_assign,
                                  const float* h_gt_pose, float w_loss_rot, float w_loss_trans, float loss_cut,
                                  const esac_hip_params* p, void* stream, double* h_out) {
+    const PoseArm arm = take_pose_arm(c);
     if (!d_out_gradients || !h_gt_pose) return fail(-1, "esac_hip_backward: null gradient tensor or ground-truth pose");
     if (!c) return fail(-1, "null context");
     if (p && (p->flags & ESAC_FLAG_STRICT_REFERENCE))
@@ -1333,6 +1374,7 @@ extern "C" int esac_hip_backward(esac_hip_ctx* c, const float* d_sc, float* d_ou
     if (p->E > 65535) return fail(-4, "esac_hip_backward: at most 65535 experts (one grid row per expert in the accumulation kernel)");
     if (p->d_hyp_index || p->hyp_offset)
         return fail(-4, "esac_hip_backward: sharded calls are not supported (the expectation needs every hypothesis)");
+    if ((rc = check_pose_arm("esac_hip_backward", arm, 1))) return rc;
     const int P = p->H * p->W;
     // Slot workspace (two 3P-double slabs + two inlier maps per slot).  How many hypotheses reach PROB_THRESH is only
     // known on the device: a blocking call starts from what earlier calls needed (at least 64 slots) and, when the
@@ -1350,6 +1392,7 @@ extern "C" int esac_hip_backward(esac_hip_ctx* c, const float* d_sc, float* d_ou
     BwdCall call = {d_out_gradients, 0, w_loss_rot, w_loss_trans, loss_cut};
     call.gt = gt;
     call.gt_pose = gt_pose;
+    call.pose_rec = arm.rec;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = enqueue_bwd_sampling(c, a, s, false))) return rc;
     // A blocking call can refine again with one workgroup per slot should a slot team time out; an asynchronous one cannot and
@@ -1407,9 +1450,11 @@ extern "C" int esac_hip_backward_batch_cams(esac_hip_ctx* c, int B, const float*
                                             int64_t grad_frame_stride, const int64_t* d_assign, const float* h_gt_poses,
                                             const esac_hip_frame_cam* h_cams, float w_loss_rot, float w_loss_trans, float loss_cut,
                                             const esac_hip_params* p, void* stream, double* h_out) {
+    const PoseArm arm = take_pose_arm(c);
     int rc = check_batch_call("esac_hip_backward_batch", c, p, B, d_sc && d_out_gradients && d_assign && h_gt_poses, false, h_out,
                               sc_frame_stride, grad_frame_stride);
     if (rc) return rc;
+    if ((rc = check_pose_arm("esac_hip_backward_batch", arm, B))) return rc;
     DeviceGuard guard(c->device);
     hipStream_t s = (hipStream_t)stream;
     if (!c->h_gt) {
@@ -1431,6 +1476,7 @@ extern "C" int esac_hip_backward_batch_cams(esac_hip_ctx* c, int B, const float*
     BwdCall call = {d_out_gradients, grad_frame_stride, w_loss_rot, w_loss_trans, loss_cut};
     call.gt_frames = c->d_gt;
     call.batch = true;
+    call.pose_rec = arm.rec;
     const int N = p->N, P = p->H * p->W, worst = bwd_rows(N);
     int cap = c->bcap_batch > 64 ? c->bcap_batch : 64;
     if (cap > worst) cap = worst;
@@ -1485,9 +1531,11 @@ extern "C" int esac_hip_backward_batch_dev(esac_hip_ctx* c, int B, const float* 
                                            int64_t grad_frame_stride, const int64_t* d_assign, const float* d_gt_poses,
                                            const esac_hip_frame_cam* h_cams, float w_loss_rot, float w_loss_trans, float loss_cut,
                                            const esac_hip_params* p, void* stream, double* d_out) {
+    const PoseArm arm = take_pose_arm(c);
     int rc = check_batch_call("esac_hip_backward_batch", c, p, B, d_sc && d_out_gradients && d_assign && d_gt_poses, true, d_out,
                               sc_frame_stride, grad_frame_stride);
     if (rc) return rc;
+    if ((rc = check_pose_arm("esac_hip_backward_batch_dev", arm, B))) return rc;
     // the chunking is known before anything is launched: cap is the worst case, so the first chunk is the largest
     const int N = p->N, P = p->H * p->W, cap = bwd_rows(N);
     const long long fit = c->bwd_budget / ((long long)cap * bwd_slot_bytes(P));
@@ -1516,6 +1564,7 @@ extern "C" int esac_hip_backward_batch_dev(esac_hip_ctx* c, int B, const float* 
     call.batch = true;
     call.frame_status = c->d_frame_status;
     call.rec_dev = d_out;
+    call.pose_rec = arm.rec;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = B - b0 < chunk ? B - b0 : chunk;
         if ((rc = chunk_args(c, d_sc, sc_frame_stride, d_assign, p, h_cams, b0, nb, &a))) return rc;

@@ -111,6 +111,8 @@ struct BwdArgs {
     int* frame_status;               // [B] 0, or 2: the frame's ground-truth pose is singular (k_bwd_gt_prepare) -- the frame selects
                                      // nothing and adds nothing; k_bwd_loss sets 1 when the frame's assignment was out of range
     double* rec_dev;                 // [B,4] the caller's device records: k_bwd_loss writes frame b's four values itself
+    // esac_hip_set_bwd_pose_records armed this call; null otherwise (no launch).  Indexed by the frame of the launch like the two above
+    double* pose_rec;                // [B,32] the caller's device records: k_bwd_pose_record writes frame b's ESAC_RES_* record
 };
 
 constexpr int ESAC_SPEC_CNT_FAN = 32, ESAC_SPEC_CNT_STRIDE = 32;  // counters of the second level; ints between two counters (128 bytes)
@@ -275,6 +277,7 @@ void launch_bwd_select(const KArgs& a, hipStream_t s);
 void launch_bwd_loss(const KArgs& a, hipStream_t s);
 void launch_bwd_paths(const KArgs& a, hipStream_t s);  // path I and path II of every slot, one launch
 void launch_bwd_accumulate(const KArgs& a, hipStream_t s);
+void launch_bwd_pose_record(const KArgs& a, hipStream_t s);  // requires a.bwd.pose_rec; one workgroup per frame
 // float poses [B,4,4] (device) -> the [B,22] records of BwdArgs::gt_frames + status[b] = 0 / 2 (singular), in stream order
 void launch_bwd_gt_prepare(const float* d_gt_poses, int B, double* gt_frames, int* status, hipStream_t s);
 // rows of the per-slot tables (dloss, map_info) of one frame: the worst case, so that a batch's tables are frame-major [B,rows]

@@ -406,7 +406,8 @@ def clamp_probs(probs, n):
 
 def train_step(image, gt_pose, gating, experts, focal_length, hypotheses=256, threshold=10.0, inlier_alpha=100.0,
                inlier_beta=0.5, max_reprojection=100.0, subsample=8, weight_rot=1.0, weight_trans=100.0, loss_cut=100.0,
-               max_experts=-1, expert_selection=False, shift=None, generator=None, strict_training=False):
+               max_experts=-1, expert_selection=False, shift=None, generator=None, strict_training=False, evaluate=False,
+               gt_expert=None):
     """One iteration of the end-to-end training loop (train_esac.py:104-192) up to and including
     `torch.autograd.backward`; the optimiser step stays with the caller (`ensemble.update`, train_esac.py:195).
 
@@ -417,6 +418,10 @@ def train_step(image, gt_pose, gating, experts, focal_length, hypotheses=256, th
         E activity flags and the loss value reach the host.
     gating(image) -> log-probabilities [1,E] (with grad); experts[e](image) -> [1,3,H/s,W/s] (with grad).
     strict_training: this call's esac.backward follows the reference in every stage (esac.set_strict_training).
+    evaluate: the solver call also hands out its winner's refined pose as a forward record (esac.set_pose_records) and
+    esac.eval_batch(record, gt_pose, gt_expert) is enqueued right behind it: the pose error, the 5 cm / 5 deg flag and the gating
+    accuracy of the step without a forward call.  The dict gains `records` [1,32] and `eval` [1,16] (device tensors, api.RES_* /
+    api.EVAL_*; EVAL_STATUS 1: the winner held no slot, no pose).
     Returns dict(loss, e_hyps, e_hist, prediction, prediction_gradients, gating_log_probs, pad)."""
     dev = image.device
     E = len(experts)
@@ -445,12 +450,19 @@ def train_step(image, gt_pose, gating, experts, focal_length, hypotheses=256, th
     prediction_gradients = torch.zeros_like(prediction)
     strict_before = api._state["strict_training"]
     api.set_strict_training(strict_before or strict_training)
+    gt_t = torch.as_tensor(gt_pose, dtype=torch.float32)
+    records = torch.zeros((1, api.RES_DOUBLES), dtype=torch.float64, device=dev) if evaluate else None
     try:
-        loss = api.backward(prediction.detach(), prediction_gradients, e_hyps, torch.as_tensor(gt_pose, dtype=torch.float32).cpu(),
+        if evaluate:
+            api.set_pose_records(records[0])
+        loss = api.backward(prediction.detach(), prediction_gradients, e_hyps, gt_t.cpu(),
                             weight_rot, weight_trans, loss_cut, pad_x, pad_y, float(focal_length), pp_x, pp_y, threshold,
                             inlier_alpha, inlier_beta, max_reprojection, subsample)
     finally:
         api.set_strict_training(strict_before)
+    ev = None
+    if evaluate:
+        ev = api.eval_batch(records, gt_t.reshape(1, 4, 4), None if gt_expert is None else [int(gt_expert)])
     # gating gradients: REINFORCE-style, loss per drawn hypothesis (train_esac.py:171-177)
     if expert_selection:
         gating_grads = torch.zeros_like(gating_log_probs)
@@ -466,14 +478,17 @@ def train_step(image, gt_pose, gating, experts, focal_length, hypotheses=256, th
         grads.append(gating_grads)
     if tensors:
         torch.autograd.backward(tensors, grads)
-    return dict(loss=loss, e_hyps=e_hyps, e_hist=e_hist, prediction=prediction, prediction_gradients=prediction_gradients,
-                gating_log_probs=gating_log_probs, pad=(pad_x, pad_y))
+    out = dict(loss=loss, e_hyps=e_hyps, e_hist=e_hist, prediction=prediction, prediction_gradients=prediction_gradients,
+               gating_log_probs=gating_log_probs, pad=(pad_x, pad_y))
+    if evaluate:
+        out["records"], out["eval"] = records, ev
+    return out
 
 
 def train_batch(images, gt_poses, gating, experts, focal_lengths, hypotheses=256, threshold=10.0, inlier_alpha=100.0,
                 inlier_beta=0.5, max_reprojection=100.0, subsample=8, weight_rot=1.0, weight_trans=100.0, loss_cut=100.0,
                 max_experts=-1, expert_selection=False, shifts=None, e_hyps=None, generator=None, strict_training=False,
-                asynchronous=False, all_experts=False):
+                asynchronous=False, all_experts=False, evaluate=False, gt_experts=None):
     """The mini-batch form of `train_step`: B images through ONE `esac.backward_batch` with a shift and a focal length per
     image (train_esac.py:112 reads the focal length per image, :125 draws a new shift for every image), up to and including
     one `torch.autograd.backward`.
@@ -492,6 +507,10 @@ def train_batch(images, gt_poses, gating, experts, focal_lengths, hypotheses=256
     `torch.autograd.backward` contains no host synchronisation, given device `images`, a device `gt_poses` tensor and `e_hyps`
     drawn on the device.  What remains host-side: the shifts (drawn or given on the host, one pad per image) and the focal lengths,
     which travel as the call's per-frame camera table; a host `gt_poses` is uploaded asynchronously.
+    evaluate: the solver call is armed to hand out every frame's winner as a forward record (poseRecords) and
+    esac.eval_batch(records, gt_poses, gt_experts) is enqueued right behind it; the dict gains `records` [B,32] and `eval` [B,16],
+    device tensors (asynchronous: still no host synchronisation in the step, given a device `gt_experts` tensor or None).  A frame
+    whose winner held no slot -- a singular ground truth on the asynchronous route among them -- has EVAL_STATUS 1 and NaN figures.
     Returns dict(losses (list of B floats; asynchronous: device tensor [B]), e_hyps [B,N], e_hist [B,E], prediction [B,E,3,h,w],
     prediction_gradients, gating_log_probs [B,E], pads (list of B pairs))."""
     dev = images.device
@@ -548,17 +567,21 @@ def train_batch(images, gt_poses, gating, experts, focal_lengths, hypotheses=256
     strict_before = api._state["strict_training"]
     api.set_strict_training(strict_before or strict_training)
     gt_t = torch.as_tensor(np.asarray(gt_poses, np.float32) if not isinstance(gt_poses, torch.Tensor) else gt_poses, dtype=torch.float32)
+    # (zeros: a frame whose kernels never reach the record write reads RES_VALID = 0 -> EVAL_STATUS 1, not stale memory)
+    records = torch.zeros((B, api.RES_DOUBLES), dtype=torch.float64, device=dev) if evaluate else None
     try:
         if asynchronous:  # (a device gt_poses stays where it is)
             losses = api.backward_batch_async(prediction.detach(), prediction_gradients, e_hyps.contiguous(), gt_t,
                                               weight_rot, weight_trans, loss_cut, [p[0] for p in pads], [p[1] for p in pads], focals,
-                                              pp_x, pp_y, threshold, inlier_alpha, inlier_beta, max_reprojection, subsample)
+                                              pp_x, pp_y, threshold, inlier_alpha, inlier_beta, max_reprojection, subsample,
+                                              poseRecords=records)
         else:
             losses = api.backward_batch(prediction.detach(), prediction_gradients, e_hyps.contiguous(), gt_t.cpu(),
                                         weight_rot, weight_trans, loss_cut, [p[0] for p in pads], [p[1] for p in pads], focals, pp_x, pp_y,
-                                        threshold, inlier_alpha, inlier_beta, max_reprojection, subsample)
+                                        threshold, inlier_alpha, inlier_beta, max_reprojection, subsample, poseRecords=records)
     finally:
         api.set_strict_training(strict_before)
+    ev = api.eval_batch(records, gt_t, gt_experts) if evaluate else None  # behind the solver on the same stream: nothing is waited for
     # gating gradients, per frame: REINFORCE-style, loss per drawn hypothesis (train_esac.py:171-177)
     loss_t = losses.to(torch.float32) if asynchronous else torch.tensor(losses, device=dev, dtype=torch.float32)
     if expert_selection:
@@ -575,5 +598,8 @@ def train_batch(images, gt_poses, gating, experts, focal_lengths, hypotheses=256
         grads.append(gating_grads)
     if tensors:
         torch.autograd.backward(tensors, grads)
-    return dict(losses=losses, e_hyps=e_hyps, e_hist=e_hist, prediction=prediction, prediction_gradients=prediction_gradients,
-                gating_log_probs=gating_log_probs, pads=pads)
+    out = dict(losses=losses, e_hyps=e_hyps, e_hist=e_hist, prediction=prediction, prediction_gradients=prediction_gradients,
+               gating_log_probs=gating_log_probs, pads=pads)
+    if evaluate:
+        out["records"], out["eval"] = records, ev
+    return out

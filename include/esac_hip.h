@@ -455,6 +455,38 @@ int esac_hip_backward_batch_dev(esac_hip_ctx* ctx, int B, const float* d_scene_c
                                 const float* d_gt_poses, const esac_hip_frame_cam* h_cams, float w_loss_rot,
                                 float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* d_out);
 
+/*
+ * The winner's refined pose of a training call, as a forward record (new, additive: the ABI version stays).  A training call
+ * draws the hypotheses of the forward call with the same (seed, call), scores all of them in reference arithmetic and refines
+ * every hypothesis with p >= PROB_THRESH -- the argmax among them, for N <= 1000 always.  An armed call hands that one out in the
+ * ESAC_RES_* format, so a training loop that logs pose errors, the winning expert or gating accuracy needs no forward call
+ * beside it: esac_hip_eval_batch reads the records as it reads a forward batch's.
+ *
+ * Arms the NEXT training call on ctx (esac_hip_backward, _backward_batch, _batch_cams, _batch_dev): frame b's
+ * forward-format record goes to d_records + b * ESAC_RES_DOUBLES (DEVICE memory), in stream order.  One-shot: consumed
+ * by that call whether it is accepted or rejected.  NULL disarms.  frames < that call's B: the call returns -4 before
+ * anything is launched.
+ *
+ * The record of frame b (one small launch per chunk behind the slot refinement; an unarmed call launches what it always did):
+ *   ESAC_RES_HYP        the argmax of the frame's exact scores: highest score, first index on ties, a NaN never wins
+ *                       (hypothesis 0 when every score is NaN) -- the hypothesis esac_hip_forward refines at this (seed, call)
+ *   ESAC_RES_SCORE, _EXPERT (expert_base included), _PROB (the softmax value of the training call), _ENTROPY (the value of the
+ *                       call's own record, h_out / d_out [b*4+2]), _CONTENDERS (N: as a forward call under
+ *                       ESAC_FLAG_EXACT_SCORES, every score is exact)
+ *   ESAC_RES_RVEC|TVEC  the slot's refined pose; ESAC_RES_POSE its inverted 4x4 as floats; _REF_STEPS, _INLIERS, _LM_ITERS of
+ *                       the slot's refinement; ESAC_RES_VALID = 1.  The slot route and the forward's team sum the LM moments in
+ *                       different orders: poses agree to ~1e-8, the discrete fields exactly.
+ * NO SLOT: the winner's probability is below PROB_THRESH (possible from N > 1000 on a flat distribution), the frame selected
+ * nothing (a singular ground-truth pose on the asynchronous route, NaN scores under ESAC_FLAG_STRICT_TRAINING).  Then SCORE, HYP,
+ * EXPERT, PROB, ENTROPY and CONTENDERS stand, RVEC|TVEC and POSE are NaN, REF_STEPS, INLIERS and LM_ITERS are 0 and
+ * ESAC_RES_VALID is 0 -- "no record" to esac_hip_eval_batch (ESAC_EVAL_STATUS 1).
+ * All ESAC_RES_DOUBLES doubles of every frame of the call are written by every pass: a batch beyond the workspace budget runs in
+ * chunks and frame b's record still lands in row b; the second pass of a blocking call (slot overflow, a slot team that timed
+ * out) overwrites what the first left, so after a blocking call every row is final.  Sharded calls stay rejected.
+ * -1: null ctx.  -4: d_records with frames < 1.
+ */
+int esac_hip_set_bwd_pose_records(esac_hip_ctx* ctx, double* d_records, int frames);
+
 /* The same phases one at a time (asynchronous on `stream`), for stage-wise parity
  * tests and for callers that interleave other work.  Order: sample, score, select, refine. */
 int esac_hip_sample(esac_hip_ctx* ctx, const float* d_scene_coords, const int64_t* d_hyp_assign,

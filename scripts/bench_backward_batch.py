@@ -12,6 +12,9 @@ mean number of slots (hypotheses with p >= PROB_THRESH) per frame.
                                                               # shift (|shift| <= sub/2) and a focal length per frame
     python scripts/bench_backward_batch.py --asynchronous [--batches 8,32,128] [--steps 4] [--reps 5]
                                                               # Engine.backward_batch_async against the blocking batch (see main_async)
+    python scripts/bench_backward_batch.py --pose-records [--batches 1,8,32] [--steps 4] [--reps 5]
+                                                              # training calls armed with pose records against unarmed ones, and
+                                                              # against unarmed + one blocking forward per frame (see main_pose_records)
 """
 import argparse
 import json
@@ -148,6 +151,83 @@ def main_async(args):
             print(json.dumps(line), flush=True)
 
 
+def main_pose_records(args):
+    """--pose-records: what arming a training call costs, and what it saves a loop that logs poses.  Per (config, B), interleaved rep
+    by rep after a warm-up of all legs, K = --steps calls per timed run:
+      (u) unarmed: B = 1 `backward_device`, else `backward_batch` (blocking) -- and `backward_batch_async`, enqueued back to back;
+      (a) the same calls armed (device record tensors): one more small launch per chunk;
+      (f) unarmed + one blocking `forward_device` per frame at the same counter: what a training loop pays today for the pose.
+    One JSON line each: ms per frame of every leg (medians over --reps with min..max), armed - unarmed, and (f) - (a)."""
+    eng = api.Engine(0)
+    batches = [int(x) for x in (args.batches if args.batches != "1,8,32,128" else "1,8,32").split(",")]
+    K = args.steps
+    for name in args.configs.split(","):
+        cfg = CONFIGS[name]
+        f0, sc_all, ha_all, gts_all, _ = make_inputs(cfg, max(batches))
+        E, _, H, W = f0["coords"].shape
+        grads = torch.zeros((max(batches), E, 3, H, W), dtype=torch.float32, device="cuda")
+        gt_dev_all = torch.from_numpy(gts_all).cuda()
+        for B in batches:
+            sc, ha, gts, gt_dev, g = sc_all[:B], ha_all[:B], gts_all[:B], gt_dev_all[:B], grads[:B]
+            recs = torch.zeros((B, api.RES_DOUBLES), dtype=torch.float64, device="cuda")
+            out4 = torch.empty((B, 4), dtype=torch.float64, device="cuda")
+
+            def params(call, **kw):
+                return eng.make_params(E, H, W, cfg["N"], focal=f0["focal"], ppx=f0["ppx"], ppy=f0["ppy"], sub_sampling=f0["sub"],
+                                       inlier_alpha=100.0, call=call, **kw)
+
+            def blocking(armed, forward=False):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for k in range(K):
+                    if B == 1:
+                        out = eng.backward_device(sc[0], g[0], ha[0], gts[0], 1.0, 100.0, 100.0, params(k),
+                                                  pose_record=recs[0] if armed else None)[None]
+                    else:
+                        out = eng.backward_batch(sc, g, ha, gts, 1.0, 100.0, 100.0, params(k * B), pose_records=recs if armed else None)
+                    if forward:
+                        for b in range(B):
+                            eng.forward_device(sc[b], ha[b], params(k * B + b, exact_scores="auto"))
+                torch.cuda.synchronize()
+                return time.perf_counter() - t0, out
+
+            def asynchronous(armed):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for k in range(K):
+                    eng.arm_pose_records(recs if armed else None)
+                    eng.backward_batch_async(sc, g, ha, gt_dev, 1.0, 100.0, 100.0, params(k * B), out=out4)
+                torch.cuda.synchronize()
+                return time.perf_counter() - t0
+
+            out = blocking(True, forward=True)[1]  # warm-up of every leg (the workspaces grow here)
+            blocking(False)
+            asynchronous(True)
+            asynchronous(False)
+            eng.check()
+            assert float(recs[:, api.RES_VALID].min()) == 1.0, "a frame's winner held no slot: the armed legs would time the no-slot record"
+            rows = {"u": [], "a": [], "f": [], "u_async": [], "a_async": []}
+            for _ in range(args.reps):
+                rows["u"].append(blocking(False)[0])
+                rows["a"].append(blocking(True)[0])
+                rows["f"].append(blocking(False, forward=True)[0])
+                rows["u_async"].append(asynchronous(False))
+                rows["a_async"].append(asynchronous(True))
+            ms = {k: 1e3 * np.asarray(v) / (K * B) for k, v in rows.items()}
+            med = lambda v: round(float(np.median(v)), 4)
+            spread = lambda v: [round(float(np.min(v)), 4), round(float(np.max(v)), 4)]
+            line = {"config": name, "B": B, "E": E, "N": cfg["N"], "grid": "%dx%d" % (H, W), "steps": K, "reps": args.reps,
+                    "slots_per_frame": round(float(out[:, 1].mean()), 2), "route": "backward_device" if B == 1 else "backward_batch"}
+            for key, label in (("u", "unarmed"), ("a", "armed"), ("f", "unarmed_plus_forward"), ("u_async", "async_unarmed"),
+                               ("a_async", "async_armed")):
+                line[label + "_ms_per_frame"] = med(ms[key])
+                line[label + "_spread"] = spread(ms[key])
+            line["arming_costs_ms_per_frame"] = round(line["armed_ms_per_frame"] - line["unarmed_ms_per_frame"], 4)
+            line["async_arming_costs_ms_per_frame"] = round(line["async_armed_ms_per_frame"] - line["async_unarmed_ms_per_frame"], 4)
+            line["saved_against_a_forward_per_frame_ms"] = round(line["unarmed_plus_forward_ms_per_frame"] - line["armed_ms_per_frame"], 4)
+            print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--asynchronous", action="store_true",
@@ -162,7 +242,11 @@ def main():
                     help="also time every (config, B) with a shift and a focal length per frame (one more JSON line, cams=per-frame)")
     ap.add_argument("--strict-training", action="store_true",
                     help="every call with ESAC_FLAG_STRICT_TRAINING (the verification route: each JSON line says strict_training=true)")
+    ap.add_argument("--pose-records", action="store_true",
+                    help="training calls armed with pose records against unarmed ones, and against unarmed + a blocking forward per frame")
     args = ap.parse_args()
+    if args.pose_records:
+        return main_pose_records(args)
     if args.asynchronous:
         return main_async(args)
     eng = api.Engine(0)
