@@ -80,3 +80,19 @@ def build_sample_plan_probe(force=False):
     if force or not os.path.exists(PLAN_LIB) or any(os.path.getmtime(d) > os.path.getmtime(PLAN_LIB) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fPIC", "-shared", PLAN_SRC, "-o", PLAN_LIB])
     return PLAN_LIB
+
+
+POLICY_SRC = os.path.join(HERE, "call_policy_probe.cpp")
+POLICY_LIB = os.path.join(HERE, "libcall_policy_probe.so")
+POLICY_EXE = os.path.join(HERE, "call_policy_probe_san")
+
+
+def build_call_policy_probe(force=False, sanitized_program=False):
+    """Host build of the C ABI host's decisions (call_policy.hpp needs no HIP header: the host compiler alone).
+    sanitized_program: the same source as a stand-alone program (its own main) under AddressSanitizer and UBSan."""
+    out = POLICY_EXE if sanitized_program else POLICY_LIB
+    deps = [POLICY_SRC, os.path.join(CSRC, "call_policy.hpp"), os.path.join(HERE, "..", "..", "include", "esac_hip.h")]
+    if force or not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        how = ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DCALL_POLICY_PROBE_MAIN"] if sanitized_program else ["-fPIC", "-shared"]
+        subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + how + [POLICY_SRC, "-o", out])
+    return out

@@ -842,3 +842,65 @@ def test_grids_at_the_lower_edge_of_the_team(engine, oracle, H, W):
     np.testing.assert_array_equal(engine.read(api.BUF_INLIER_COUNTS), ref["inlier_counts"])
     np.testing.assert_array_equal(engine.read(api.BUF_INLIER_MAP), ref["inlier_map"])
     np.testing.assert_allclose(rec[api.RES_RVEC:api.RES_RVEC + 6], ref["refined"], rtol=0, atol=1e-6)
+
+
+# (call, E, N, H, W, sub-sampling, score shape) -- 6x8: the smallest workspace; 32x32 tiled: the tiled-score workspace comes into
+# being; 96x96 (P > 8192): the training workspace regrows with its correspondence lists; then the first two shapes again
+_REGROW_STEPS = [("forward", 1, 16, 6, 8, 80, "auto"), ("forward", 2, 64, 32, 32, 15, "tiled"), ("backward", 1, 16, 6, 8, 80, "auto"),
+                 ("backward", 1, 16, 96, 96, 5, "auto"), ("forward", 1, 16, 6, 8, 80, "auto"), ("backward", 1, 16, 6, 8, 80, "auto")]
+
+
+def _regrow_call(eng, step):
+    """One call of the sequence on `eng`: everything the call hands out, by name.  The key (seed, call) and the inputs depend on
+    the step's shape only, so the repeats at the end of the sequence are the calls of its beginning."""
+    kind, E, N, H, W, sub, shape = step
+    f = S.make_frame(700 + H, E=E, H=H, W=W, sub=sub)
+    ha = S.gating_assignment(f, N, mode="gating")
+    sc, hat = torch.from_numpy(f["coords"]).cuda(), torch.from_numpy(ha).cuda()
+    p = eng.make_params(E, H, W, N, seed=77, call=H + (1000 if kind == "backward" else 0), refine_solo=True, score_shape=shape, **_kw(f))
+    out = {}
+    if kind == "forward":
+        scores = torch.empty(N, dtype=torch.float64, device="cuda")
+        out["record"] = eng.forward_device(sc, hat, p, scores_out=scores).copy()
+        out["scores"] = scores.cpu().numpy()
+    else:
+        gt = f["gt_pose"].astype(np.float32)
+        gt[:3, 3] += np.float32(0.03)
+        grads = torch.zeros_like(sc)
+        rec = torch.zeros(api.RES_DOUBLES, dtype=torch.float64, device="cuda")
+        out["values"] = eng.backward_device(sc, grads, hat, gt, 1.0, 100.0, 100.0, p, pose_record=rec).copy()
+        out["record"] = rec.cpu().numpy()
+        out["scores"] = eng.read(api.BUF_SCORES)
+        out["gradients"] = grads.cpu().numpy()
+    out["tries"] = eng.read(api.BUF_TRIES)
+    out["sample_xy"] = eng.read(api.BUF_SAMPLE_XY)
+    return out
+
+
+def _regrow_runs():
+    """The sequence on ONE engine, and every call of it on a fresh engine of its own."""
+    eng = api.Engine(0)
+    return [_regrow_call(eng, s) for s in _REGROW_STEPS], [_regrow_call(api.Engine(0), s) for s in _REGROW_STEPS]
+
+
+def test_a_regrown_workspace_is_invisible():
+    """One engine runs _REGROW_STEPS in order: its forward workspace grows twice, its tiled-score workspace comes into being, its
+    training workspace grows and then regrows with the correspondence lists of a grid above the LDS limit.  Every call must hand out
+    what a fresh engine hands out for it, and the repeats at the end (steps 5, 6) what steps 1 and 3 handed out: record, score
+    vector, tries, sampled cells, the four training values, the gradient tensor.  All with ESAC_FLAG_REFINE_SOLO and fixed keys.
+    EXACT equality for every field, by reasoning and not yet by a measurement on the commit before the workspace owners existed (to
+    be made with the first GPU run of this test): tries and sampled cells are functions of the RNG key (tests/test_gpu_parity.py
+    holds them equal to the oracle's); no kernel adds floating-point values with atomics (every atomic in esac_amd/csrc is an
+    integer counter or ticket), every sum runs in an order fixed by the launch shape, and with ESAC_FLAG_REFINE_SOLO one workgroup
+    refines -- so scores, record, training values and gradients depend on the call's inputs and shape alone.  A field that turns
+    out not to be bit-reproducible on that commit gets the tolerance tests/test_gpu_parity.py uses for it, and is named here."""
+    seq, fresh = _regrow_runs()
+    for k, (a, b) in enumerate(zip(seq, fresh)):
+        assert a.keys() == b.keys()
+        for name in a:
+            print("step", k + 1, name, "differing elements:", int(np.sum(~((a[name] == b[name]) | ((a[name] != a[name]) & (b[name] != b[name]))))))
+            np.testing.assert_array_equal(a[name], b[name], err_msg="step %d %s against a fresh engine" % (k + 1, name))
+    for first, again in ((0, 4), (2, 5)):
+        for name in seq[first]:
+            np.testing.assert_array_equal(seq[first][name], seq[again][name], err_msg="step %d %s against its repeat" % (first + 1, name))
+    assert seq[3]["values"][1] >= 1 and np.abs(seq[3]["gradients"]).max() > 0  # (the large grid refined slots and produced gradients)
