@@ -141,7 +141,12 @@ __device__ __forceinline__ double lane_bc(double x) {
     return __builtin_amdgcn_update_dpp(u, x, 0x150 + K, 0xf, 0xf, false);
 }
 // -1 / p, correctly rounded: v_rcp_f64 is good to 2^-24.4, x0 (1 + e + e^2) with e = 1 - p x0 then equals the rounded quotient
-// on every input tried (scripts/dev/lat_probe.hip, 2^20 inputs: as two Newton steps, one dependent operation less)
+// on every input tried (scripts/dev/lat_probe.hip, 2^20 inputs: as two Newton steps, one dependent operation less;
+// tests/test_gpu_device_math.py asserts bit-equality with -1.0 / p on 58 196 inputs: 2^+-300 of both signs, mantissa edges,
+// pivots 1e-12 .. 1e12).  At p = +-0, +-inf and denormal p (1 / p overflows) the result is NaN where the quotient is
+// -+inf / -+0 (the test pins it): p is a pivot of lm_lane_solve, whose row keeps it in its own lane, and `own > 1e-12 (1 +
+// lambda) dg` is false for 0, NaN, +-inf (dg is inf then) and for a denormal under any diagonal entry >= 1e-296 -- the
+// verdict is false and dx, NaN or not, is discarded for the pseudo-inverse step.
 __device__ __forceinline__ double lane_rcp_neg(double p) {
     const double x0 = __builtin_amdgcn_rcp(p);
     const double e = __builtin_fma(-p, x0, 1.0);

@@ -7,10 +7,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "host_math_probe.cpp")
 LIB = os.path.join(HERE, "libhost_math_probe.so")
 CSRC = os.path.join(HERE, "..", "..", "esac_amd", "csrc")
+BODIES = os.path.join(HERE, "math_probe_bodies.hpp")  # the per-item work both math probes run
 
 
 def build(force=False):
-    deps = [SRC] + [os.path.join(CSRC, h) for h in ("pose_math.hpp", "lm_math.hpp", "bwd_math.hpp", "lm_lanes.hpp", "select_math.hpp", "device_common.hpp")]
+    deps = [SRC, BODIES] + [os.path.join(CSRC, h) for h in ("pose_math.hpp", "lm_math.hpp", "bwd_math.hpp", "lm_lanes.hpp", "select_math.hpp", "device_common.hpp", "p3p_screen.hpp")]
     if force or not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
         hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
         subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC",
@@ -55,6 +56,21 @@ def build_screen_campaign(force=False):
         hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
         subprocess.check_call([hipcc] + product.FLAGS + [CAMPAIGN_SRC, "-o", CAMPAIGN_LIB])
     return CAMPAIGN_LIB
+
+
+DEVICE_MATH_SRC = os.path.join(HERE, "device_math_probe.hip")
+DEVICE_MATH_LIB = os.path.join(HERE, "libdevice_math_probe.so")
+
+
+def build_device_math_probe(force=False):
+    """DEVICE build of the per-function probe of the math headers (device_math_probe.hip): the product's own compiler flags, so
+    every __HIP_DEVICE_COMPILE__ branch runs as the kernels compile it (tests/test_gpu_device_math.py)."""
+    from esac_amd import build as product
+    deps = [DEVICE_MATH_SRC, BODIES] + [os.path.join(CSRC, h) for h in product.HEADERS if h.endswith(".hpp")]
+    if force or not os.path.exists(DEVICE_MATH_LIB) or any(os.path.getmtime(d) > os.path.getmtime(DEVICE_MATH_LIB) for d in deps):
+        hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
+        subprocess.check_call([hipcc] + product.FLAGS + ["-Wno-unused-result", DEVICE_MATH_SRC, "-o", DEVICE_MATH_LIB])
+    return DEVICE_MATH_LIB
 
 
 FILLER_SRC = os.path.join(HERE, "filler.hip")

@@ -6,6 +6,7 @@
 #include "../../esac_amd/csrc/bwd_math.hpp"
 #include "../../esac_amd/csrc/lm_lanes.hpp"
 #include "../../esac_amd/csrc/select_math.hpp"
+#include "math_probe_bodies.hpp"
 using namespace esac;
 extern "C" {
 int probe_p3p(const double* obj, const double* img, double fx, double fy, double cx, double cy, double* rvec, double* tvec, double* Rout) {
@@ -173,5 +174,29 @@ void probe_softmax_stats_inline(const double* s, int n, double m, double* out) {
         acc[1] += ex * d;
     }
     out[0] = acc[0]; out[1] = acc[1]; out[2] = log2(acc[0]) - acc[1] / (acc[0] * 0.6931471805599453);
+}
+// ---- the per-function bodies the device probe runs (math_probe_bodies.hpp), looped over on the host: the #else side of every
+// __HIP_DEVICE_COMPILE__ branch (fast_rcp, scr_sqrt, cbrt_pos, cos_third_acos, lm_pose_rotation's trigonometric route,
+// lm_point_terms) gets a CPU test of its own and is what the device results are compared with at special values
+void probe_scalars(int op, int n, const double* in, double* out) {
+    for (int i = 0; i < n; i++) out[i] = esac_probe::body_scalar(op, in[i]);
+}
+void probe_rotation(int n, const double* in, double* out) {
+    for (int i = 0; i < n; i++) esac_probe::body_rotation(in + 6 * i, out + esac_probe::ROT_OUT * i);
+}
+int probe_point_terms(int np, int n, const double* in, double* out) {
+    if (np < 1 || np > 4) return -1;
+    for (int i = 0; i < n; i++) {
+        const double* q = in + esac_probe::PT_IN * i;
+        double* o = out + esac_probe::PT_OUT * i;
+        if (np == 1) esac_probe::body_point_terms<1>(q, o);
+        if (np == 2) esac_probe::body_point_terms<2>(q, o);
+        if (np == 3) esac_probe::body_point_terms<3>(q, o);
+        if (np == 4) esac_probe::body_point_terms<4>(q, o);
+    }
+    return 0;
+}
+void probe_solves(int n, const double* in, double* out) {
+    for (int i = 0; i < n; i++) esac_probe::body_solves(in + esac_probe::SOLVE_IN * i, out + esac_probe::SOLVE_OUT * i);
 }
 }

@@ -201,23 +201,9 @@ def test_lane_dealt_lm_step_equals_the_uniform_route(probe):
     chain-rule columns, two 3x3-block products on row_newbcast FMAs, Gauss-Jordan over the lanes) on the host's 16-lane
     emulation == lm_moments_to_acc + lm_transform + lm_solve6 on the same totals: the system to rounding, the step to
     the conditioning of the solve, the pivot verdict on a rank-deficient system."""
-    rng = np.random.default_rng(33)
+    from tests import device_math_cases as DC
     worst_sys = worst_dx = 0.0
-    for it in range(300):
-        # moments of a real point set, so that the normal matrix is SPD with the structure the kernels produce
-        n = [6, 40, 400][it % 3]
-        x, y = rng.normal(size=n) * 0.4, rng.normal(size=n) * 0.3
-        iz = 1.0 / rng.uniform(1.0, 6.0, size=n)
-        ex, ey = rng.normal(size=n) * 3.0, rng.normal(size=n) * 3.0
-        xx, yy, xy = x * x, y * y, x * y
-        r2, ox, oy = xx + yy, 1 + xx, 1 + yy
-        qq, p1, p2, iz2 = 1 + r2, x * iz, y * iz, iz * iz
-        mom = [x, y, r2, iz2, iz2 * x, iz2 * y, iz2 * r2, p1, p2, xy * iz, oy * iz, ox * iz, p2 * qq, p1 * qq, xy * (1 + qq),
-               xy * xy + oy * oy, xy * xy + ox * ox, xy * ex + oy * ey, ox * ex + xy * ey, x * ey - y * ex, iz * ex, iz * ey,
-               p1 * ex + p2 * ey, ex * ex + ey * ey]
-        sums = np.array([m.sum() for m in mom] + [1.0, 2.0, float(n)])
-        pose = np.concatenate([rng.normal(size=3) * [1e-9, 0.3, 1.5][it % 3], rng.normal(size=3) * [0.1, 3.0][it % 2]])
-        lam = 10.0 ** rng.integers(-6, 3)
+    for sums, pose, lam in DC.lane_step_cases():  # (shared with the device test, tests/test_gpu_device_math.py)
         U, g, dx = np.zeros(21), np.zeros(6), np.zeros(6)
         ok = probe.probe_lane_step(_p(sums), _p(pose), float(lam), _p(U), _p(g), _p(dx))
         # the uniform route on the same totals
