@@ -241,7 +241,7 @@ __device__ __forceinline__ bool team_step(bool fresh, const LaneConst& lc, const
     }
     CYC_PIN(param, 6);
     CYC_END(8);
-    return iters + 1 >= 20 || relative_step_below_eps(dn, pn);
+    return iters + 1 >= 20 || relative_step_below_eps<true>(dn, pn);  // (every lane holds the same step)
 }
 
 // ---- the selection, folded into the prologue (see the header).  N <= REFINE_B: one hypothesis per thread.
@@ -445,6 +445,7 @@ __global__ __launch_bounds__(REFINE_B) void k_refine_team(KArgs a) {
         coop_init(co, a, (int)gridDim.x / a.team_stride, (int)blockIdx.x / a.team_stride, ESAC_TEAM_SPIN_LIMIT);
     }
     co.expect = co.G;
+    team_begin(co);
     if (a.coop_extra && co.g == co.G - 1) return;  // ESAC_DEBUG_COOP_STALL: the last member never shows up
     // first exchange, in flight while the winner is looked up: a census of the XCDs the members run on (64^XCC_ID each)
     int xcc;
@@ -593,7 +594,7 @@ __global__ __launch_bounds__(REFINE_B) void k_refine_team(KArgs a) {
         if (co.dead) break;  // an exchange timed out: the sums are garbage, the call reports it
         CYC_BEGIN();
         bool fresh = true;  // normal equations from this pass (else: state CHECK_ERR failed, retry from `prev` with a larger lambda)
-        if (in_refit && trial_rejected(sums[0], prev_err2, ends_refit, (a.flags & ESAC_FLAG_STRICT_REFERENCE_K) != 0) && ++lambda_lg10 <= 16) {
+        if (in_refit && trial_rejected<true>(sums[0], prev_err2, ends_refit, (a.flags & ESAC_FLAG_STRICT_REFERENCE_K) != 0) && ++lambda_lg10 <= 16) {
             fresh = false;
         } else {
             if (in_refit) {
@@ -613,7 +614,7 @@ __global__ __launch_bounds__(REFINE_B) void k_refine_team(KArgs a) {
             if (!in_refit) {
                 // error image at `param` (reproErrs, esac.cpp:169 / esac_util.h:445-452): next_set, its size, its normal equations
                 if (rstep >= a.max_ref_steps) break;  // the reference also evaluates the errors of its last re-fit
-                const int n_inl = (int)sums[2];
+                const int n_inl = __builtin_amdgcn_readfirstlane((int)sums[2]);  // (a total out of LDS, the same in every lane)
                 if (!SLOTS && writer && threadIdx.x == 0) a.inlier_counts[rstep] = n_inl;
                 if ((unsigned)n_inl <= best_inliers) break;  // converged (esac_util.h:417-419)
                 best_inliers = (unsigned)n_inl;

@@ -155,24 +155,37 @@ __device__ __forceinline__ double pow10_int(int k) {
 // not end their re-fit keep the reference's comparison (an acceptance there would change lambda's course).
 // strict (ESAC_FLAG_STRICT_REFERENCE, a word of the call's flags): no such exception -- every trial is the reference's comparison
 // alone, sqrt(err2) > sqrt(prev2), and a converged trial inside the band goes up the lambda ladder when the roots say so.
+// UNIFORM (the team kernel): every lane holds the same err2 / prev2, and each comparison is handed on as a SCALAR (uniform_bool)
+// -- the branches around the rare paths are then s_cbranch on a scalar condition with no exec mask saved and restored.
+__device__ __forceinline__ bool uniform_bool(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
+template <bool UNIFORM = false>
 __device__ __forceinline__ bool trial_rejected(double err2, double prev2, bool ends_refit, bool strict) {
-    if (!(err2 > prev2)) return false;
-    if (err2 > prev2 * (1.0 + 8.0 * DBL_EPSILON)) return true;
+    auto u = [](bool b) {
+        if constexpr (UNIFORM) return uniform_bool(b);
+        else return b;
+    };
+    if (!u(err2 > prev2)) return false;
+    if (u(err2 > prev2 * (1.0 + 8.0 * DBL_EPSILON))) return true;
     if (ends_refit && !strict) return false;
     asm volatile("; norms a few ulp apart");  // (keeps the two square roots BEHIND the branch: as plain arithmetic they are
                                               // if-converted and run on every pass, ~45 instructions)
-    return sqrt(err2) > sqrt(prev2);
+    return u(sqrt(err2) > sqrt(prev2));
 }
 // cvNorm(param, prevParam, CV_RELATIVE_L2) < FLT_EPSILON, i.e. sqrt(dn) / (sqrt(pn) + DBL_EPSILON) < eps, dn = |param - prev|^2,
 // pn = |prev|^2: decided on the squares wherever the answer is clear of the threshold by 1e-9 (relative), by the
 // reference's own expression in between.  sqrt(pn) <= max(1, pn) bounds the DBL_EPSILON term from above.
+template <bool UNIFORM = false>
 __device__ __forceinline__ bool relative_step_below_eps(double dn, double pn) {
+    auto u = [](bool b) {
+        if constexpr (UNIFORM) return uniform_bool(b);
+        else return b;
+    };
     const double e2 = (double)FLT_EPSILON * (double)FLT_EPSILON;
     const double lo = e2 * pn;
-    if (dn < lo * (1.0 - 1e-9)) return true;
+    if (u(dn < lo * (1.0 - 1e-9))) return true;
     const double hi = lo + e2 * DBL_EPSILON * (2.0 * (pn > 1.0 ? pn : 1.0) + DBL_EPSILON);
-    if (dn > hi * (1.0 + 1e-9)) return false;
-    return sqrt(dn) / (sqrt(pn) + DBL_EPSILON) < (double)FLT_EPSILON;
+    if (u(dn > hi * (1.0 + 1e-9))) return false;
+    return u(sqrt(dn) / (sqrt(pn) + DBL_EPSILON) < (double)FLT_EPSILON);
 }
 
 // ---- cooperating workgroups ------------------------------------------------------------------------------------------------
@@ -211,7 +224,9 @@ struct Coop {
     double* partials;              // REFINE_COOP: [2][G][32]
     unsigned long long* counter;   // REFINE_COOP: monotonic arrival counter, zeroed by the launcher; COOP_POISON is or-ed in on a time-out
     unsigned long long* failed;    // the launch tag of the most recent launch in which an exchange timed out (what the host reads)
-    unsigned long long arrivals;   // exchanges passed so far (same in every thread of every workgroup)
+    unsigned long long arrivals;   // exchanges passed so far (same in every thread of every workgroup); REFINE_TEAM: launch tag | that
+                                   // count in ONE word (team_begin) -- what the next exchange's granules must carry is arrivals + 1, and the
+                                   // round loop keeps one 64-bit scalar where tag and count were two
     int expect;                    // workgroups an exchange waits for (= G; ESAC_DEBUG_COOP_STALL: G + 1, never reached)
     long spin_limit;               // REFINE_COOP: polls before the barrier gives up; REFINE_TEAM: ticks of the 100 MHz wall clock
     int* s_dead;                   // LDS flag: an exchange of this launch timed out somewhere
@@ -247,6 +262,14 @@ __device__ __forceinline__ void coop_mark_failed(Coop& co) {
 }
 
 // ---- REFINE_TEAM: the tagged-granule exchange
+// The launch's tag has its low 20 bits clear and they count the exchanges: the team keeps both in co.arrivals.
+constexpr unsigned long long TEAM_COUNT_MASK = (1ull << 20) - 1ull;
+__device__ __forceinline__ void team_begin(Coop& co) { co.arrivals = co.tag; }  // behind coop_init (and whatever sets co.tag after it)
+__device__ __forceinline__ unsigned long long team_tag(const Coop& co) { return co.arrivals & ~TEAM_COUNT_MASK; }
+__device__ __forceinline__ void team_mark_failed(Coop& co) {
+    __hip_atomic_store(co.failed, team_tag(co), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    *co.s_dead = 1;
+}
 __device__ __forceinline__ u32x4 gran_load(const u32x4* p) {
     u32x4 v;
     asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
@@ -270,7 +293,7 @@ __device__ __forceinline__ void team_publish(double own, const Coop& co) {
     static_assert(NV <= 32, "32 granules per member");
     if (co.dead) return;
     if (threadIdx.x < NV) {
-        const unsigned long long want = co.tag | (co.arrivals + 1ull);
+        const unsigned long long want = co.arrivals + 1ull;
         const unsigned long long bits = (unsigned long long)__double_as_longlong(own), tg = want ^ bits;
         u32x4* buf = co.gran + (size_t)(co.arrivals & 1ull) * (TEAM_MAX * 32);
         gran_store(buf + co.g * 32 + threadIdx.x, u32x4{(unsigned)bits, (unsigned)(bits >> 32), (unsigned)tg, (unsigned)(tg >> 32)}, co.local);
@@ -292,7 +315,7 @@ __device__ __forceinline__ void team_collect_lds(Coop& co, double* s_tot, double
     static_assert(NV <= 32 && REFINE_B == 256 && TEAM_MAX <= 32, "poll layout");
     static_assert(WIDE == 8 || WIDE == 16 || WIDE == 32, "members an instantiation collects");
     if (co.dead) return;
-    const unsigned long long want = co.tag | (co.arrivals + 1ull);
+    const unsigned long long want = co.arrivals + 1ull;
     const u32x4* buf = co.gran + (size_t)(co.arrivals & 1ull) * (TEAM_MAX * 32);
     const int k = threadIdx.x >> 3, j = threadIdx.x & 7;
     double val = 0.0;
@@ -314,7 +337,7 @@ __device__ __forceinline__ void team_collect_lds(Coop& co, double* s_tot, double
             return false;
         }
         if ((spins & 63) != 0) return false;
-        return wall_clock64() - t_first > co.spin_limit || __hip_atomic_load(co.failed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == co.tag;
+        return wall_clock64() - t_first > co.spin_limit || __hip_atomic_load(co.failed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == team_tag(co);
     };
     constexpr bool row16 = WIDE == 16;
     double val_b = 0.0;  // (9 .. 16 members: this thread's second value, 16 + t >> 4)
@@ -389,13 +412,13 @@ __device__ __forceinline__ void team_collect_lds(Coop& co, double* s_tot, double
 #pragma unroll
         for (int i = 0; i < 4; i++)
             if (need[i]) s_x[(int)threadIdx.x + i * REFINE_B] = timed_out ? 0.0 : x[i];
-        if (timed_out) coop_mark_failed(co);
+        if (timed_out) team_mark_failed(co);
         timed_out = false;
         barrier_lds();
         if (k < NV)
             for (int m = j; m < co.expect; m += 8) val += s_x[m * 32 + k];  // members j, j + 8, j + 16, j + 24 in that order
     }
-    if (timed_out) coop_mark_failed(co);
+    if (timed_out) team_mark_failed(co);
     val += dpp_move<0xB1>(val);   // lanes (0,1) (2,3) (4,5) (6,7)
     val += dpp_move<0x4E>(val);   // quads
     val += dpp_move<0x141>(val);  // all eight
@@ -421,7 +444,7 @@ __device__ __forceinline__ void team_collect_lds(Coop& co, double* s_tot, double
         if (NEG) s_tot[32 + k] = -val;
     }
     barrier_lds();
-    co.dead = *co.s_dead != 0;
+    co.dead = __builtin_amdgcn_readfirstlane(*co.s_dead) != 0;  // (one word of LDS: the same in every lane -- a scalar to branch on)
     co.arrivals += 1ull;
 }
 template <int NV, int WIDE>
@@ -540,7 +563,8 @@ __device__ __forceinline__ void refine_write_record(const KArgs& a, const Record
                                                     unsigned long long census, double* s_rec) {
     const int lane = threadIdx.x & 63;
     // an exchange between the workgroups sharing this refinement timed out: the record is not to be trusted
-    const bool coop_failed = mode != REFINE_SOLO && (co.dead || __hip_atomic_load(co.failed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == co.tag);
+    const unsigned long long launch_tag = mode == REFINE_TEAM ? team_tag(co) : co.tag;
+    const bool coop_failed = mode != REFINE_SOLO && (co.dead || __hip_atomic_load(co.failed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == launch_tag);
     if (lane == 0) {
         double R[9];
         rodrigues_vec2mat<false>(pose, R, nullptr);
@@ -576,7 +600,7 @@ __device__ __forceinline__ void refine_write_record(const KArgs& a, const Record
             a.refine_info[2] = (int)lo;
             a.refine_info[7] = (int)hi;
             a.refine_info[3] = mode == REFINE_TEAM ? same : 0;
-            a.refine_info[4] = (int)co.arrivals;
+            a.refine_info[4] = (int)(mode == REFINE_TEAM ? co.arrivals & TEAM_COUNT_MASK : co.arrivals);
             a.refine_info[5] = coop_failed ? 1 : 0;
         }
     }
