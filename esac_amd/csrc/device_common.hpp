@@ -297,19 +297,68 @@ __device__ __forceinline__ size_t user_slot(const KArgs& a, int h) {
 __device__ __forceinline__ float cell_px(const KArgs& a, int x) { return (float)(x * a.sub + a.sub / 2 - a.shift_x); }
 __device__ __forceinline__ float cell_py(const KArgs& a, int y) { return (float)(y * a.sub + a.sub / 2 - a.shift_y); }
 
-// Origin of the fp32 scoring stream for one expert's map: the scene point of the middle cell (0 when it is not finite).
-// The stream evaluates R*(X - c) + (t + R*c) with the second term formed in double when the hypothesis is stored, so its
-// rounding error scales with the extent of the scene around c, not with the distance of the scene from the world origin
-// (world-frame maps of outdoor scenes sit ~1e3 m out: float(t) alone would shift every projection by ~1e-2 px).
+// Origin of the fp32 scoring stream for one expert's map.  The stream evaluates R*(X - c) + (t + R*c) with the second term
+// formed in double when the hypothesis is stored, so its rounding error scales with the extent of the scene around c, not
+// with the distance of the scene from the world origin (world-frame maps of outdoor scenes sit ~1e3 m out: float(t) alone
+// would shift every projection by ~1e-2 px).  c must therefore be a TYPICAL point of the map, and one cell decides nothing:
+//   c = the scene point of the middle cell, while it is finite and lies inside the box spanned by the four quarter-point cells
+//       ((H/4 | 3H/4) x (W/4 | 3W/4)) padded by 8x the box's largest side -- the origin such a map always had, every bit of its scores kept;
+//   else the quarter-point cell with the smallest summed distance to the other three (their medoid: a wild probe is never it);
+//   with fewer than two finite quarter-point cells nothing can be judged: the middle cell if finite, else the finite one, else 0.
+// A wild or non-finite middle cell (|X - c| ~ 1e5 m costs every cell of the expert its low bits; origin 0 puts the world
+// origin's distance back into the stream) and any blotch -- it covers at most one of the five probes, which are H/4 and W/4
+// apart -- leave the origin among the healthy cells.  Not covered: two wild probes at once, a map that is mostly garbage
+// (ESAC_FLAG_EXACT_SCORES is the guarantee there).  The five probes are wave-uniform loads.  store_rt32, k_sample_decide, score_fast_one and k_score_tiled
+// must agree on c: this is the one definition.
 struct Centre {
     float x, y, z;
 };
+__device__ __forceinline__ bool centre_finite(const Centre& c) {  // false for NaN / inf
+    return fabsf(c.x) <= 3.0e38f && fabsf(c.y) <= 3.0e38f && fabsf(c.z) <= 3.0e38f;
+}
+__device__ __forceinline__ float centre_dist(const Centre& p, const Centre& q) {  // L-inf; inf where a difference overflows
+    return fmaxf(fmaxf(fabsf(p.x - q.x), fabsf(p.y - q.y)), fabsf(p.z - q.z));
+}
+// the rare end of map_centre: the middle cell was refused, or fewer than two quarter-point cells are finite
+__device__ __forceinline__ Centre centre_fallback(const Centre& c, bool mid_ok, const Centre (&q)[4], const bool (&ok)[4], int n) {
+    Centre best{0.0f, 0.0f, 0.0f};
+    bool have = false;
+    float best_d = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {  // (fully unrolled: q[] and ok[] stay in registers)
+        float d = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            if (j != k) d += ok[j] ? centre_dist(q[k], q[j]) : 0.0f;
+        if (ok[k] && (!have || d < best_d)) best = q[k], best_d = d, have = true;  // (n == 1: the finite one; n == 0: stays 0)
+    }
+    return n < 2 && mid_ok ? c : best;
+}
 __device__ __forceinline__ Centre map_centre(const KArgs& a, const float* __restrict__ map) {
     const int P = a.H * a.W, mid = (a.H >> 1) * a.W + (a.W >> 1);
-    Centre c{map[mid], map[P + mid], map[2 * P + mid]};
-    const bool ok = fabsf(c.x) <= 3.0e38f && fabsf(c.y) <= 3.0e38f && fabsf(c.z) <= 3.0e38f;  // false for NaN / inf
-    if (!ok) c = Centre{0.0f, 0.0f, 0.0f};
-    return c;
+    const int y0 = a.H >> 2, y1 = (3 * a.H) >> 2, x0 = a.W >> 2, x1 = (3 * a.W) >> 2;
+    const int c0 = y0 * a.W + x0, c1 = y0 * a.W + x1, c2 = y1 * a.W + x0, c3 = y1 * a.W + x1;
+    // all fifteen loads first and nothing conditional before the last of them is used: ONE trip to memory, as the middle cell
+    // alone was.  (Written probe by probe with `if (finite)` around the box update, the compiler put each probe's loads behind
+    // the previous probe's branch: four trips in a row at the head of k_score_fast, 1.7 % of the headline call.)
+    const Centre c{map[mid], map[P + mid], map[2 * P + mid]};
+    const Centre q[4] = {Centre{map[c0], map[P + c0], map[2 * P + c0]}, Centre{map[c1], map[P + c1], map[2 * P + c1]},
+                         Centre{map[c2], map[P + c2], map[2 * P + c2]}, Centre{map[c3], map[P + c3], map[2 * P + c3]}};
+    const bool ok[4] = {centre_finite(q[0]), centre_finite(q[1]), centre_finite(q[2]), centre_finite(q[3])};
+    const bool mid_ok = centre_finite(c);
+    const int n = (int)ok[0] + (int)ok[1] + (int)ok[2] + (int)ok[3];
+    const float big = 3.4e38f;
+    Centre lo{big, big, big}, hi{-big, -big, -big};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {  // selects, no branches
+        lo = Centre{fminf(lo.x, ok[k] ? q[k].x : big), fminf(lo.y, ok[k] ? q[k].y : big), fminf(lo.z, ok[k] ? q[k].z : big)};
+        hi = Centre{fmaxf(hi.x, ok[k] ? q[k].x : -big), fmaxf(hi.y, ok[k] ? q[k].y : -big), fmaxf(hi.z, ok[k] ? q[k].z : -big)};
+    }
+    const float pad = 8.0f * fmaxf(fmaxf(hi.x - lo.x, hi.y - lo.y), hi.z - lo.z);  // (inf when a side overflows: everything is inside)
+    const bool inside = (n >= 2) & mid_ok & (c.x >= lo.x - pad) & (c.x <= hi.x + pad) & (c.y >= lo.y - pad) & (c.y <= hi.y + pad) &
+                        (c.z >= lo.z - pad) & (c.z <= hi.z + pad);
+    if (__builtin_expect(inside, 1)) return c;
+    return centre_fallback(c, mid_ok, q, ok, n);
 }
 
 
