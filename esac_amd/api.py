@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "esac_hip_backward_batch_dev",  # additive: the ABI version stays
     "esac_hip_eval_batch",  # additive too
     "esac_hip_set_bwd_pose_records",  # additive too
+    "esac_hip_forward_batch_shapes",  # additive too
 ]
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
@@ -121,6 +122,78 @@ def _cams_arg(cams, B, who):
     return arr
 
 
+def _shapes_arg(who, shapes, B):
+    """`shapes` of a ragged batch as a list of B (h, w) int pairs.  Raises RuntimeError naming the argument; touches no device."""
+    if isinstance(shapes, (torch.Tensor, np.ndarray)):
+        shapes = shapes.tolist()
+    if not isinstance(shapes, (list, tuple)) or len(shapes) != B:
+        raise RuntimeError("%s: shapes must hold one (h, w) pair per frame (%d), found %s"
+                           % (who, B, "%d" % len(shapes) if isinstance(shapes, (list, tuple)) else type(shapes).__name__))
+    out = []
+    for b, s in enumerate(shapes):
+        try:
+            h, w = s
+            ok = int(h) == h and int(w) == w
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise RuntimeError("%s: shapes[%d] must be a pair of integers (h, w), found %r" % (who, b, s))
+        h, w = int(h), int(w)
+        # the grid rule of a single call (call_policy.hpp: check_grid)
+        if h < 3 or w < 3 or (h - 1) * (w - 1) < 4 or h > 65535 or w > 65535:
+            raise RuntimeError("%s: shapes[%d] = %dx%d is no legal grid (at least 3x3 with (h-1)(w-1) >= 4, at most 65535 rows / columns)"
+                               % (who, b, h, w))
+        out.append((h, w))
+    return out
+
+
+def capacity_shape(shapes):
+    """The (H, W) a ragged batch's parameter block carries: the grid of the frame with the most cells (only H*W matters: it is
+    the cell count every per-frame buffer and launch is sized for)."""
+    return max(shapes, key=lambda s: s[0] * s[1])
+
+
+def packed_stride(E, shapes):
+    """Floats per frame slot of a packed ragged batch: 3*E*max(h*w), rounded up to a multiple of 4 (16-byte aligned slots)."""
+    return (3 * int(E) * max(h * w for h, w in shapes) + 3) // 4 * 4
+
+
+def _ragged_maps(who, maps):
+    """A list of B float32 [E,3,h_b,w_b] tensors with one E.  Returns (E, shapes); RuntimeError naming sceneCoordinates otherwise."""
+    if not isinstance(maps, (list, tuple)) or len(maps) == 0:
+        raise RuntimeError("%s: sceneCoordinates must be a non-empty list of float32 [E,3,h,w] tensors" % who)
+    E = None
+    for b, m in enumerate(maps):
+        if not isinstance(m, torch.Tensor):
+            raise RuntimeError("%s: sceneCoordinates[%d] must be a torch.Tensor" % (who, b))
+        if m.dtype != torch.float32:
+            raise RuntimeError("%s: expected scalar type torch.float32 for sceneCoordinates[%d] but found %s" % (who, b, m.dtype))
+        if m.dim() != 4 or m.size(1) != 3:
+            raise RuntimeError("%s: sceneCoordinates[%d] must be [E,3,h,w], found %s" % (who, b, list(m.shape)))
+        if E is None:
+            E = int(m.size(0))
+        elif int(m.size(0)) != E:
+            raise RuntimeError("%s: sceneCoordinates[%d] holds %d experts, sceneCoordinates[0] holds %d" % (who, b, m.size(0), E))
+    return E, [(int(m.size(2)), int(m.size(3))) for m in maps]
+
+
+def pack_frames(maps, device=None):
+    """Packs frames that differ in image size for `forward_batch(shapes=...)`: maps = a list of B float32 [E,3,h_b,w_b] tensors
+    (host or device).  Returns (packed, shapes): packed float32 [B,S] on the device with frame b's maps DENSE in packed[b,
+    :3*E*h_b*w_b] (the rest of the row is zero and never read), S = 3*E*max(h_b*w_b) rounded up to a multiple of 4; shapes =
+    [(h_b, w_b), ...].  device: where packed lives (default: the first device tensor's device, else the current GPU)."""
+    who = "esac.pack_frames"
+    E, shapes = _ragged_maps(who, maps)
+    shapes = _shapes_arg(who, shapes, len(maps))
+    if device is None:
+        on_dev = [m.device for m in maps if m.is_cuda]
+        device = on_dev[0] if on_dev else engine(None).device
+    packed = torch.zeros(len(maps), packed_stride(E, shapes), dtype=torch.float32, device=device)
+    for b, m in enumerate(maps):
+        packed[b, :m.numel()].copy_(m.reshape(-1), non_blocking=True)
+    return packed, shapes
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -147,6 +220,7 @@ def load_library():
         lib.esac_hip_forward.argtypes = [vp, vp, vp, pp, vp, vp, vp, vp]
         lib.esac_hip_forward_batch.argtypes = [vp, i32, vp, C.c_int64, vp, pp, vp, vp, vp, vp]
         lib.esac_hip_forward_batch_cams.argtypes = [vp, i32, vp, C.c_int64, vp, pp, vp, vp, vp, vp, vp]
+        lib.esac_hip_forward_batch_shapes.argtypes = [vp, i32, vp, C.c_int64, vp, pp, vp, vp, vp, vp, vp]
         for name in ("esac_hip_sample", "esac_hip_score", "esac_hip_select", "esac_hip_refine", "esac_hip_score_exact"):
             getattr(lib, name).argtypes = [vp, vp, vp, pp, vp]
         lib.esac_hip_backward.argtypes = [vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, pp, vp, vp]
@@ -321,11 +395,13 @@ class Engine:
         self._keep = (sc, ha)  # keep inputs alive until the (possibly asynchronous) kernels have run
         return self._host_np.copy() if want_host else None
 
-    def forward_batch(self, scene_coords, hyp_assign, params, scores_out=None, result_out=None, want_host=True, cams=None):
+    def forward_batch(self, scene_coords, hyp_assign, params, scores_out=None, result_out=None, want_host=True, cams=None, shapes=None):
         """B frames per launch set. scene_coords [B,E,3,H,W] (or [E,3,H,W] shared by all frames), hyp_assign [B,N];
         `params` describes one frame, frame b uses call + b. Returns np.float64 [B,32] (or None).
         cams: None (every frame uses the shift, focal length and principal point of `params`) or B records (make_cams):
-        frame b uses cams[b] and the five fields of `params` are ignored (esac_hip_forward_batch_cams)."""
+        frame b uses cams[b] and the five fields of `params` are ignored (esac_hip_forward_batch_cams).
+        shapes: None, or B (h, w) pairs -- a ragged batch (esac_hip_forward_batch_shapes): scene_coords is the packed [B,S] tensor
+        of pack_frames, params.H * params.W the capacity in cells (capacity_shape), frame b's grid is shapes[b]."""
         sc = scene_coords if scene_coords.is_cuda else scene_coords.to(self.device, non_blocking=True)
         ha = hyp_assign if hyp_assign.is_cuda else hyp_assign.to(self.device, non_blocking=True)
         sc, ha = sc.contiguous(), ha.contiguous()
@@ -334,7 +410,19 @@ class Engine:
         host = np.zeros((B, RES_DOUBLES), np.float64) if want_host else None
         outs = (scores_out.data_ptr() if scores_out is not None else None,
                 result_out.data_ptr() if result_out is not None else None, host.ctypes.data if want_host else None)
-        if cams is None:
+        if shapes is not None:
+            who = "esac.forward_batch"
+            shapes = _shapes_arg(who, shapes, B)
+            if sc.dim() != 2 or sc.shape[0] != B:
+                raise RuntimeError("%s: with shapes, scene_coords must be the packed [B,S] tensor (pack_frames), found %s" % (who, list(sc.shape)))
+            if cams is None:
+                cams = make_cams([params.shift_x] * B, [params.shift_y] * B, [params.focal] * B, [params.ppx] * B, [params.ppy] * B)
+            else:
+                cams = _cams_arg(cams, B, who).copy()  # (the caller's table keeps its padding)
+            cams["reserved"][:, :2] = np.asarray(shapes, np.int32)
+            self._call(self.lib.esac_hip_forward_batch_shapes, B, sc.data_ptr(), int(sc.stride(0)), ha.data_ptr(), C.byref(params),
+                       cams.ctypes.data, self._stream(), *outs)
+        elif cams is None:
             self._call(self.lib.esac_hip_forward_batch, B, sc.data_ptr(), stride, ha.data_ptr(), C.byref(params), self._stream(), *outs)
         else:
             cams = _cams_arg(cams, B, "esac.forward_batch")  # (the library copies the table before it returns)
@@ -541,7 +629,10 @@ class Engine:
         return out
 
     def read_forward_frames(self, which, B):
-        """BUF_HYPS / _SAMPLE_XY / _TRIES / _SCORES / _INLIER_COUNTS of all B frames of the last batched call, frame-major."""
+        """BUF_HYPS / _SAMPLE_XY / _TRIES / _SCORES / _INLIER_COUNTS of all B frames of the last batched call, frame-major.
+        After a ragged batch (forward_batch(shapes=...)) the strides stay the capacity's: these five are per hypothesis and
+        read as ever (sampled cells index frame b's own w_b-wide grid); a per-cell buffer (read(BUF_INLIER_MAP): frame 0, returned
+        at the capacity's [H,W]) holds the frame's data in its first h_b*w_b entries: out.reshape(-1)[:h*w].reshape(h, w)."""
         N, H, W = self._shape
         shapes = {BUF_HYPS: ((N, 6), np.float64), BUF_SAMPLE_XY: ((N, 4, 2), np.int32), BUF_TRIES: ((N,), np.int32),
                   BUF_SCORES: ((N,), np.float64), BUF_INLIER_COUNTS: ((MAX_REF_STEPS + 1,), np.int32)}
@@ -980,16 +1071,91 @@ def _per_frame_cams(who, B, shiftX, shiftY, focalLength, ppointX, ppointY):
     return (int(cols[0][0]), int(cols[1][0]), float(cols[2][0]), float(cols[3][0]), float(cols[4][0])), cams
 
 
+def _ragged_args(who, sceneCoordinates, B, shapes, experts):
+    """The checks of a ragged batch's sceneCoordinates / shapes / experts before any device is touched.  sceneCoordinates: a list
+    of B maps (packed later, on the call's device) or the packed float32 [B,S] tensor of pack_frames.  Returns (E, shapes)."""
+    shapes = _shapes_arg(who, shapes, B)
+    if experts is not None and (not isinstance(experts, int) or isinstance(experts, bool) or experts < 1):
+        raise RuntimeError("%s: experts must be a positive int, found %r" % (who, experts))
+    if isinstance(sceneCoordinates, (list, tuple)):
+        E, found = _ragged_maps(who, sceneCoordinates)
+        if len(found) != B:
+            raise RuntimeError("%s: sceneCoordinates holds %d frames, hypAssignment %d" % (who, len(found), B))
+        for b in range(B):
+            if found[b] != shapes[b]:
+                raise RuntimeError("%s: shapes[%d] = %dx%d, sceneCoordinates[%d] is %dx%d" % ((who, b) + shapes[b] + (b,) + found[b]))
+        if experts is not None and experts != E:
+            raise RuntimeError("%s: experts = %d, sceneCoordinates holds %d experts per frame" % (who, experts, E))
+        return E, shapes
+    if not isinstance(sceneCoordinates, torch.Tensor) or sceneCoordinates.dtype != torch.float32 or sceneCoordinates.dim() != 2:
+        raise RuntimeError("%s: with shapes, sceneCoordinates must be the packed float32 [B,S] tensor of pack_frames or a list of "
+                           "float32 [E,3,h,w] maps" % who)
+    if sceneCoordinates.size(0) != B:
+        raise RuntimeError("%s: batch sizes of sceneCoordinates and hypAssignment differ" % who)
+    S, cells = int(sceneCoordinates.size(1)), max(h * w for h, w in shapes)
+    if S % 4:
+        raise RuntimeError("%s: sceneCoordinates [B,S] needs S to be a multiple of 4 floats, found %d (pack_frames)" % (who, S))
+    # pack_frames' S is 3*E*max(h*w) rounded up by at most 3 floats, less than one expert's share: E follows from it
+    E = experts if experts is not None else S // (3 * cells)
+    if E < 1 or 3 * E * cells > S:
+        raise RuntimeError("%s: sceneCoordinates [B,%d] is too short for %d expert(s) on the largest grid of shapes (%d cells)"
+                           % (who, S, max(E, 1), cells))
+    return E, shapes
+
+
+def _ragged_call(who, sceneCoordinates, hypAssignment, shapes, experts, cam_args, score_args, want_host):
+    """forward_batch / forward_batch_async with shapes: returns (host records or None, device records or None, scores, first call)."""
+    B, N = hypAssignment.shape
+    if B > MAX_BATCH:
+        raise RuntimeError("%s: hypAssignment holds %d frames, at most %d per call" % (who, B, MAX_BATCH))
+    E, shapes = _ragged_args(who, sceneCoordinates, B, shapes, experts)
+    (shiftX, shiftY, focalLength, ppointX, ppointY), cams = _per_frame_cams(who, B, *cam_args)
+    if isinstance(sceneCoordinates, (list, tuple)):
+        on_dev = [m.device.index for m in sceneCoordinates if m.is_cuda]
+        eng = engine(on_dev[0] if on_dev else None)
+        packed, _ = pack_frames(sceneCoordinates, device=eng.device)
+    else:
+        eng = engine(sceneCoordinates.device.index if sceneCoordinates.is_cuda else None)
+        packed = sceneCoordinates
+    H, W = capacity_shape(shapes)
+    p = eng.make_params(E, H, W, N, shiftX, shiftY, focalLength, ppointX, ppointY, *score_args, seed=_state["seed"],
+                        call=_state["call"], max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"],
+                        strict_reference=_state["strict_reference"])
+    first = _state["call"]
+    scores = torch.empty(B, N, dtype=torch.float64, device=eng.device)
+    # (zeros: a frame whose kernels never reach the record write reads RES_VALID = 0 -> EVAL_STATUS 1, not stale memory)
+    records = None if want_host else torch.zeros(B, RES_DOUBLES, dtype=torch.float64, device=eng.device)
+    res = eng.forward_batch(packed, hypAssignment, p, scores_out=scores, result_out=records, want_host=want_host, cams=cams, shapes=shapes)
+    _state["call"] += B  # (behind the call: a table the library refuses -- a frame's camera beyond its own pixel range -- draws no RNG stream)
+    return res, records, scores, first
+
+
 def forward_batch(sceneCoordinates, hypAssignment, outPoses, shiftX, shiftY, focalLength, ppointX, ppointY,
-                  inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling):
+                  inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling, shapes=None, experts=None):
     """Batched companion of `forward` (new API): sceneCoordinates [B,E,3,H,W] (or [E,3,H,W] shared),
     hypAssignment [B,N] int64, outPoses [B,4,4] float32 written in place; returns the list of winning experts.
     Frame b is what the b-th of B consecutive `forward` calls would compute (discrete outputs identical; poses to the rounding of
     the LM sums, bit for bit when the single calls refine with teams of 8 like a batch does: include/esac_hip.h).
     Each of shiftX, shiftY, focalLength, ppointX, ppointY is a scalar (the whole batch) or a length-B sequence / 1-D tensor /
-    numpy array (frame b uses element b; test sets whose images differ in focal length)."""
-    if hypAssignment.dim() != 2 or hypAssignment.dtype != torch.int64:
+    numpy array (frame b uses element b; test sets whose images differ in focal length).
+    shapes: None, or B (h, w) pairs -- a RAGGED batch, frames that differ in image size (esac_hip_forward_batch_shapes):
+    sceneCoordinates is then the packed [B,S] tensor of `pack_frames`, or a list of B float32 [E,3,h_b,w_b] maps which is packed
+    here; frame b is `forward` on its own maps.  experts: the E of a packed tensor whose S is not pack_frames' own (default:
+    S // (3 * the largest h*w)).  Everything else, and every return value, as without shapes."""
+    if not isinstance(hypAssignment, torch.Tensor) or hypAssignment.dim() != 2 or hypAssignment.dtype != torch.int64:
         raise RuntimeError("esac.forward_batch: hypAssignment must be int64 [B,N]")
+    if shapes is not None:
+        B, N = hypAssignment.shape
+        if not isinstance(outPoses, torch.Tensor) or outPoses.dtype != torch.float32 or tuple(outPoses.shape) != (B, 4, 4):
+            raise RuntimeError("esac.forward_batch: outPoses must be float32 [B,4,4]")
+        res, _, scores, _ = _ragged_call("esac.forward_batch", sceneCoordinates, hypAssignment, shapes, experts,
+                                         (shiftX, shiftY, focalLength, ppointX, ppointY),
+                                         (inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling), True)
+        outPoses.copy_(torch.from_numpy(res[:, RES_POSE:RES_POSE + 16].astype(np.float32).reshape(B, 4, 4)))
+        _state["last"] = {"scores": scores, "result": res}
+        return [int(v) for v in res[:, RES_EXPERT]]
+    if experts is not None:
+        raise RuntimeError("esac.forward_batch: experts is an argument of a ragged batch (shapes=...)")
     if sceneCoordinates.dtype != torch.float32 or sceneCoordinates.dim() not in (4, 5) or sceneCoordinates.size(-3) != 3:
         raise RuntimeError("esac.forward_batch: sceneCoordinates must be float32 [B,E,3,H,W] or [E,3,H,W]")
     B, N = hypAssignment.shape
@@ -1233,15 +1399,24 @@ def eval_batch(records, gtPoses, gtExperts=None, rotThreshold=5.0, transThreshol
 
 
 def forward_batch_async(sceneCoordinates, hypAssignment, shiftX, shiftY, focalLength, ppointX, ppointY,
-                        inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling):
+                        inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling, shapes=None, experts=None):
     """`forward_batch` without the host inside the call: the launches are enqueued on torch's current stream, the result records
     stay on the device and nothing is waited for (device inputs; host tensors are uploaded first).  Arguments as forward_batch,
     minus outPoses.  Returns dict(records = device float64 [B,32] -- RES_VALID 1: a record, 3: the frame's refinement team timed
     out, run it again as a blocking call with refine_solo at call + b (harness.rerun_frames) --, scores = device float64 [B,N],
-    call = the call counter of frame 0, seed); last_result() returns the same dict.  Advances the call counter by B."""
+    call = the call counter of frame 0, seed); last_result() returns the same dict.  Advances the call counter by B.
+    shapes, experts: a ragged batch, as in forward_batch."""
     who = "esac.forward_batch_async"
     if not isinstance(hypAssignment, torch.Tensor) or hypAssignment.dim() != 2 or hypAssignment.dtype != torch.int64 or hypAssignment.numel() == 0:
         raise RuntimeError("%s: hypAssignment must be a non-empty int64 [B,N]" % who)
+    if shapes is not None:
+        _, records, scores, first = _ragged_call(who, sceneCoordinates, hypAssignment, shapes, experts,
+                                                 (shiftX, shiftY, focalLength, ppointX, ppointY),
+                                                 (inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling), False)
+        _state["last"] = {"records": records, "scores": scores, "call": first, "seed": _state["seed"]}
+        return _state["last"]
+    if experts is not None:
+        raise RuntimeError("%s: experts is an argument of a ragged batch (shapes=...)" % who)
     if not isinstance(sceneCoordinates, torch.Tensor) or sceneCoordinates.dtype != torch.float32 or sceneCoordinates.dim() not in (4, 5) \
             or sceneCoordinates.size(-3) != 3:
         raise RuntimeError("%s: sceneCoordinates must be float32 [B,E,3,H,W] or [E,3,H,W]" % who)

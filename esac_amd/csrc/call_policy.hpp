@@ -9,6 +9,7 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
 #include "../../include/esac_hip.h"
 
@@ -31,15 +32,29 @@ inline int fail(int code, const char* fmt, ...) {
 }
 
 // One camera's checks (cam_frame >= 0: a record of a per-frame table, the error names the frame)
-inline int check_cam(const esac_hip_params* p, int shift_x, int shift_y, float focal, int cam_frame) {
+// (H, W: the grid the camera looks at -- p's own, or the frame's in a ragged batch)
+inline int check_cam(const esac_hip_params* p, int shift_x, int shift_y, float focal, int cam_frame, int H, int W) {
     char where[32] = "";
     if (cam_frame >= 0) snprintf(where, sizeof(where), " in frame %d", cam_frame);
     // pixel centres col*sub + sub/2 - shift (esac_util.h:64-66) are formed in int32 on the device
     const int64_t lim = 0x7fffffffLL, half = p->sub_sampling / 2;
-    const int64_t xs[4] = {half - shift_x, (int64_t)(p->W - 1) * p->sub_sampling + half - shift_x, half - shift_y, (int64_t)(p->H - 1) * p->sub_sampling + half - shift_y};
+    const int64_t xs[4] = {half - shift_x, (int64_t)(W - 1) * p->sub_sampling + half - shift_x, half - shift_y, (int64_t)(H - 1) * p->sub_sampling + half - shift_y};
     for (int64_t v : xs)
         if (v > lim || v < -lim) return fail(-4, "pixel positions overflow int32 (subSampling=%d, shift=(%d,%d))%s", p->sub_sampling, shift_x, shift_y, where);
     if (!(focal > 0)) return fail(-4, "focal length must be positive%s", where);
+    return 0;
+}
+inline int check_cam(const esac_hip_params* p, int shift_x, int shift_y, float focal, int cam_frame) {
+    return check_cam(p, shift_x, shift_y, focal, cam_frame, p->H, p->W);
+}
+// The grid-size rule of a call, and of every frame of a ragged batch (frame >= 0: the error names it)
+inline int check_grid(int H, int W, int frame) {
+    char where[32] = "";
+    if (frame >= 0) snprintf(where, sizeof(where), " in frame %d", frame);
+    if (H < 3 || W < 3 || (int64_t)(H - 1) * (W - 1) < 4)
+        return fail(-4, "grid %dx%d too small: 4 distinct cells must exist in [0,W-2]x[0,H-2] (esac_util.h:164-176)%s", H, W, where);
+    if ((int64_t)H * W > (int64_t)1 << 28 || H > 65535 || W > 65535)
+        return fail(-4, "grid %dx%d too large (at most 65535 rows / columns, 2^28 cells)%s", H, W, where);
     return 0;
 }
 // Validation of a call's parameters: what the reference leaves to accessor<>() / OpenCV asserts.  ctx, tensors: the context /
@@ -50,10 +65,7 @@ inline int check_args(bool ctx, bool tensors, const esac_hip_params* p, int B, i
     if (!p) return fail(-1, "null params");
     if (!tensors) return fail(-1, "null scene-coordinate or assignment pointer");
     if (p->E <= 0 || p->N <= 0) return fail(-4, "E=%d, N=%d must be positive", p->E, p->N);
-    if (p->H < 3 || p->W < 3 || (int64_t)(p->H - 1) * (p->W - 1) < 4)
-        return fail(-4, "grid %dx%d too small: 4 distinct cells must exist in [0,W-2]x[0,H-2] (esac_util.h:164-176)", p->H, p->W);
-    if ((int64_t)p->H * p->W > (int64_t)1 << 28 || p->H > 65535 || p->W > 65535)
-        return fail(-4, "grid %dx%d too large (at most 65535 rows / columns, 2^28 cells)", p->H, p->W);
+    if (int rc_grid = check_grid(p->H, p->W, -1)) return rc_grid;
     if (p->sub_sampling <= 0) return fail(-4, "subSampling=%d must be positive", p->sub_sampling);
     if ((p->flags & ESAC_FLAG_STRICT_REFERENCE) && (p->flags & (ESAC_FLAG_SCORE_TILED | ESAC_FLAG_SCORE_STREAM | ESAC_FLAG_AUTO_EXACT)))
         return fail(-4, "ESAC_FLAG_STRICT_REFERENCE cannot be combined with ESAC_FLAG_SCORE_TILED, ESAC_FLAG_SCORE_STREAM or ESAC_FLAG_AUTO_EXACT "
@@ -75,6 +87,14 @@ struct CallScalars {
     int max_tries, max_ref_steps, samp_cap, flags;
     float margin;
 };
+// band of the fp32 maximum that is re-scored exactly: the stream's rounding (<= 2e-5 * alpha measured) plus two
+// cells' weight -- an ill-conditioned projection (scene point next to the camera centre) can put a cell on the other
+// side of tau under fp32, which moves a score by alpha / (H*W); on small grids that exceeds alpha * 1e-3.
+// (cells: the grid the score is summed over -- a frame's own in a ragged batch, never the capacity's: the band of a small
+// frame is wider than the capacity's)
+inline float rescore_margin(const esac_hip_params* p, int cells) {
+    return p->rescore_margin > 0 ? p->rescore_margin : fabsf(p->inlier_alpha) * (ESAC_DEFAULT_MARGIN + 2.0f / (float)cells);
+}
 inline CallScalars call_scalars(const esac_hip_params* p, long long cap_n) {
     CallScalars v;
     v.max_tries = p->max_tries > 0 ? p->max_tries : ESAC_MAX_SAMPLING_TRIES;
@@ -85,10 +105,7 @@ inline CallScalars call_scalars(const esac_hip_params* p, long long cap_n) {
     if (v.flags & ESAC_FLAG_STRICT_REFERENCE) v.flags |= ESAC_FLAG_EXACT_SCORES | ESAC_FLAG_EXACT_SAMPLING;  // (implied)
     // the training path's strict mode: the strict bit the samplers, k_rescore_strict and trial_rejected read, and the two exact routes
     if (v.flags & ESAC_FLAG_STRICT_TRAINING) v.flags |= ESAC_FLAG_STRICT_REFERENCE | ESAC_FLAG_EXACT_SCORES | ESAC_FLAG_EXACT_SAMPLING;
-    // band of the fp32 maximum that is re-scored exactly: the stream's rounding (<= 2e-5 * alpha measured) plus two
-    // cells' weight -- an ill-conditioned projection (scene point next to the camera centre) can put a cell on the other
-    // side of tau under fp32, which moves a score by alpha / (H*W); on small grids that exceeds alpha * 1e-3
-    v.margin = p->rescore_margin > 0 ? p->rescore_margin : fabsf(p->inlier_alpha) * (ESAC_DEFAULT_MARGIN + 2.0f / (float)(p->H * p->W));
+    v.margin = rescore_margin(p, p->H * p->W);
     return v;
 }
 // ESAC_FLAG_AUTO_EXACT: the guaranteed routes where they are free (include/esac_hip.h)
@@ -334,3 +351,5 @@ inline int read_size(int which, size_t bytes, bool have_src, const ReadDims& d, 
 }
 
 }  // namespace esac
+
+#include "ragged_policy.hpp"  // check_shapes, shape_record: the ragged batch (esac_hip_forward_batch_shapes)

@@ -185,8 +185,8 @@ __device__ __forceinline__ void block_sum28(double (&v)[NV], double* s_part, dou
 // buffer is laid out frame-major, so a frame's view is the same KArgs with offset pointers; frame b draws
 // the RNG streams of call + b, which makes a batch bit-identical to B sequential calls.
 // A batch with per-frame cameras (KArgs::cams): the frame's shift, focal length and principal point replace the inline fields
-// here, so every kernel reads the five values AFTER its frame's view is applied.  Frame 0 returns early: the host puts record 0
-// into the inline fields (make_args), which also serves the kernels and launch paths that never take a frame's view.
+// here, so every kernel reads the five values AFTER its frame's view is applied.  Frame 0 keeps the inline fields: the host puts
+// record 0 there (make_args), which also serves the kernels and launch paths that never take a frame's view.
 __device__ __forceinline__ void frame_cam(KArgs& a, int fr) {
     const FrameCam c = a.cams[fr];
     a.shift_x = c.shift_x;
@@ -195,8 +195,17 @@ __device__ __forceinline__ void frame_cam(KArgs& a, int fr) {
     a.ppx = c.ppx;
     a.ppy = c.ppy;
 }
-__device__ __forceinline__ void frame_view(KArgs& a, int fr) {
-    if (fr == 0) return;
+// A ragged batch (KArgs::shapes): the strides below are taken from the inline capacity shape like any batch's; only then do the
+// frame's own grid and re-score margin replace H, W and margin -- for frame 0 too, whose camera is inline but whose shape is not.
+// The record is the one frame_cam reads (a scalar load at an address that depends on the workgroup's frame only).
+__device__ __forceinline__ void frame_shape(KArgs& a, int fr) {
+    const FrameCam c = a.cams[fr];
+    a.H = c.h;
+    a.W = c.w;
+    a.margin = c.margin;
+}
+// the pointers and the camera of frame fr != 0 (every stride from the inline shape: the capacity of a ragged batch)
+__device__ __forceinline__ void frame_strides(KArgs& a, int fr) {
     if (a.cams) frame_cam(a, fr);
     const size_t N = (size_t)a.N, P = (size_t)a.H * a.W, f = (size_t)fr;
     a.sc += f * a.sc_frame_stride;
@@ -226,6 +235,12 @@ __device__ __forceinline__ void frame_view(KArgs& a, int fr) {
     if (a.scores_user) a.scores_user += f * N;
     if (a.result_user) a.result_user += f * 32;
     if (a.result_pin) a.result_pin += f * ESAC_PIN_DOUBLES;
+}
+// (ONE site for the shape, behind the strides, and not a second one in an early return for frame 0: with two, the single-frame
+// sampler k_sample<256, 2> -- whose H and W then merge from three places -- issued 54 more register-file copies in its try loop)
+__device__ __forceinline__ void frame_view(KArgs& a, int fr) {
+    if (fr != 0) frame_strides(a, fr);
+    if (a.shapes) frame_shape(a, fr);
 }
 
 __device__ __forceinline__ void frame_view(KArgs& a) { frame_view(a, (int)blockIdx.y); }
@@ -334,10 +349,11 @@ __device__ __forceinline__ Centre centre_fallback(const Centre& c, bool mid_ok, 
     }
     return n < 2 && mid_ok ? c : best;
 }
-__device__ __forceinline__ Centre map_centre(const KArgs& a, const float* __restrict__ map) {
-    const int P = a.H * a.W, mid = (a.H >> 1) * a.W + (a.W >> 1);
-    const int y0 = a.H >> 2, y1 = (3 * a.H) >> 2, x0 = a.W >> 2, x1 = (3 * a.W) >> 2;
-    const int c0 = y0 * a.W + x0, c1 = y0 * a.W + x1, c2 = y1 * a.W + x0, c3 = y1 * a.W + x1;
+// (H, W: the grid of the map -- a.H, a.W behind the frame's view; k_sample_decide, whose lanes serve different frames, passes its own)
+__device__ __forceinline__ Centre map_centre(int H, int W, const float* __restrict__ map) {
+    const int P = H * W, mid = (H >> 1) * W + (W >> 1);
+    const int y0 = H >> 2, y1 = (3 * H) >> 2, x0 = W >> 2, x1 = (3 * W) >> 2;
+    const int c0 = y0 * W + x0, c1 = y0 * W + x1, c2 = y1 * W + x0, c3 = y1 * W + x1;
     // all fifteen loads first and nothing conditional before the last of them is used: ONE trip to memory, as the middle cell
     // alone was.  (Written probe by probe with `if (finite)` around the box update, the compiler put each probe's loads behind
     // the previous probe's branch: four trips in a row at the head of k_score_fast, 1.7 % of the headline call.)
@@ -360,6 +376,7 @@ __device__ __forceinline__ Centre map_centre(const KArgs& a, const float* __rest
     if (__builtin_expect(inside, 1)) return c;
     return centre_fallback(c, mid_ok, q, ok, n);
 }
+__device__ __forceinline__ Centre map_centre(const KArgs& a, const float* __restrict__ map) { return map_centre(a.H, a.W, map); }
 
 
 // ---- speculative forward (KArgs::spec_mode): hand-offs between the streams of a call

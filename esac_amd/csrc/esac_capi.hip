@@ -108,6 +108,8 @@ struct esac_hip_ctx {
     DevBufs fwd_bufs;    // the forward workspace (ensure_ws)
     DevBufs tiled_bufs;  // the tile-stationary score workspace (ensure_tiled_ws); dies with the forward workspace
     int lastN = 0, lastH = 0, lastW = 0;
+    size_t last_map1 = 0;  // where frame 0's SECOND inlier-map buffer starts in its slot: the cells of the grid frame 0's refinement
+                           // ran on (k_refine alternates maps + cur * P with ITS P) -- lastH * lastW, or frame 0's own h * w after a ragged batch
     int lastB = 1;  // frames of the most recent launch set (esac_hip_read: B x the single-frame size reads the per-frame forward buffers of all of them)
     bool keep_errs = false;  // esac_hip_set_debug: store the winner's error image
     PinView pin;
@@ -439,6 +441,7 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
     }
     a.frames = B; a.sc_frame_stride = sc_frame_stride;
     a.cams = nullptr;  // (the _cams entry points set it after stage_cams)
+    a.shapes = 0;      // (esac_hip_forward_batch_shapes sets it with the table)
     a.sc = d_sc; a.assign = d_assign;
     a.E = p->E; a.H = p->H; a.W = p->W; a.N = p->N;
     a.shift_x = p->shift_x; a.shift_y = p->shift_y; a.sub = p->sub_sampling;
@@ -458,6 +461,7 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
     // (device-side span stamps only on sampled calls in timing mode: forward_impl clears tstamps otherwise)
     if (!c->keep_errs) a.errs = nullptr;
     c->lastN = p->N; c->lastH = p->H; c->lastW = p->W;
+    c->last_map1 = (size_t)P;  // (a ragged batch: prepare_forward puts frame 0's own cell count here)
     c->lastB = B;
     c->train.last_dev_batch = 0;  // (esac_hip_backward_batch_dev sets it again once its launches are queued)
     *out = a;
@@ -468,11 +472,20 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
 // make_args with record 0), then staged in pinned memory of the context's own and uploaded on `s` -- once per call; chunks and
 // re-runs offset the device pointer.  The staging is rewritten only after the previous upload has left it (an asynchronous
 // forward batch may still have its copy queued); the device table is rewritten in stream order behind its last readers.
-static int stage_cams(esac_hip_ctx* c, const esac_hip_params* p, const esac_hip_frame_cam* h_cams, int B, hipStream_t s) {
+// shapes_vec != null: a ragged batch (esac_hip_forward_batch_shapes) -- every record is checked with its own grid (check_shapes),
+// staged with its own re-score margin (shape_record), and *shapes_vec says whether every frame's width is a multiple of 4.
+static int stage_cams(esac_hip_ctx* c, const esac_hip_params* p, const esac_hip_frame_cam* h_cams, int B, hipStream_t s,
+                      int64_t sc_frame_stride = 0, bool* shapes_vec = nullptr) {
     static_assert(sizeof(esac_hip_frame_cam) == sizeof(FrameCam) && offsetof(esac_hip_frame_cam, focal) == offsetof(FrameCam, focal) &&
                   offsetof(esac_hip_frame_cam, ppy) == offsetof(FrameCam, ppy), "esac_hip_frame_cam is the device record");
-    for (int b = 0; b < B; b++)
-        if (int rc = check_cam(p, h_cams[b].shift_x, h_cams[b].shift_y, h_cams[b].focal, b)) return rc;
+    static_assert(offsetof(esac_hip_frame_cam, reserved) == offsetof(FrameCam, h) && offsetof(FrameCam, w) == offsetof(FrameCam, h) + 4 &&
+                  offsetof(FrameCam, margin) == offsetof(FrameCam, h) + 8, "reserved[0..2] = the frame's h, w and margin");
+    if (shapes_vec) {
+        if (int rc = check_shapes(p, B, h_cams, sc_frame_stride, shapes_vec)) return rc;
+    } else {
+        for (int b = 0; b < B; b++)
+            if (int rc = check_cam(p, h_cams[b].shift_x, h_cams[b].shift_y, h_cams[b].focal, b)) return rc;
+    }
     if (!c->stage.h_cams) {
         HIP_OK(hipHostMalloc((void**)&c->stage.h_cams, (size_t)ESAC_MAX_BATCH * sizeof(FrameCam), hipHostMallocDefault));
         HIP_OK(hipMalloc((void**)&c->stage.d_cams, (size_t)ESAC_MAX_BATCH * sizeof(FrameCam)));
@@ -483,6 +496,11 @@ static int stage_cams(esac_hip_ctx* c, const esac_hip_params* p, const esac_hip_
         c->stage.cams_queued = false;
     }
     memcpy(c->stage.h_cams, h_cams, (size_t)B * sizeof(FrameCam));
+    if (shapes_vec)
+        for (int b = 0; b < B; b++) {
+            const esac_hip_frame_cam r = shape_record(p, h_cams[b]);
+            memcpy(c->stage.h_cams + b, &r, sizeof(r));
+        }
     HIP_OK(hipMemcpyAsync(c->stage.d_cams, c->stage.h_cams, (size_t)B * sizeof(FrameCam), hipMemcpyHostToDevice, s));
     HIP_OK(hipEventRecord(c->stage.cams_ev, s));
     c->stage.cams_queued = true;
@@ -597,13 +615,21 @@ static inline const char* enqueue_serial_stage(esac_hip_ctx* c, const KArgs& a, 
 }
 // A forward call up to its first launch (p carries record 0 of a per-frame camera table in its inline fields); *tm: the call is timed
 static int prepare_forward(esac_hip_ctx* c, const float* d_sc, long long sc_frame_stride, const int64_t* d_assign, const esac_hip_params* p,
-                           int B, hipStream_t s, const esac_hip_frame_cam* h_cams, double t_entry, KArgs* out, bool* tm) {
+                           int B, hipStream_t s, const esac_hip_frame_cam* h_cams, bool shapes, double t_entry, KArgs* out, bool* tm) {
     KArgs& a = *out;
     int rc = make_args(c, d_sc, d_assign, p, &a, B, sc_frame_stride, h_cams ? 0 : -1);
     if (rc) return rc;
     if (h_cams && B > 1) {  // (one frame: record 0 is the whole table)
-        if ((rc = stage_cams(c, p, h_cams, B, s))) return rc;
+        // shapes: p's H x W is the capacity -- make_args has sized the workspaces, and every host decision below reads a.H * a.W as
+        // that (team size and cells per lane, LDS or global list, the selection's split, the sampler's plan); the kernels take the
+        // frame's own grid and margin from the table (device_common.hpp:frame_view)
+        bool all_vec = true;
+        if ((rc = stage_cams(c, p, h_cams, B, s, sc_frame_stride, shapes ? &all_vec : nullptr))) return rc;
         a.cams = c->stage.d_cams;
+        a.shapes = !shapes ? 0 : all_vec ? 1 : 2;
+        // esac_hip_read(ESAC_BUF_INLIER_MAP): the one-workgroup refinement alternates its two map buffers P cells apart with the
+        // P of the frame's OWN grid (the team kernel only ever writes buffer 0)
+        if (shapes) c->last_map1 = (size_t)h_cams[0].reserved[0] * (size_t)h_cams[0].reserved[1];
     }
     c->team.latch.forward_call();
     forward_team(c, a);
@@ -753,7 +779,8 @@ static int collect_records(esac_hip_ctx* c, KArgs& a, int B, hipStream_t s, doub
 }
 
 static int forward_impl(esac_hip_ctx* c, const float* d_sc, long long sc_frame_stride, const int64_t* d_assign,
-                        const esac_hip_params* p, int B, void* stream, double* d_scores_out, double* d_result_out, double* h_result_out, const esac_hip_frame_cam* h_cams = nullptr) {
+                        const esac_hip_params* p, int B, void* stream, double* d_scores_out, double* d_result_out, double* h_result_out, const esac_hip_frame_cam* h_cams = nullptr,
+                        bool shapes = false) {
     if (!c) return fail(-1, "null context");
     const double t_entry = now_ns();
     DeviceGuard guard(c->device);
@@ -763,9 +790,19 @@ static int forward_impl(esac_hip_ctx* c, const float* d_sc, long long sc_frame_s
         p0 = with_cam(*p, h_cams[0]);
         p = &p0;
     }
+    if (shapes && p && B == 1) {
+        // a ragged batch of one frame IS the single call on that frame's grid: checked like any table, then record 0's shape
+        // stands in the parameter block and every single-frame route (tiled score, packed maps, speculation) is open to it
+        bool all_vec;
+        if (int rc0 = check_args(true, d_sc && d_assign, p, B, 0, false)) return rc0;
+        if (int rc0 = check_shapes(p, 1, h_cams, sc_frame_stride, &all_vec)) return rc0;
+        p0.H = h_cams[0].reserved[0];
+        p0.W = h_cams[0].reserved[1];
+        shapes = false;
+    }
     KArgs a;
     bool tm = false;
-    int rc = prepare_forward(c, d_sc, sc_frame_stride, d_assign, p, B, s, h_cams, t_entry, &a, &tm);
+    int rc = prepare_forward(c, d_sc, sc_frame_stride, d_assign, p, B, s, h_cams, shapes, t_entry, &a, &tm);
     if (rc) return rc;
     a.scores_user = d_scores_out; a.result_user = d_result_out;
     a.result_pin = h_result_out ? c->pin.d : nullptr;
@@ -984,6 +1021,14 @@ extern "C" int esac_hip_forward_batch_cams(esac_hip_ctx* c, int B, const float* 
                                            void* stream, double* d_scores_out, double* d_result_out, double* h_result_out) {
     if (h_cams && (B < 1 || B > ESAC_MAX_BATCH)) return fail(-4, "batch size %d outside [1,%d]", B, ESAC_MAX_BATCH);  // (before h_cams[0] is read)
     return forward_impl(c, d_sc, (long long)sc_frame_stride, d_assign, p, B, stream, d_scores_out, d_result_out, h_result_out, h_cams);
+}
+// Frames that differ in image size: esac_hip_forward_batch_cams with frame b's grid in h_cams[b].reserved[0..1]; p->H * p->W is
+// the capacity in cells (include/esac_hip.h).  reserved[2] is the library's (the frame's margin goes there on the way to the device).
+extern "C" int esac_hip_forward_batch_shapes(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, const int64_t* d_assign, const esac_hip_params* p, const esac_hip_frame_cam* h_cams,
+                                             void* stream, double* d_scores_out, double* d_result_out, double* h_result_out) {
+    if (!h_cams) return fail(-1, "esac_hip_forward_batch_shapes: null frame table (h_cams carries every frame's grid)");
+    if (B < 1 || B > ESAC_MAX_BATCH) return fail(-4, "batch size %d outside [1,%d]", B, ESAC_MAX_BATCH);  // (before h_cams[0] is read)
+    return forward_impl(c, d_sc, (long long)sc_frame_stride, d_assign, p, B, stream, d_scores_out, d_result_out, h_result_out, h_cams, true);
 }
 
 // ---------------------------------------------------------------- training path
@@ -1402,7 +1447,8 @@ extern "C" int esac_hip_read(esac_hip_ctx* c, int which, void* h_dst, size_t byt
                 memset(h_dst, 0, P);
                 return 0;
             }
-            HIP_OK(hipMemcpy(h_dst, c->ws.inlier_map + (which_buf > 0.5 ? P : 0), P, hipMemcpyDeviceToHost));
+            // (after a ragged batch the P bytes are frame 0's slot view: its map is the first h_0 * w_0 of them; last_map1 + P <= 2 P)
+            HIP_OK(hipMemcpy(h_dst, c->ws.inlier_map + (which_buf > 0.5 ? c->last_map1 : 0), P, hipMemcpyDeviceToHost));
             return 0;
         }
         case ESAC_BUF_BWD_TEAM_INFO: {

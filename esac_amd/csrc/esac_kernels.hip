@@ -73,15 +73,15 @@ __device__ __forceinline__ bool cannot_pass(double reproj2, double tau) {
 // the 4 cells of try t of hypothesis gh, their scene points and pixel positions.  With the planar [E,3,H,W] layout a
 // cell is three 4-byte reads from three cache lines; when the maps are too large for the caches (KArgs::sc4, see
 // k_pack_cells) the sampler reads one 16-byte (x, y, z, -) record per cell instead.
-// (shift_x, shift_y: the frame's -- a.shift_x, a.shift_y wherever the frame's view has been applied)
+// (shift_x, shift_y, W, H: the frame's -- a.shift_x, a.shift_y, a.W, a.H wherever the frame's view has been applied)
 __device__ __forceinline__ void gather_sample(const KArgs& a, const float* __restrict__ map, int P, const Philox& rng, uint32_t gh,
                                               uint32_t t, int (&cx)[4], int (&cy)[4], V3 (&Pt)[4], float (&Pf)[4][3],
-                                              double (&mu)[4], double (&mv)[4], int shift_x, int shift_y) {
-    draw_cells(rng, gh, t, a.W, a.H, cx, cy);
+                                              double (&mu)[4], double (&mv)[4], int shift_x, int shift_y, int W, int H) {
+    draw_cells(rng, gh, t, W, H, cx, cy);
     const float4* __restrict__ map4 = a.sc4 ? a.sc4 + (size_t)(map - a.sc) / 3 : nullptr;  // (map - sc) / 3 = expert * P
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        const int idx = cy[j] * a.W + cx[j];
+        const int idx = cy[j] * W + cx[j];
         if (map4) {
             const float4 v = map4[idx];
             Pf[j][0] = v.x; Pf[j][1] = v.y; Pf[j][2] = v.z;
@@ -98,7 +98,7 @@ __device__ __forceinline__ void gather_sample(const KArgs& a, const float* __res
 __device__ __forceinline__ void gather_sample(const KArgs& a, const float* __restrict__ map, int P, const Philox& rng, uint32_t gh,
                                               uint32_t t, int (&cx)[4], int (&cy)[4], V3 (&Pt)[4], float (&Pf)[4][3],
                                               double (&mu)[4], double (&mv)[4]) {
-    gather_sample(a, map, P, rng, gh, t, cx, cy, Pt, Pf, mu, mv, a.shift_x, a.shift_y);
+    gather_sample(a, map, P, rng, gh, t, cx, cy, Pt, Pf, mu, mv, a.shift_x, a.shift_y, a.W, a.H);
 }
 
 // planar [E,3,H,W] -> [E,H*W] records (x, y, z, 0): one coalesced pass (12 B read, 16 B written per cell), paid once per
@@ -445,25 +445,27 @@ __global__ __launch_bounds__(64) void k_sample_decide(KArgs a0) {
         const int64_t* assign = a0.assign + (size_t)fr * a0.N;
         const long long ev = a0.E == 1 ? 0 : assign[h];
         const int e = (unsigned long long)ev < (unsigned long long)a0.E ? (int)ev : 0;
-        const int P = a0.H * a0.W;
-        const float* __restrict__ map = sc + (size_t)e * 3 * P;
         const Philox rng(a0.seed, a0.call + (uint64_t)fr);
         // ... and its camera: the one kernel in which the frame differs from lane to lane, so a batch with per-frame cameras
-        // reads the record per lane here (a 32-byte load per listed try; nothing when the table is null)
+        // reads the record per lane here (a 32-byte load per listed try; nothing when the table is null) -- and with it the
+        // frame's grid in a ragged batch (KArgs::shapes)
         Cam cam = make_cam(a0);
-        int shift_x = a0.shift_x, shift_y = a0.shift_y;
+        int shift_x = a0.shift_x, shift_y = a0.shift_y, H = a0.H, W = a0.W;
         if (a0.cams) {
             const FrameCam fc = a0.cams[fr];
             cam = Cam{(double)fc.focal, (double)fc.focal, (double)fc.ppx, (double)fc.ppy};
             shift_x = fc.shift_x;
             shift_y = fc.shift_y;
+            if (a0.shapes) H = fc.h, W = fc.w;
         }
+        const int P = H * W;
+        const float* __restrict__ map = sc + (size_t)e * 3 * P;
         const uint32_t gh = (uint32_t)global_hyp(a0, h);
         int cx[4], cy[4];
         V3 Pt[4];
         float Pf[4][3];
         double mu[4], mv[4], Rp[9], Tp[3], reproj2 = 0;
-        gather_sample(a0, map, P, rng, gh, (uint32_t)t, cx, cy, Pt, Pf, mu, mv, shift_x, shift_y);
+        gather_sample(a0, map, P, rng, gh, (uint32_t)t, cx, cy, Pt, Pf, mu, mv, shift_x, shift_y, W, H);
         bool solved;
         if (quad) {  // the four lanes of this entry replay p3p_4pt's scan over the candidates (k_sample: same rule, same NaN behaviour)
             const int lane = threadIdx.x, root = lane & 3, quad0 = lane & ~3;
@@ -498,7 +500,7 @@ __global__ __launch_bounds__(64) void k_sample_decide(KArgs a0) {
                 cd[0] = rvec[0]; cd[1] = rvec[1]; cd[2] = rvec[2]; cd[3] = T[0]; cd[4] = T[1]; cd[5] = T[2];
 #pragma unroll
                 for (int k = 0; k < 9; k++) cd[6 + k] = R[k];
-                const Centre c = map_centre(a0, map);
+                const Centre c = map_centre(H, W, map);
                 float* cf = reinterpret_cast<float*>(cd + 15);  // 12 floats: [R | t + R c] (store_rt32)
 #pragma unroll
                 for (int k = 0; k < 9; k++) cf[k] = (float)R[k];

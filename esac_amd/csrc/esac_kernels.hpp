@@ -119,10 +119,13 @@ constexpr int ESAC_SPEC_CNT_FAN = 32, ESAC_SPEC_CNT_STRIDE = 32;  // counters of
 constexpr int ESAC_SPEC_CNT_INTS = ESAC_SPEC_CNT_STRIDE * (1 + ESAC_SPEC_CNT_FAN);
 // One frame's camera in a batch with per-frame cameras (= esac_hip_frame_cam, include/esac_hip.h): 32 bytes, so that a frame's
 // record is one aligned scalar load (s_load_dwordx8) at an address that depends on the workgroup's frame only.
+// A batch whose frames differ in image size (esac_hip_forward_batch_shapes, KArgs::shapes) carries the frame's grid and its
+// re-score margin in the three words the camera-only entry points leave unread: still the one scalar load.
 struct FrameCam {
     int shift_x, shift_y;
     float focal, ppx, ppy;
-    int pad_[3];
+    int h, w;      // KArgs::shapes only: the frame's grid (esac_hip_frame_cam::reserved[0..1])
+    float margin;  // KArgs::shapes only: call_scalars' margin for h x w (the host writes it over reserved[2])
 };
 static_assert(sizeof(FrameCam) == 32, "one aligned 32-byte record per frame");
 
@@ -231,6 +234,10 @@ struct KArgs {
     long long sc_frame_stride;  // elements between the coordinate tensors of consecutive frames
     const FrameCam* cams;       // per-frame cameras [B] (esac_hip_*_batch_cams), or null: every frame uses the inline shift_x .. ppy.
                                 // When set, the inline fields hold record 0 (frame_view resolves the others)
+    int shapes;                 // 0: every frame is the inline H x W.  A ragged batch (esac_hip_forward_batch_shapes; needs cams): the
+                                // inline H x W is the CAPACITY -- what every per-frame buffer, stride and launch is sized by -- and
+                                // frame_view puts cams[b].h, .w, .margin into H, W, margin (frame 0 included) AFTER the strides are
+                                // taken.  1: every frame's w is a multiple of 4 (the 16-byte error pass is legal), 2: not all are
     BwdArgs bwd;                // training path only
 };
 

@@ -612,11 +612,14 @@ unsigned long long next_refine_tag() {
     return (seq.fetch_add(1) + 1ull) << 20;
 }
 
+// W % 4 == 0 for EVERY frame of the launch: the inline W, or what the host found in the table of a ragged batch (KArgs::shapes)
+static bool rows_vectorise(const KArgs& a) { return a.shapes ? a.shapes == 1 : (a.W & 3) == 0; }
+
 unsigned long long launch_refine(const KArgs& a, hipStream_t s) {
     constexpr int B = REFINE_B;
-    const bool global_list = a.H * a.W > LDS_CAP;
+    const bool global_list = a.H * a.W > LDS_CAP;  // (a ragged batch: the capacity decides for every frame; a smaller frame fits either list)
     // 16-byte accesses: W % 4 == 0 keeps every row, plane (P % 4 == 0) and expert map 16-byte aligned
-    const bool vec = (a.W & 3) == 0 && (reinterpret_cast<uintptr_t>(a.sc) & 15) == 0;
+    const bool vec = rows_vectorise(a) && (reinterpret_cast<uintptr_t>(a.sc) & 15) == 0;
     if (!a.solo && refine_team_members(a) > 0) return launch_refine_team(a, s);  // single frames (and small batches) on grids up to 32768 cells
     const int slice = a.solo ? 0 : refine_coop_slice(a);
     if (slice > 0) {
@@ -642,7 +645,7 @@ unsigned long long launch_refine(const KArgs& a, hipStream_t s) {
 void launch_refine_slots(const KArgs& a, hipStream_t s) {
     constexpr int B = REFINE_B;
     const bool global_list = a.H * a.W > LDS_CAP;
-    const bool vec = (a.W & 3) == 0 && (reinterpret_cast<uintptr_t>(a.sc) & 15) == 0 && (a.frames == 1 || (a.sc_frame_stride & 3) == 0);
+    const bool vec = rows_vectorise(a) && (reinterpret_cast<uintptr_t>(a.sc) & 15) == 0 && (a.frames == 1 || (a.sc_frame_stride & 3) == 0);
     const dim3 grid(a.N < a.bwd.cap ? a.N : a.bwd.cap, a.frames);
     if (global_list) {
         if (vec) hipLaunchKernelGGL((k_refine<B, true, true, true>), grid, dim3(B), 0, s, a);

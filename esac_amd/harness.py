@@ -164,7 +164,12 @@ def localize_batch(images, gating, experts, focal_lengths, gt_poses=None, gt_exp
     prediction [B,E,3,h,w] device, active_experts [B] device, call (frame 0's call counter; frame b ran at call + b), seed, time_s
     and what `rerun_frames` needs).  Not asynchronous: also poses [B,4,4] float32 cpu, experts (list of B ints), records_host,
     eval as a numpy array [B,16] (the device tensor stays under eval_device) and active_experts as a list; frames with status 3
-    have been run again already."""
+    have been run again already.
+    images may also be a LIST of B images [1,3,H_b,W_b] (or [3,H_b,W_b]) of different sizes: a ragged batch (`_localize_ragged`)."""
+    if isinstance(images, (list, tuple)):
+        return _localize_ragged(list(images), gating, experts, focal_lengths, gt_poses, gt_experts, hypotheses, threshold, inlier_alpha,
+                                inlier_beta, max_reprojection, subsample, e_hyps, expert_selection, oracle_experts, generator,
+                                asynchronous, all_experts, strict_reference, rot_threshold_deg, trans_threshold_cm)
     dev = images.device
     B, E = int(images.size(0)), len(experts)
     pp_x = float(images.size(3) / 2)
@@ -173,12 +178,28 @@ def localize_batch(images, gating, experts, focal_lengths, gt_poses=None, gt_exp
     pred_h = math.ceil(images.size(2) / subsample)
     focals = _focal_list("localize_batch", focal_lengths, B)
     start = time.time()
+    e_hyps = _draw_hyps(lambda: torch.exp(gating(images)), B, dev, e_hyps, hypotheses, expert_selection, oracle_experts, generator)
+    e_hist = torch.zeros((B, E), device=dev).scatter_add_(1, e_hyps, torch.ones(e_hyps.shape, device=dev))
+    active_count = (e_hist > 0).sum(dim=1)  # [B], device
+    if all_experts:
+        active_any = [True] * E  # no flags cross to the host: every expert runs
+    else:
+        active_any = (e_hist > 0).any(dim=0).cpu().tolist()  # E flags: all that reaches the host before the call
+    outputs = [experts[e](images) if on else torch.zeros((B, 3, pred_h, pred_w), device=dev) for e, on in enumerate(active_any)]
+    prediction = torch.stack(outputs, dim=1)  # [B,E,3,h,w]; rows of inactive experts are never read
+    return _solve_batch(prediction, None, e_hyps, e_hist, active_count, focals, pp_x, pp_y, gt_poses, gt_experts, threshold, inlier_alpha,
+                        inlier_beta, max_reprojection, subsample, asynchronous, strict_reference, rot_threshold_deg, trans_threshold_cm, start)
+
+
+def _draw_hyps(gating_probs_of, B, dev, e_hyps, hypotheses, expert_selection, oracle_experts, generator):
+    """The hypothesis assignment [B,N] of a batch: the caller's, or one multinomial row per frame from the gating's
+    probabilities (gating_probs_of() -> [B,E] on the device; only called when they are needed)."""
     if e_hyps is not None:
         e_hyps = torch.as_tensor(e_hyps, dtype=torch.int64).to(dev)
         if e_hyps.dim() != 2 or e_hyps.size(0) != B:
             raise RuntimeError("localize_batch: e_hyps must be [B,N]")
     else:
-        gating_probs = torch.exp(gating(images))  # [B,E], stays on the device
+        gating_probs = gating_probs_of()  # [B,E], stays on the device
         if oracle_experts is not None:
             oracle = torch.as_tensor(oracle_experts, dtype=torch.int64).reshape(-1)
             if oracle.numel() != B:
@@ -189,27 +210,28 @@ def localize_batch(images, gating, experts, focal_lengths, gt_poses=None, gt_exp
             e_hyps = expert.expand((B, hypotheses))  # stride-0 rows, as in the reference
         else:
             e_hyps = torch.multinomial(gating_probs, hypotheses, replacement=True, generator=generator)  # one row of draws per frame
-    e_hist = torch.zeros((B, E), device=dev).scatter_add_(1, e_hyps, torch.ones(e_hyps.shape, device=dev))
-    active_count = (e_hist > 0).sum(dim=1)  # [B], device
-    if all_experts:
-        active_any = [True] * E  # no flags cross to the host: every expert runs
-    else:
-        active_any = (e_hist > 0).any(dim=0).cpu().tolist()  # E flags: all that reaches the host before the call
-    outputs = [experts[e](images) if on else torch.zeros((B, 3, pred_h, pred_w), device=dev) for e, on in enumerate(active_any)]
-    prediction = torch.stack(outputs, dim=1)  # [B,E,3,h,w]; rows of inactive experts are never read
+    return e_hyps
+
+
+def _solve_batch(prediction, shapes, e_hyps, e_hist, active_count, focals, pp_x, pp_y, gt_poses, gt_experts, threshold, inlier_alpha,
+                 inlier_beta, max_reprojection, subsample, asynchronous, strict_reference, rot_threshold_deg, trans_threshold_cm, start):
+    """The solver half of localize_batch: ONE forward batch, ONE eval_batch, the result dict.  shapes: None and prediction
+    [B,E,3,h,w], or the B grids of a ragged batch with prediction the packed [B,S] buffer (pp_x, pp_y then hold B values)."""
+    B, E = int(e_hyps.shape[0]), int(e_hist.shape[1])
     e_hyps = e_hyps.contiguous()
     strict_before = api._state["strict_reference"]
     strict = bool(strict_before or strict_reference)
     api.set_strict_reference(strict)
     try:
+        ragged = {} if shapes is None else dict(shapes=shapes, experts=E)
         fwd = api.forward_batch_async(prediction, e_hyps, 0, 0, focals, pp_x, pp_y, threshold, inlier_alpha, inlier_beta,
-                                      max_reprojection, subsample)
+                                      max_reprojection, subsample, **ragged)
     finally:
         api.set_strict_reference(strict_before)
     ev = None
     if gt_poses is not None:
         ev = api.eval_batch(fwd["records"], gt_poses, gt_experts, rot_threshold_deg, trans_threshold_cm)
-    out = dict(records=fwd["records"], scores=fwd["scores"], eval=ev, e_hyps=e_hyps, e_hist=e_hist, prediction=prediction,
+    out = dict(records=fwd["records"], scores=fwd["scores"], eval=ev, e_hyps=e_hyps, e_hist=e_hist, prediction=prediction, shapes=shapes,
                active_experts=active_count, call=fwd["call"], seed=fwd["seed"], focals=focals, gt_poses=gt_poses, gt_experts=gt_experts,
                solver=dict(pp_x=pp_x, pp_y=pp_y, threshold=threshold, inlier_alpha=inlier_alpha, inlier_beta=inlier_beta,
                            max_reprojection=max_reprojection, subsample=subsample, strict_reference=strict,
@@ -230,6 +252,53 @@ def localize_batch(images, gating, experts, focal_lengths, gt_poses=None, gt_exp
     return out
 
 
+@torch.no_grad()
+def _localize_ragged(images, gating, experts, focal_lengths, gt_poses, gt_experts, hypotheses, threshold, inlier_alpha, inlier_beta,
+                     max_reprojection, subsample, e_hyps, expert_selection, oracle_experts, generator, asynchronous, all_experts,
+                     strict_reference, rot_threshold_deg, trans_threshold_cm):
+    """localize_batch over images of different sizes (test sets resized by their shorter edge).  The networks run once per group
+    of equally sized images and write straight into the packed buffer of a ragged batch (esac.pack_frames' layout: frame b's
+    [E,3,h_b,w_b] dense at the head of row b); every frame gets its own principal point (the image centre) and focal length; then
+    ONE solver call (`esac.forward_batch_async(shapes=...)`) and ONE `esac.eval_batch` for the whole batch, as with one size.
+    The result dict is localize_batch's with prediction = the packed [B,S] buffer and shapes = [(h_b, w_b)]."""
+    images = [im if im.dim() == 4 else im.unsqueeze(0) for im in images]
+    B, E = len(images), len(experts)
+    if B == 0 or any(im.dim() != 4 or im.size(0) != 1 for im in images):
+        raise RuntimeError("localize_batch: images must be a [B,3,H,W] tensor or a non-empty list of [1,3,H,W] / [3,H,W] images")
+    dev = images[0].device
+    focals = _focal_list("localize_batch", focal_lengths, B)
+    pp_x = [float(im.size(3) / 2) for im in images]
+    pp_y = [float(im.size(2) / 2) for im in images]
+    shapes = [(math.ceil(im.size(2) / subsample), math.ceil(im.size(3) / subsample)) for im in images]
+    groups = {}  # image size -> frames, in order of first appearance
+    for b, im in enumerate(images):
+        groups.setdefault(tuple(im.shape[1:]), []).append(b)
+    stacked = {key: torch.cat([images[b] for b in members]) for key, members in groups.items()}
+    start = time.time()
+
+    def gating_probs():
+        probs = torch.zeros((B, E), device=dev)
+        for key, members in groups.items():
+            probs[torch.as_tensor(members, device=dev)] = torch.exp(gating(stacked[key]))
+        return probs
+
+    e_hyps = _draw_hyps(gating_probs, B, dev, e_hyps, hypotheses, expert_selection, oracle_experts, generator)
+    e_hist = torch.zeros((B, E), device=dev).scatter_add_(1, e_hyps, torch.ones(e_hyps.shape, device=dev))
+    active_count = (e_hist > 0).sum(dim=1)  # [B], device
+    active = None if all_experts else (e_hist > 0).cpu().tolist()  # B x E flags: all that reaches the host before the call
+    packed = torch.zeros((B, api.packed_stride(E, shapes)), dtype=torch.float32, device=dev)
+    for key, members in groups.items():
+        h, w = shapes[members[0]]
+        for e in range(E):
+            if active is not None and not any(active[b][e] for b in members):
+                continue  # (rows of inactive experts are never read)
+            maps = experts[e](stacked[key])  # [n,3,h,w]
+            for i, b in enumerate(members):
+                packed[b, :3 * E * h * w].view(E, 3, h, w)[e] = maps[i]
+    return _solve_batch(packed, shapes, e_hyps, e_hist, active_count, focals, pp_x, pp_y, gt_poses, gt_experts, threshold, inlier_alpha,
+                        inlier_beta, max_reprojection, subsample, asynchronous, strict_reference, rot_threshold_deg, trans_threshold_cm, start)
+
+
 def frames_to_rerun(eval_host):
     """Indices of the rows of a host copy of `eval` ([n,16]) whose EVAL_STATUS is 3: frames of an asynchronous batch whose
     refinement team timed out (include/esac_hip.h, ESAC_RES_VALID = 3).  A pure function."""
@@ -245,19 +314,25 @@ def rerun_frames(batch_out, frames):
     against the float32 ground truth the device row used.  Host-side entries of `batch_out` (records_host, poses, experts, eval as
     numpy) are updated in place where they exist."""
     pred, e_hyps, s = batch_out["prediction"], batch_out["e_hyps"], batch_out["solver"]
-    B, E, _, H, W = pred.shape
-    N = int(e_hyps.shape[1])
+    shapes = batch_out.get("shapes")  # a ragged batch: the frame's own maps, grid and principal point
+    B, N = int(e_hyps.shape[0]), int(e_hyps.shape[1])
+    E = int(batch_out["e_hist"].shape[1]) if shapes is not None else int(pred.shape[1])
     eng = api.engine(pred.device.index)
     done = {}
     for b in frames:
         b = int(b)
         if not 0 <= b < B:
             raise RuntimeError("rerun_frames: frame %d outside the batch of %d" % (b, B))
-        p = eng.make_params(E, H, W, N, 0, 0, batch_out["focals"][b], s["pp_x"], s["pp_y"], s["threshold"], s["inlier_alpha"],
+        if shapes is not None:
+            H, W = shapes[b]
+            maps, pp_x, pp_y = pred[b, :3 * E * H * W].view(E, 3, H, W), s["pp_x"][b], s["pp_y"][b]
+        else:
+            (H, W), maps, pp_x, pp_y = pred.shape[3:], pred[b], s["pp_x"], s["pp_y"]
+        p = eng.make_params(E, H, W, N, 0, 0, batch_out["focals"][b], pp_x, pp_y, s["threshold"], s["inlier_alpha"],
                             s["inlier_beta"], s["max_reprojection"], s["subsample"], seed=batch_out["seed"], call=batch_out["call"] + b,
                             max_tries=s["max_tries"], max_ref_steps=s["max_ref_steps"], refine_solo=True,
                             strict_reference=s["strict_reference"])
-        rec = eng.forward_device(pred[b], e_hyps[b], p)
+        rec = eng.forward_device(maps, e_hyps[b], p)
         pose = rec[api.RES_POSE:api.RES_POSE + 16].astype(np.float32).reshape(4, 4)
         row = None
         if batch_out.get("gt_poses") is not None:
@@ -300,9 +375,10 @@ def evaluate(samples, gating, experts, trans_threshold_cm=5.0, rot_threshold_deg
              asynchronous=False, **kw):
     """The statistics block of test_esac.py:249-289 over `samples` = iterable of
     (name, image, focal_length, gt_pose [4,4], gt_expert).
-    batch_size > 1: consecutive samples whose images have one shape are stacked, up to batch_size of them (a batch is cut where
-    the shape changes; the last one may be short), and each batch goes through `localize_batch` -- one forward batch and one
-    on-device evaluation instead of batch_size blocking calls with their copies.  The eval rows of all batches are copied to the
+    batch_size > 1: batch_size consecutive samples form a batch (the last one may be short) and each batch goes through
+    `localize_batch` -- one forward batch and one on-device evaluation instead of batch_size blocking calls with their copies.
+    Images of one size are stacked; a batch whose images differ in size is a ragged batch (the networks run per group of equal
+    size, the solver once: esac.forward_batch_async(shapes=...)).  The eval rows of all batches are copied to the
     host ONCE, after the last batch; frames whose status is 3 are run again (`rerun_frames`); the statistics and the pose-log lines
     (the format string of `pose_file_line` over the row's quaternion and translation) follow from the rows.  asynchronous: the
     batches are enqueued without a host synchronisation (localize_batch(asynchronous=True, all_experts=True)), given device images.
@@ -338,7 +414,9 @@ def _evaluate_batched(samples, gating, experts, trans_threshold_cm, rot_threshol
     batches, names, gt_exp = [], [], []  # per batch: its localize_batch result; per image: name and true expert
 
     def run(group):
-        images = torch.cat([g[1] for g in group])
+        # one size: the stacked batch, as ever; several: a ragged batch (the list form of localize_batch)
+        one_size = all(tuple(g[1].shape) == tuple(group[0][1].shape) for g in group)
+        images = torch.cat([g[1] for g in group]) if one_size else [g[1] for g in group]
         gts = np.stack([np.asarray(g[3].detach().cpu() if isinstance(g[3], torch.Tensor) else g[3], np.float32) for g in group])
         out = localize_batch(images, gating, experts, [float(g[2]) for g in group], gt_poses=gts,
                              gt_experts=[int(g[4]) for g in group], asynchronous=asynchronous,
@@ -350,7 +428,7 @@ def _evaluate_batched(samples, gating, experts, trans_threshold_cm, rot_threshol
 
     group = []
     for sample in samples:
-        if group and (len(group) == batch_size or tuple(sample[1].shape) != tuple(group[0][1].shape)):
+        if group and len(group) == batch_size:
             run(group)
             group = []
         group.append(sample)

@@ -69,11 +69,12 @@ typedef struct esac_hip_params {
 
 /* One frame's camera in a batch whose frames differ in shift, focal length or principal point (esac_hip_forward_batch_cams,
  * esac_hip_backward_batch_cams): the five per-image values of esac_hip_params, padded to 32 bytes (one aligned record per frame
- * on the device).  The padding is ignored. */
+ * on the device).  The padding is ignored by the _cams entry points (it may hold anything); esac_hip_forward_batch_shapes reads
+ * the frame's grid from it. */
 typedef struct esac_hip_frame_cam {
     int32_t shift_x, shift_y; /* esac.cpp:67-68: the image's random shift (training) or 0 */
     float focal, ppx, ppy;    /* esac.cpp:69-71 */
-    int32_t reserved[3];
+    int32_t reserved[3];      /* esac_hip_forward_batch_shapes: [0] rows h, [1] columns w of the frame's grid; [2] ignored */
 } esac_hip_frame_cam;
 
 /* esac_hip_forward / _batch: score EVERY hypothesis in the reference's mixed float/double arithmetic
@@ -282,6 +283,29 @@ int esac_hip_forward_batch(esac_hip_ctx* ctx, int B, const float* d_scene_coords
 int esac_hip_forward_batch_cams(esac_hip_ctx* ctx, int B, const float* d_scene_coords, int64_t sc_frame_stride,
                                 const int64_t* d_hyp_assign, const esac_hip_params* p, const esac_hip_frame_cam* h_cams,
                                 void* stream, double* d_scores_out, double* d_result_out, double* h_result_out);
+
+/*
+ * A RAGGED batch: esac_hip_forward_batch_cams whose frames also differ in image size (test sets resized by the shorter edge:
+ * grids such as 60x80, 80x60 and 60x90 side by side).  Frame b's grid is h_cams[b].reserved[0] rows x reserved[1] columns
+ * (reserved[2] is ignored); h_cams is required.  Additive: the ABI version stays.
+ *   layout    frame b's maps lie DENSE as [E,3,h_b,w_b] floats at d_scene_coords + b * sc_frame_stride -- no row strides; the
+ *             rest of the slot is never read.  sc_frame_stride >= 3 * E * h_b * w_b for every frame, and a multiple of 4
+ *             floats (the 16-byte loads of the score and refinement kernels).
+ *   capacity  p->H * p->W is the number of cells every per-frame buffer and every launch is sized for: h_b * w_b <= p->H * p->W.
+ *             Only the product matters (60x80 and 80x60 share a capacity of 4800); p->H x p->W must itself be a legal grid.
+ *   contract  frame b is esac_hip_forward on that frame alone: its own [E,3,h_b,w_b] maps, h_cams[b]'s camera, call p->call + b,
+ *             and the re-score margin of ITS grid (p->rescore_margin, or the default for h_b * w_b cells) -- discrete outputs
+ *             and ESAC_RES_CONTENDERS identical, scores and poses as described for esac_hip_forward_batch.
+ *   checks    every frame passes a single call's grid rule (at least 3x3, (h-1)(w-1) >= 4, at most 65535 rows / columns), fits
+ *             the capacity and its slot, and its camera fits ITS pixel range; the error (-4) names the first offending frame.
+ *   read-back esac_hip_read keeps the capacity stride: after the call, frame b's per-cell data is the first h_b * w_b entries
+ *             of its slot of p->H * p->W (ESAC_BUF_INLIER_MAP, frame 0's: p->H * p->W bytes whose first h_0 * w_0 are the map).
+ * A table whose shapes all equal p->H x p->W computes what esac_hip_forward_batch_cams computes, bit for bit.  B == 1 is the
+ * single call on h_cams[0]'s grid.  h_result_out == NULL is the asynchronous form.  The training calls have no such form yet.
+ */
+int esac_hip_forward_batch_shapes(esac_hip_ctx* ctx, int B, const float* d_scene_coords, int64_t sc_frame_stride,
+                                  const int64_t* d_hyp_assign, const esac_hip_params* p, const esac_hip_frame_cam* h_cams,
+                                  void* stream, double* d_scores_out, double* d_result_out, double* h_result_out);
 
 /*
  * Multi-GPU exchange (new; the reference has no multi-device path): d_records = `world` result records of
