@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "esac_hip_eval_batch",  # additive too
     "esac_hip_set_bwd_pose_records",  # additive too
     "esac_hip_forward_batch_shapes",  # additive too
+    "esac_hip_backward_batch_shapes", "esac_hip_backward_batch_dev_shapes",  # additive too
 ]
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
@@ -194,6 +195,24 @@ def pack_frames(maps, device=None):
     return packed, shapes
 
 
+def unpack_frames(packed, shapes, E):
+    """The inverse of `pack_frames`: the list of B [E,3,h_b,w_b] VIEWS of a packed [B,S] tensor (no copy: writing a view writes
+    the packed row) -- the maps of a packed batch, or the gradients `backward_batch_shapes` accumulated into a packed
+    tensor, handed back to autograd per frame.  Raises RuntimeError naming the argument; touches no device."""
+    who = "esac.unpack_frames"
+    if not isinstance(packed, torch.Tensor) or packed.dim() != 2:
+        raise RuntimeError("%s: packed must be a [B,S] tensor, found %s"
+                           % (who, list(packed.shape) if isinstance(packed, torch.Tensor) else type(packed).__name__))
+    if not isinstance(E, int) or isinstance(E, bool) or E < 1:
+        raise RuntimeError("%s: E must be a positive int, found %r" % (who, E))
+    shapes = _shapes_arg(who, shapes, int(packed.size(0)))
+    S = int(packed.size(1))
+    if 3 * E * max(h * w for h, w in shapes) > S:
+        raise RuntimeError("%s: packed [B,%d] is too short for E = %d expert(s) on the largest grid of shapes (%d cells)"
+                           % (who, S, E, max(h * w for h, w in shapes)))
+    return [packed[b, :3 * E * h * w].view(E, 3, h, w) for b, (h, w) in enumerate(shapes)]
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -230,6 +249,8 @@ def load_library():
                                                      C.c_float, pp, vp, vp]
         lib.esac_hip_backward_batch_dev.argtypes = [vp, i32, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_float, C.c_float,
                                                     C.c_float, pp, vp, vp]
+        lib.esac_hip_backward_batch_shapes.argtypes = lib.esac_hip_backward_batch_cams.argtypes
+        lib.esac_hip_backward_batch_dev_shapes.argtypes = lib.esac_hip_backward_batch_dev.argtypes
         lib.esac_hip_eval_batch.argtypes = [vp, i32, vp, vp, vp, C.c_float, C.c_float, vp, vp]
         lib.esac_hip_set_bwd_pose_records.argtypes = [vp, vp, i32]
         lib.esac_hip_read.argtypes = [vp, i32, vp, C.c_size_t]
@@ -494,6 +515,28 @@ class Engine:
             raise RuntimeError("%s: the gradient tensor must be a dense float32 device tensor [B,E,3,H,W]" % who)
         return sc, ha, B, int(sc.stride(0)) if sc.dim() == 5 else 0
 
+    def _ragged_batch_inputs(self, who, scene_coords, out_gradients, hyp_assign, params, cams, shapes):
+        """The device inputs of a ragged training batch: the packed maps and the packed gradients (both [B,S'] float32 on this
+        device, rows contiguous; frame b dense at the head of row b) and the camera table with every frame's grid in it."""
+        sc = scene_coords if scene_coords.is_cuda else scene_coords.to(self.device, non_blocking=True)
+        ha = hyp_assign if hyp_assign.is_cuda else hyp_assign.to(self.device, non_blocking=True)
+        sc, ha = sc.contiguous(), ha.contiguous()
+        B = int(ha.shape[0])
+        shapes = _shapes_arg(who, shapes, B)
+        if sc.dim() != 2 or sc.shape[0] != B:
+            raise RuntimeError("%s: with shapes, scene_coords must be the packed [B,S] tensor (pack_frames), found %s" % (who, list(sc.shape)))
+        g = out_gradients
+        if not (isinstance(g, torch.Tensor) and g.is_cuda and g.device == self.device and g.dtype == torch.float32 and g.dim() == 2
+                and g.shape[0] == B and g.is_contiguous() and g.shape[1] >= 3 * params.E * max(h * w for h, w in shapes)):
+            raise RuntimeError("%s: with shapes, the gradient tensor must be a packed float32 [B,S] tensor on this device, contiguous, "
+                               "S >= 3*E*max(h*w)" % who)
+        if cams is None:
+            cams = make_cams([params.shift_x] * B, [params.shift_y] * B, [params.focal] * B, [params.ppx] * B, [params.ppy] * B)
+        else:
+            cams = _cams_arg(cams, B, who).copy()  # (the caller's table keeps its padding)
+        cams["reserved"][:, :2] = np.asarray(shapes, np.int32)
+        return sc, ha, B, cams
+
     def backward_batch(self, scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, cams=None,
                        pose_records=None):
         """Training path over B frames in one set of launches (esac_hip_backward_batch). scene_coords [B,E,3,H,W] (or [E,3,H,W]
@@ -502,17 +545,40 @@ class Engine:
         An out-of-range device assignment raises after every frame has run; the exception's `records` holds the [B,4] records.
         cams: None or B per-frame camera records (make_cams), as in forward_batch (esac_hip_backward_batch_cams).
         pose_records: None, or a float64 tensor [B,32] (this device, contiguous; or CPU) filled in place: row b = the
-        forward-format record of frame b's argmax hypothesis, as backward_device's pose_record."""
+        forward-format record of frame b's argmax hypothesis, as backward_device's pose_record.
+        Frames that differ in image size: backward_batch_shapes."""
+        return self._backward_batch(scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, cams, pose_records, None)
+
+    def backward_batch_shapes(self, scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, shapes, cams=None,
+                              pose_records=None):
+        """backward_batch over a RAGGED batch (esac_hip_backward_batch_shapes): shapes = B (h, w) pairs, scene_coords the packed
+        [B,S] tensor of pack_frames, out_gradients a packed float32 [B,S'] tensor of the same row layout on this device (frame b's
+        [E,3,h_b,w_b] gradients dense at the head of row b: unpack_frames), params.H * params.W the capacity in cells
+        (capacity_shape).  Everything else, and the return value, as backward_batch.  (A method of its own: the parameter lists
+        of backward_batch and backward_batch_async are held as they are.)"""
+        return self._backward_batch(scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, cams, pose_records,
+                                    _shapes_arg("esac.backward_batch_shapes", shapes, int(hyp_assign.shape[0])))
+
+    def _backward_batch(self, scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, cams, pose_records, shapes):
         pose_records = self._take_pose_arm(pose_records)
-        sc, ha, B, sc_stride = self._batch_inputs("esac.backward_batch", scene_coords, out_gradients, hyp_assign)
+        if shapes is not None:
+            sc, ha, B, cams = self._ragged_batch_inputs("esac.backward_batch_shapes", scene_coords, out_gradients, hyp_assign, params, cams, shapes)
+            sc_stride = int(sc.stride(0))
+        else:
+            sc, ha, B, sc_stride = self._batch_inputs("esac.backward_batch", scene_coords, out_gradients, hyp_assign)
         gt = np.ascontiguousarray(np.asarray(gt_poses, np.float32).reshape(-1))
         if gt.size != 16 * B:
             raise RuntimeError("esac.backward_batch: gtPoses must hold B 4x4 poses")
         host = np.zeros((B, 4), np.float64)
-        if cams is not None:
+        if cams is not None and shapes is None:
             cams = _cams_arg(cams, B, "esac.backward_batch")
         rec_dev = self._arm_pose_records("esac.backward_batch", "poseRecords", pose_records, B, False) if pose_records is not None else None
-        if cams is None:
+        if shapes is not None:
+            rc = self.lib.esac_hip_backward_batch_shapes(
+                self.ctx, B, sc.data_ptr(), sc_stride, out_gradients.data_ptr(), int(out_gradients.stride(0)), ha.data_ptr(),
+                gt.ctypes.data, cams.ctypes.data, float(w_rot), float(w_trans), float(loss_cut), C.byref(params), self._stream(),
+                host.ctypes.data)
+        elif cams is None:
             rc = self.lib.esac_hip_backward_batch(
                 self.ctx, B, sc.data_ptr(), sc_stride, out_gradients.data_ptr(), int(out_gradients.stride(0)), ha.data_ptr(),
                 gt.ctypes.data, float(w_rot), float(w_trans), float(loss_cut), C.byref(params), self._stream(), host.ctypes.data)
@@ -540,9 +606,24 @@ class Engine:
         cams: None or B per-frame camera records (make_cams), copied before the call returns.
         Pose records: arm_pose_records(t) before the call, t a contiguous float64 tensor [B,32] on this device, written in
         stream order: row b = the forward-format record of frame b's argmax hypothesis (RES_VALID 0 and a NaN pose for a frame
-        that selected nothing, a singular ground truth among them); eval_batch may be enqueued right behind the call."""
+        that selected nothing, a singular ground truth among them); eval_batch may be enqueued right behind the call.
+        Frames that differ in image size: backward_batch_shapes_async."""
+        return self._backward_batch_async(scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, cams, out, None)
+
+    def backward_batch_shapes_async(self, scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, shapes,
+                                    cams=None, out=None):
+        """backward_batch_async over a RAGGED batch (esac_hip_backward_batch_dev_shapes): shapes and the packed tensors as in
+        backward_batch_shapes, everything else as backward_batch_async."""
+        return self._backward_batch_async(scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, cams, out,
+                                          _shapes_arg("esac.backward_batch_shapes_async", shapes, int(hyp_assign.shape[0])))
+
+    def _backward_batch_async(self, scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, cams, out, shapes):
         pose_records = self._take_pose_arm(None)
-        sc, ha, B, sc_stride = self._batch_inputs("esac.backward_batch_async", scene_coords, out_gradients, hyp_assign)
+        if shapes is not None:
+            sc, ha, B, ragged_cams = self._ragged_batch_inputs("esac.backward_batch_shapes_async", scene_coords, out_gradients, hyp_assign, params, cams, shapes)
+            sc_stride = int(sc.stride(0))
+        else:
+            sc, ha, B, sc_stride = self._batch_inputs("esac.backward_batch_async", scene_coords, out_gradients, hyp_assign)
         if pose_records is not None:
             _check_pose_records("esac.backward_batch_async", "poseRecords", pose_records, B, True, self.device)
         if isinstance(gt_poses, torch.Tensor) and gt_poses.is_cuda:
@@ -563,11 +644,13 @@ class Engine:
         elif not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (B, 4)):
             raise RuntimeError("esac.backward_batch_async: out must be a dense float64 device tensor [B,4]")
         table = None
-        if cams is not None:
+        if shapes is not None:
+            table = ragged_cams
+        elif cams is not None:
             table = _cams_arg(cams, B, "esac.backward_batch_async")
         if pose_records is not None:
             self._arm_pose_records("esac.backward_batch_async", "poseRecords", pose_records, B, True)
-        rc = self.lib.esac_hip_backward_batch_dev(
+        rc = (self.lib.esac_hip_backward_batch_dev_shapes if shapes is not None else self.lib.esac_hip_backward_batch_dev)(
             self.ctx, B, sc.data_ptr(), sc_stride, out_gradients.data_ptr(), int(out_gradients.stride(0)), ha.data_ptr(),
             gt.data_ptr(), table.ctypes.data if table is not None else None, float(w_rot), float(w_trans), float(loss_cut),
             C.byref(params), self._stream(), out.data_ptr())
@@ -668,17 +751,24 @@ class Engine:
         assert h.ndim == 2 and h.shape[1] == 6
         _check(self.lib.esac_hip_write_hyps(self.ctx, h.ctypes.data_as(C.c_void_p), h.shape[0]), self.lib)
 
-    def read_slabs(self, which, k):
-        """Gradient slabs [k,3,H,W] (float64) of the first k slots of the last backward call (BUF_BWD_PATH1 / _PATH2)."""
+    def read_slabs(self, which, k, shape=None):
+        """Gradient slabs [k,3,H,W] (float64) of the first k slots of the last backward call (BUF_BWD_PATH1 / _PATH2).
+        shape: after a ragged batch (backward_batch_shapes), the (h, w) of frame 0 of its last chunk -- that frame's slots
+        lie at its own h*w, and the slabs come back as [k,3,h,w]."""
         _, H, W = self._shape
+        if shape is not None:
+            H, W = int(shape[0]), int(shape[1])
         out = np.zeros((int(k), 3, H, W), np.float64)
         _check(self.lib.esac_hip_read(self.ctx, which, out.ctypes.data_as(C.c_void_p), out.nbytes), self.lib)
         return out
 
-    def read_maps(self, k):
+    def read_maps(self, k, shape=None):
         """Both inlier-map buffers [k,2,H*W] (uint8, cells as y * W + x) of the first k slots of the last blocking backward call
-        (BUF_BWD_MAPS); BUF_BWD_SLOT_INFO[s][0] names the one holding slot s's last accepted inlier set (-1: neither)."""
+        (BUF_BWD_MAPS); BUF_BWD_SLOT_INFO[s][0] names the one holding slot s's last accepted inlier set (-1: neither).
+        shape: after a ragged batch, frame 0's own (h, w), as in read_slabs."""
         _, H, W = self._shape
+        if shape is not None:
+            H, W = int(shape[0]), int(shape[1])
         out = np.zeros((int(k), 2, H * W), np.uint8)
         _check(self.lib.esac_hip_read(self.ctx, BUF_BWD_MAPS, out.ctypes.data_as(C.c_void_p), out.nbytes), self.lib)
         return out
@@ -1251,6 +1341,135 @@ def _check_batch_tensors(who, sceneCoordinates, outGradients, hypAssignment, gtP
     return B, N, E, H, W
 
 
+def _ragged_backward_args(who, sceneCoordinates, outGradients, hypAssignment, gtPoses, shapes, experts, packed_only):
+    """The checks of a ragged training batch's tensors before any device is touched and before the call counter moves.
+    outGradients: a packed float32 [B,S'] tensor of pack_frames' row layout, or (blocking call only) a list of B float32
+    [E,3,h_b,w_b] tensors.  Returns (B, N, E, shapes); RuntimeError naming the argument otherwise."""
+    if not isinstance(hypAssignment, torch.Tensor) or hypAssignment.dtype != torch.int64 or hypAssignment.dim() != 2 or hypAssignment.numel() == 0:
+        raise RuntimeError("%s: hypAssignment must be a non-empty int64 [B,N]" % who)
+    B, N = hypAssignment.shape
+    if B > MAX_BATCH:
+        raise RuntimeError("%s: hypAssignment holds %d frames, at most %d per call" % (who, B, MAX_BATCH))
+    E, shapes = _ragged_args(who, sceneCoordinates, B, shapes, experts)
+    if packed_only and not isinstance(sceneCoordinates, torch.Tensor):
+        raise RuntimeError("%s: with shapes, sceneCoordinates must be the packed device tensor of pack_frames (an asynchronous call "
+                           "stages nothing)" % who)
+    if not isinstance(gtPoses, torch.Tensor) or gtPoses.dtype != torch.float32 or tuple(gtPoses.shape) != (B, 4, 4):
+        raise RuntimeError("%s: gtPoses must be float32 [B,4,4]" % who)
+    need = 3 * E * max(h * w for h, w in shapes)
+    if isinstance(outGradients, (list, tuple)):
+        if packed_only:
+            raise RuntimeError("%s: with shapes, outGradients must be the packed float32 [B,S] device tensor (an asynchronous call "
+                               "cannot copy back into a list)" % who)
+        if len(outGradients) != B:
+            raise RuntimeError("%s: outGradients holds %d frames, hypAssignment %d" % (who, len(outGradients), B))
+        for b, g in enumerate(outGradients):
+            if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or tuple(g.shape) != (E, 3) + shapes[b]:
+                raise RuntimeError("%s: outGradients[%d] must be float32 %s" % (who, b, [E, 3] + list(shapes[b])))
+    else:
+        if not isinstance(outGradients, torch.Tensor) or outGradients.dtype != torch.float32 or outGradients.dim() != 2:
+            raise RuntimeError("%s: with shapes, outGradients must be a packed float32 [B,S] tensor%s" %
+                               (who, "" if packed_only else " or a list of B float32 [E,3,h,w] tensors"))
+        if outGradients.size(0) != B:
+            raise RuntimeError("%s: batch sizes of outGradients and hypAssignment differ" % who)
+        if outGradients.size(1) < need:
+            raise RuntimeError("%s: outGradients [B,%d] is too short for %d expert(s) on the largest grid of shapes (3*E*h*w = %d)"
+                               % (who, outGradients.size(1), E, need))
+    return int(B), int(N), E, shapes
+
+
+def _ragged_backward_params(eng, E, shapes, N, cam_scalars, score_args):
+    H, W = capacity_shape(shapes)
+    return eng.make_params(E, H, W, N, *cam_scalars, *score_args, seed=_state["seed"], call=_state["call"],
+                           max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"],
+                           strict_training=_state["strict_training"])
+
+
+def _ragged_backward_batch(who, sceneCoordinates, outGradients, hypAssignment, gtPoses, loss_args, cam_args, score_args, shapes,
+                           experts, poseRecords):
+    B, N, E, shapes = _ragged_backward_args(who, sceneCoordinates, outGradients, hypAssignment, gtPoses, shapes, experts, False)
+    some = sceneCoordinates[0] if isinstance(sceneCoordinates, (list, tuple)) else sceneCoordinates
+    if poseRecords is not None:
+        _check_pose_records(who, "poseRecords", poseRecords, B, False, some.device if some.is_cuda else None)
+    if not hypAssignment.is_cuda:
+        lo, hi = int(hypAssignment.min()), int(hypAssignment.max())
+        if lo < 0 or hi >= E:
+            raise RuntimeError("%s: hypAssignment values must lie in [0,%d), found [%d,%d]" % (who, E, lo, hi))
+    cam_scalars, cams = _per_frame_cams(who, B, *cam_args)
+    if isinstance(sceneCoordinates, (list, tuple)):
+        on_dev = [m.device.index for m in sceneCoordinates if m.is_cuda]
+        eng = engine(on_dev[0] if on_dev else None)
+        packed, _ = pack_frames(sceneCoordinates, device=eng.device)
+    else:
+        eng = engine(sceneCoordinates.device.index if sceneCoordinates.is_cuda else None)
+        packed = sceneCoordinates
+    p = _ragged_backward_params(eng, E, shapes, N, cam_scalars, score_args)
+    as_list = isinstance(outGradients, (list, tuple))
+    if as_list:
+        grads, _ = pack_frames(list(outGradients), device=eng.device)
+    else:
+        in_place = outGradients.is_cuda and outGradients.is_contiguous() and outGradients.device == eng.device
+        grads = outGradients if in_place else outGradients.to(eng.device).contiguous()
+    out = eng.backward_batch_shapes(packed, grads, hypAssignment, gtPoses.detach().cpu().numpy(), *loss_args, p, shapes, cams=cams,
+                                    pose_records=poseRecords)
+    _state["call"] += B  # (behind the call: a table the library refuses draws no RNG stream)
+    if as_list:
+        for g, v in zip(outGradients, unpack_frames(grads, shapes, E)):
+            g.copy_(v)  # the accumulated tensors back into the caller's
+    elif grads is not outGradients:
+        outGradients.copy_(grads)
+    _state["last"] = {"backward": out}
+    return [float(v) for v in out[:, 0]]
+
+
+def backward_batch_shapes(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLossRot, wLossTrans, lossCut, shiftX, shiftY,
+                          focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling, *, shapes,
+                          experts=None, poseRecords=None):
+    """`backward_batch` over a RAGGED batch -- frames that differ in image size (esac_hip_backward_batch_shapes).  shapes (keyword
+    only, required): B (h, w) pairs.  sceneCoordinates is the packed [B,S] tensor of `pack_frames` or a list of B float32
+    [E,3,h_b,w_b] maps; outGradients a packed float32 [B,S'] tensor of the same row layout (frame b's gradients dense at the head of
+    row b: `unpack_frames`), or a list of B float32 [E,3,h_b,w_b] tensors, accumulated into and copied back.  Frame b is `backward`
+    on its own maps with counter call + b.  experts: the E of a packed tensor, as in forward_batch.  Everything else, and the
+    return value, as `backward_batch`; the call counter advances by B behind the call (a refused table draws no RNG stream).
+    A function of its own, like the C entry point: the parameter lists of `backward_batch` and `backward_batch_async` stay as they are."""
+    poseRecords = _take_pose_records(poseRecords)
+    _no_strict_training("esac.backward_batch_shapes")
+    return _ragged_backward_batch("esac.backward_batch_shapes", sceneCoordinates, outGradients, hypAssignment, gtPoses,
+                                  (wLossRot, wLossTrans, lossCut), (shiftX, shiftY, focalLength, ppointX, ppointY),
+                                  (inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling), shapes, experts, poseRecords)
+
+
+def backward_batch_shapes_async(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLossRot, wLossTrans, lossCut, shiftX, shiftY,
+                                focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling, *, shapes,
+                                experts=None, poseRecords=None):
+    """`backward_batch_async` over a RAGGED batch (esac_hip_backward_batch_dev_shapes): shapes and experts as in
+    `backward_batch_shapes`; sceneCoordinates and outGradients are the packed DEVICE tensors (no lists: nothing is staged or copied
+    back).  Everything else, and the return value, as `backward_batch_async`."""
+    who = "esac.backward_batch_shapes_async"
+    poseRecords = _take_pose_records(poseRecords)
+    _no_strict_training(who)
+    B, N, E, shapes = _ragged_backward_args(who, sceneCoordinates, outGradients, hypAssignment, gtPoses, shapes, experts, True)
+    if poseRecords is not None:
+        _check_pose_records(who, "poseRecords", poseRecords, B, True, sceneCoordinates.device if sceneCoordinates.is_cuda else None)
+    cam_scalars, cams = _per_frame_cams(who, B, shiftX, shiftY, focalLength, ppointX, ppointY)
+    if not outGradients.is_contiguous():
+        raise RuntimeError("%s: outGradients must be contiguous (an asynchronous call cannot copy back into strided storage)" % who)
+    for name, t in (("outGradients", outGradients), ("sceneCoordinates", sceneCoordinates), ("hypAssignment", hypAssignment)):
+        if not t.is_cuda:
+            raise RuntimeError("%s: %s must be a device tensor (an asynchronous call stages nothing on the host)" % (who, name))
+    if outGradients.device != sceneCoordinates.device or hypAssignment.device != sceneCoordinates.device or \
+            (gtPoses.is_cuda and gtPoses.device != sceneCoordinates.device):
+        raise RuntimeError("%s: sceneCoordinates, outGradients, hypAssignment and a device gtPoses must live on one device" % who)
+    eng = engine(sceneCoordinates.device.index)
+    p = _ragged_backward_params(eng, E, shapes, N, cam_scalars, (inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling))
+    eng.arm_pose_records(poseRecords)
+    rec = eng.backward_batch_shapes_async(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLossRot, wLossTrans, lossCut, p, shapes,
+                                          cams=cams)
+    _state["call"] += B  # (behind the call: a refused table draws no RNG stream)
+    _state["last"] = {"backward": rec}
+    return rec[:, 0]
+
+
 def backward_batch(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLossRot, wLossTrans, lossCut, shiftX, shiftY,
                    focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling, *, poseRecords=None):
     """Batched companion of `backward` (new API): sceneCoordinates [B,E,3,H,W] (or [E,3,H,W] shared by all frames),
@@ -1261,7 +1480,8 @@ def backward_batch(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLoss
     Each of shiftX, shiftY, focalLength, ppointX, ppointY is a scalar (the whole batch) or a length-B sequence / 1-D tensor /
     numpy array: frame b uses element b (a training mini-batch: one random shift and one focal length per image).
     poseRecords (keyword only; or `set_pose_records` before the call): a float64 tensor [B,32], CPU or device, filled in place:
-    row b is frame b's record as `backward` describes it."""
+    row b is frame b's record as `backward` describes it.
+    Frames that differ in image size: `backward_batch_shapes`."""
     poseRecords = _take_pose_records(poseRecords)
     _no_strict_training("esac.backward_batch")
     B, N, E, H, W = _check_batch_tensors("esac.backward_batch", sceneCoordinates, outGradients, hypAssignment, gtPoses, name_each=False)
@@ -1303,7 +1523,8 @@ def backward_batch_async(sceneCoordinates, outGradients, hypAssignment, gtPoses,
     Advances the call counter by B.  The camera arguments are host values, as in backward_batch.
     poseRecords (keyword only; or `set_pose_records` before the call): a contiguous DEVICE float64 tensor [B,32], written in
     stream order: row b is frame b's record as `backward` describes it (RES_VALID 0 for a frame with a singular ground truth);
-    `eval_batch` may be enqueued right behind the call."""
+    `eval_batch` may be enqueued right behind the call.
+    Frames that differ in image size: `backward_batch_shapes_async`."""
     who = "esac.backward_batch_async"
     poseRecords = _take_pose_records(poseRecords)
     _no_strict_training(who)

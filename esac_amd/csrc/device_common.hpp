@@ -247,8 +247,11 @@ __device__ __forceinline__ void frame_view(KArgs& a) { frame_view(a, (int)blockI
 
 // The training path's buffers of frame fr of a batched call (esac_hip_backward_batch): per-hypothesis arrays are [B,N],
 // the slot workspace [B,cap] slots, the small per-slot tables [B,bwd_rows(N)], the record [B,4], the gradient tensor of
-// frame fr at out_grad + fr * grad_frame_stride.  Used together with frame_view (the sampler's and the scores' slices).
-__device__ __forceinline__ void bwd_frame_view(KArgs& a, int fr) {
+// frame fr at out_grad + fr * grad_frame_stride.  Every stride comes from the inline shape -- the CAPACITY of a ragged batch -- so
+// this runs BEFORE frame_view puts the frame's own grid there: the kernels call train_frame_view, never the two by themselves.
+// Inside a frame's region a ragged frame's slot k lies at the frame's OWN p = h*w (maps + k*2*p, slabs + k*3*p, list
+// k*corr_entries(p)): what the kernels' P = a.H * a.W indexing gives behind the view, and always below the capacity's.
+__device__ __forceinline__ void bwd_frame_strides(KArgs& a, int fr) {
     if (fr == 0) return;
     const size_t N = (size_t)a.N, P = (size_t)a.H * a.W, f = (size_t)fr, cap = (size_t)a.bwd.cap, rows = (size_t)bwd_rows(a.N);
     a.bwd.sel += f * N;
@@ -265,6 +268,12 @@ __device__ __forceinline__ void bwd_frame_view(KArgs& a, int fr) {
     a.bwd.grad2 += f * cap * 3 * P;
     a.bwd.out += f * 4;
     a.bwd.out_grad += f * (size_t)a.bwd.grad_frame_stride;
+}
+// the view of frame fr in a training kernel: the training buffers' strides from the capacity, then the forward view, whose one
+// shape site (frame_shape) replaces H, W and margin last
+__device__ __forceinline__ void train_frame_view(KArgs& a, int fr) {
+    bwd_frame_strides(a, fr);
+    frame_view(a, fr);
 }
 // ground truth of frame fr into registers (the inline fields on a single call)
 __device__ __forceinline__ void bwd_load_gt(const KArgs& a, int fr, double (&gt)[16], double (&gt_pose)[6]) {

@@ -47,8 +47,7 @@ __global__ __launch_bounds__(B) void k_bwd_select(KArgs a) {
     __shared__ int s_wcount[B / 64];
     __shared__ int s_base;
     if (BATCH) {
-        frame_view(a);
-        bwd_frame_view(a, (int)blockIdx.y);
+        train_frame_view(a, (int)blockIdx.y);
     }
     // a batch: does this frame's assignment row hold a value outside [0,E)?  (the sampler's status word is shared by the frames;
     // the same test as flag_bad_assignment: one expert never reads the row)
@@ -138,8 +137,7 @@ __global__ __launch_bounds__(B) void k_bwd_loss(KArgs a) {
     __shared__ double s_tot[1];
     double gt[16], gt_pose[6];
     if (BATCH) {
-        frame_view(a);
-        bwd_frame_view(a, (int)blockIdx.y);
+        train_frame_view(a, (int)blockIdx.y);
         bwd_load_gt(a, (int)blockIdx.y, gt, gt_pose);
     } else {
 #pragma unroll
@@ -232,8 +230,7 @@ __global__ __launch_bounds__(B) void k_bwd_pose_record(KArgs a) {
     // (both indexed by the frame of the launch, not moved by the frame's view)
     double* const rec = a.bwd.pose_rec + (size_t)blockIdx.y * BWD_REC_DOUBLES;
     const bool dead = a.bwd.frame_status && a.bwd.frame_status[blockIdx.y] == 2;  // singular ground truth: k_bwd_loss reports entropy 0
-    frame_view(a);
-    bwd_frame_view(a, (int)blockIdx.y);
+    train_frame_view(a, (int)blockIdx.y);
     double bs = -INFINITY;
     int bi = BEST_NONE, bg = BEST_NONE;
     for (int h = threadIdx.x; h < a.N; h += B) best_take(bs, bi, bg, a.scores[h], h, global_hyp(a, h));
@@ -507,8 +504,7 @@ __global__ __launch_bounds__(B) void k_bwd_paths(KArgs a) {
     __shared__ double s_sol[18][6];
     __shared__ double s_J[72];
     __shared__ int s_bad;
-    frame_view(a);  // (a batch: grid (2 slots, frames))
-    bwd_frame_view(a, (int)blockIdx.y);
+    train_frame_view(a, (int)blockIdx.y);  // (a batch: grid (2 slots, frames))
     const int slots = (int)gridDim.x >> 1;
     if ((int)blockIdx.x < slots) bwd_path1<B, STRICT>(a, (int)blockIdx.x, s_part, s_tot, s_max);
     else                         bwd_path2<B, STRICT>(a, (int)blockIdx.x - slots, s_part, s_tot, s_sol, s_J, s_bad);
@@ -526,11 +522,12 @@ __device__ __forceinline__ void bwd_accumulate_body(const KArgs& a) {
     __shared__ int s_slot[ESAC_BWD_SLOTS_K];
     __shared__ double s_prob[ESAC_BWD_SLOTS_K];
     __shared__ int s_count;
-    const int P = a.H * a.W;
     const int e = blockIdx.y;
     KArgs f = a;  // frame blockIdx.z of a batch (grid (tiles, experts, frames)); `a` keeps the batch's record and pinned slots
-    frame_view(f, (int)blockIdx.z);
-    bwd_frame_view(f, (int)blockIdx.z);
+    train_frame_view(f, (int)blockIdx.z);
+    // the FRAME's cells: its gradients are dense [E,3,h,w] at the head of its slot, its slabs lie at its own 3 h w.  (The grid's
+    // tiles cover the capacity of a ragged batch; `rem < 3 * P` below keeps a smaller frame's workgroups inside its own tensor.)
+    const int P = f.H * f.W;
     const int n_sel = f.bwd.n_sel[0];
     // more slots than the workspace holds: nothing is accumulated, the host grows it and retries.  The slots were refined by
     // teams and one of them timed out (a member never became resident): nothing is accumulated either, the host refines the

@@ -145,6 +145,8 @@ struct esac_hip_ctx {
         long long budget = 2048LL << 20;       // bytes of slot workspace a batch may use (ESAC_BWD_BATCH_BUDGET_MB): beyond it, chunks of frames
         int last_frames = 1;                   // frames whose training-path buffers the workspace holds (the last launch set)
         int last_batch_cap = 0;                // slots per frame of the last launch set when it was a batch's (0: a single call)
+        size_t last_slot_cells = 0;            // a ragged training batch was the most recent call: the cells of its (last chunk's) frame 0, whose
+                                               // slots lie that far apart (esac_hip_read of the slabs and the slot maps); 0 otherwise
         int last_dev_batch = 0;                // B of esac_hip_backward_batch_dev while it is the most recent call on the context (esac_hip_check reads that many words)
     } train;
     struct {  // per-call staging
@@ -160,6 +162,7 @@ struct esac_hip_ctx {
         FrameCam* d_cams = nullptr;            // ... and the table the kernels read (KArgs::cams)
         hipEvent_t cams_ev = nullptr;          // recorded behind the most recent upload: the staging is rewritten only after it
         bool cams_queued = false;
+        bool shapes_next = false;              // esac_hip_backward_batch_dev_shapes: the esac_hip_backward_batch_dev call it makes is a ragged one (one-shot)
     } stage;
     float4* sc4 = nullptr;  // packed copy of the maps for the sampler (ensure_pack_ws), of sc4_cells cells
     long long sc4_cells = 0, tPart = 0;  // tN, tChunks, tPart: what the tile-stationary score workspace holds (ensure_tiled_ws)
@@ -464,6 +467,7 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
     c->last_map1 = (size_t)P;  // (a ragged batch: prepare_forward puts frame 0's own cell count here)
     c->lastB = B;
     c->train.last_dev_batch = 0;  // (esac_hip_backward_batch_dev sets it again once its launches are queued)
+    c->train.last_slot_cells = 0; // (a ragged training batch sets it behind its chunk's arguments)
     *out = a;
     return 0;
 }
@@ -474,14 +478,16 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
 // forward batch may still have its copy queued); the device table is rewritten in stream order behind its last readers.
 // shapes_vec != null: a ragged batch (esac_hip_forward_batch_shapes) -- every record is checked with its own grid (check_shapes),
 // staged with its own re-score margin (shape_record), and *shapes_vec says whether every frame's width is a multiple of 4.
+// bwd_who != null: the table of a ragged TRAINING batch (the entry point's name) -- the gradient slots are checked with it.
 static int stage_cams(esac_hip_ctx* c, const esac_hip_params* p, const esac_hip_frame_cam* h_cams, int B, hipStream_t s,
-                      int64_t sc_frame_stride = 0, bool* shapes_vec = nullptr) {
+                      int64_t sc_frame_stride = 0, bool* shapes_vec = nullptr, const char* bwd_who = nullptr, int64_t grad_frame_stride = 0) {
     static_assert(sizeof(esac_hip_frame_cam) == sizeof(FrameCam) && offsetof(esac_hip_frame_cam, focal) == offsetof(FrameCam, focal) &&
                   offsetof(esac_hip_frame_cam, ppy) == offsetof(FrameCam, ppy), "esac_hip_frame_cam is the device record");
     static_assert(offsetof(esac_hip_frame_cam, reserved) == offsetof(FrameCam, h) && offsetof(FrameCam, w) == offsetof(FrameCam, h) + 4 &&
                   offsetof(FrameCam, margin) == offsetof(FrameCam, h) + 8, "reserved[0..2] = the frame's h, w and margin");
     if (shapes_vec) {
-        if (int rc = check_shapes(p, B, h_cams, sc_frame_stride, shapes_vec)) return rc;
+        if (int rc = bwd_who ? check_bwd_shapes(bwd_who, p, B, h_cams, sc_frame_stride, grad_frame_stride, shapes_vec)
+                             : check_shapes(p, B, h_cams, sc_frame_stride, shapes_vec)) return rc;
     } else {
         for (int b = 0; b < B; b++)
             if (int rc = check_cam(p, h_cams[b].shift_x, h_cams[b].shift_y, h_cams[b].focal, b)) return rc;
@@ -1033,7 +1039,7 @@ extern "C" int esac_hip_forward_batch_shapes(esac_hip_ctx* c, int B, const float
 
 // ---------------------------------------------------------------- training path
 // `cap` = slots (hypotheses with p >= PROB_THRESH) per frame the slab workspace must hold, for B frames (a batch: every buffer
-// frame-major, device_common.hpp:bwd_frame_view); it only ever grows
+// frame-major, device_common.hpp:bwd_frame_strides); it only ever grows
 static int ensure_bws(esac_hip_ctx* c, int N, int P, int cap, int B = 1) {
     const bool lists = P > ESAC_REFINE_LDS_CAP;
     const long long NB = (long long)N * B, slots = (long long)cap * B, rows = (long long)bwd_rows(N) * B;
@@ -1076,12 +1082,36 @@ static int enqueue_bwd_sampling(esac_hip_ctx* c, KArgs& a, hipStream_t s, bool p
 }
 
 // The KArgs of a batch's chunk [b0, b0 + nb): camera record b0 in the inline fields, the call counter, the tensors and the camera
-// table offset by the chunk's first frame (validated, workspaces grown, a fresh epoch: make_args)
-static int chunk_args(esac_hip_ctx* c, const float* d_sc, int64_t sc_frame_stride, const int64_t* d_assign, const esac_hip_params* p, const esac_hip_frame_cam* h_cams, int b0, int nb, KArgs* a) {
+// table offset by the chunk's first frame (validated, workspaces grown, a fresh epoch: make_args).  shapes: KArgs::shapes of a
+// ragged batch (p's H x W is the capacity), decided over the WHOLE table, so that every chunk takes the same refinement kernel
+static int chunk_args(esac_hip_ctx* c, const float* d_sc, int64_t sc_frame_stride, const int64_t* d_assign, const esac_hip_params* p, const esac_hip_frame_cam* h_cams, int b0, int nb, KArgs* a,
+                      int shapes = 0) {
     esac_hip_params pc = h_cams ? with_cam(*p, h_cams[b0]) : *p;
     pc.call = p->call + (uint64_t)b0;
     if (int rc = make_args(c, d_sc + (size_t)b0 * sc_frame_stride, d_assign + (size_t)b0 * p->N, &pc, a, nb, sc_frame_stride, -1, true)) return rc;
     if (h_cams) a->cams = c->stage.d_cams + b0;
+    a->shapes = shapes;
+    // esac_hip_read of the slabs / slot maps: frame 0 of this chunk keeps its slots at its OWN h*w (device_common.hpp:bwd_frame_strides)
+    if (shapes) c->train.last_slot_cells = (size_t)h_cams[b0].reserved[0] * (size_t)h_cams[b0].reserved[1];
+    return 0;
+}
+
+// A ragged training batch up to its table (both routes; who: the entry point).  p's H x W is the capacity: the workspaces, the
+// chunks (bwd_slot_bytes of the capacity -- a chunk of small frames could hold more of them; the charge is the safe side and
+// keeps the chunking a function of the parameters alone) and every launch are sized by it.  One frame IS the B = 1 batch on that
+// frame's grid: *p1 then carries the grid and the call goes on as a shared-shape one (*shapes = false).
+static int ragged_bwd_entry(const char* who, bool ctx, bool tensors, const esac_hip_params* p, int B, const esac_hip_frame_cam* h_cams,
+                            int64_t sc_frame_stride, int64_t grad_frame_stride, esac_hip_params* p1, bool* shapes) {
+    if (int rc = check_bwd_shapes_entry(who, h_cams != nullptr)) return rc;
+    if (!ctx || !p || B != 1) return 0;  // (check_batch_call reports the first two; B > 1: stage_cams checks the table)
+    const esac_hip_params p0 = with_cam(*p, h_cams[0]);
+    bool all_vec;
+    if (int rc = check_args(true, tensors, &p0, 1, 0, true)) return rc;
+    if (int rc = check_bwd_shapes(who, &p0, 1, h_cams, sc_frame_stride, grad_frame_stride, &all_vec)) return rc;
+    *p1 = *p;
+    p1->H = h_cams[0].reserved[0];
+    p1->W = h_cams[0].reserved[1];
+    *shapes = false;
     return 0;
 }
 
@@ -1241,12 +1271,21 @@ extern "C" int esac_hip_backward_batch(esac_hip_ctx* c, int B, const float* d_sc
 
 // ... with a camera per frame (h_cams: host, B records; NULL: the five fields of p for every frame).  Record b0 of a chunk goes
 // into the chunk's inline fields, the table pointer is offset by the chunk's first frame like gt_frames and the call counter.
-extern "C" int esac_hip_backward_batch_cams(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
-                                            int64_t grad_frame_stride, const int64_t* d_assign, const float* h_gt_poses, const esac_hip_frame_cam* h_cams,
-                                            float w_loss_rot, float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* h_out) {
+// shapes: esac_hip_backward_batch_shapes -- h_cams carries every frame's grid, p's H x W is the capacity (ragged_bwd_entry)
+static int backward_batch_impl(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
+                               int64_t grad_frame_stride, const int64_t* d_assign, const float* h_gt_poses, const esac_hip_frame_cam* h_cams,
+                               float w_loss_rot, float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* h_out, bool shapes) {
     const PoseArm arm = take_pose_arm(c);
-    int rc = check_batch_call("esac_hip_backward_batch", c != nullptr, p, B, d_sc && d_out_gradients && d_assign && h_gt_poses, false, h_out != nullptr, sc_frame_stride, grad_frame_stride);
+    const char* const shapes_who = "esac_hip_backward_batch_shapes";
+    // (a ragged batch: the capacity is no bound of the gradient stride -- check_bwd_shapes holds it against every frame's own grid)
+    int rc = check_batch_call("esac_hip_backward_batch", c != nullptr, p, B, d_sc && d_out_gradients && d_assign && h_gt_poses, false, h_out != nullptr, sc_frame_stride,
+                              shapes ? INT64_MAX : grad_frame_stride);
     if (rc) return rc;
+    esac_hip_params p1;
+    if (shapes) {
+        if ((rc = ragged_bwd_entry(shapes_who, true, true, p, B, h_cams, sc_frame_stride, grad_frame_stride, &p1, &shapes))) return rc;
+        if (!shapes) p = &p1;
+    }
     if ((rc = check_pose_arm("esac_hip_backward_batch", arm, B))) return rc;
     DeviceGuard guard(c->device);
     hipStream_t s = (hipStream_t)stream;
@@ -1264,7 +1303,9 @@ extern "C" int esac_hip_backward_batch_cams(esac_hip_ctx* c, int B, const float*
     KArgs a;
     const esac_hip_params p0 = h_cams ? with_cam(*p, h_cams[0]) : *p;
     if ((rc = make_args(c, d_sc, d_assign, &p0, &a, 1, 0, h_cams ? 0 : -1, true))) return rc;
-    if (h_cams && (rc = stage_cams(c, &p0, h_cams, B, s))) return rc;  // (checks every record before the first launch)
+    bool all_vec = true;
+    if (h_cams && (rc = stage_cams(c, &p0, h_cams, B, s, sc_frame_stride, shapes ? &all_vec : nullptr, shapes_who, grad_frame_stride))) return rc;  // (checks every record before the first launch)
+    const int shapes_mode = !shapes ? 0 : all_vec ? 1 : 2;
     HIP_OK(hipMemcpyAsync(c->stage.d_gt, c->stage.h_gt, (size_t)B * ESAC_GT_DOUBLES * sizeof(double), hipMemcpyHostToDevice, s));
     BwdCall call = {d_out_gradients, grad_frame_stride, w_loss_rot, w_loss_trans, loss_cut};
     call.gt_frames = c->stage.d_gt; call.batch = true; call.pose_rec = arm.rec;
@@ -1274,7 +1315,7 @@ extern "C" int esac_hip_backward_batch_cams(esac_hip_ctx* c, int B, const float*
     bool any_bad = false;
     for (int b0 = 0; b0 < B;) {
         int nb = chunk_frames(c->train.budget, cap, slot_bytes, B - b0);
-        if ((rc = chunk_args(c, d_sc, sc_frame_stride, d_assign, p, h_cams, b0, nb, &a))) return rc;
+        if ((rc = chunk_args(c, d_sc, sc_frame_stride, d_assign, p, h_cams, b0, nb, &a, shapes_mode))) return rc;
         if ((rc = enqueue_bwd_sampling(c, a, s, true))) return rc;
         for (int attempt = 0;; attempt++) {
             if ((rc = ensure_bws(c, N, P, cap, nb))) return rc;
@@ -1302,6 +1343,18 @@ extern "C" int esac_hip_backward_batch_cams(esac_hip_ctx* c, int B, const float*
                          "hypotheses were scored against expert 0)", p->E);
     return 0;
 }
+extern "C" int esac_hip_backward_batch_cams(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
+                                            int64_t grad_frame_stride, const int64_t* d_assign, const float* h_gt_poses, const esac_hip_frame_cam* h_cams,
+                                            float w_loss_rot, float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* h_out) {
+    return backward_batch_impl(c, B, d_sc, sc_frame_stride, d_out_gradients, grad_frame_stride, d_assign, h_gt_poses, h_cams, w_loss_rot, w_loss_trans, loss_cut, p, stream, h_out, false);
+}
+// Frames that differ in image size (include/esac_hip.h): frame b's grid in h_cams[b].reserved[0..1], its maps and its gradients
+// dense at the head of their slots; p->H * p->W is the capacity in cells.
+extern "C" int esac_hip_backward_batch_shapes(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
+                                              int64_t grad_frame_stride, const int64_t* d_assign, const float* h_gt_poses, const esac_hip_frame_cam* h_cams,
+                                              float w_loss_rot, float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* h_out) {
+    return backward_batch_impl(c, B, d_sc, sc_frame_stride, d_out_gradients, grad_frame_stride, d_assign, h_gt_poses, h_cams, w_loss_rot, w_loss_trans, loss_cut, p, stream, h_out, true);
+}
 
 // The asynchronous batch (include/esac_hip.h): ground truth, records and per-frame outcomes stay on the device, the host enqueues
 // and returns.  Nothing in here waits for the stream -- the one wait is stage_cams' on the PREVIOUS call's table copy -- and
@@ -1309,12 +1362,23 @@ extern "C" int esac_hip_backward_batch_cams(esac_hip_ctx* c, int B, const float*
 // chunks of consecutive frames sized by that worst case, one launch set after the other on the stream (which serialises their
 // use of the workspace).  A workspace that has to grow is grown before the first launch (ensure_ws / ensure_bws: one device
 // synchronisation, on the first call of a shape only).
+// (esac_hip_backward_batch_dev_shapes is this function behind a one-shot mark on the context, taken here like the pose arm: the
+// asynchronous route keeps ONE body, which tests/test_backward_batch_async_api.py reads from this signature to its closing brace)
 extern "C" int esac_hip_backward_batch_dev(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
                                            int64_t grad_frame_stride, const int64_t* d_assign, const float* d_gt_poses, const esac_hip_frame_cam* h_cams,
                                            float w_loss_rot, float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* d_out) {
     const PoseArm arm = take_pose_arm(c);
-    int rc = check_batch_call("esac_hip_backward_batch", c != nullptr, p, B, d_sc && d_out_gradients && d_assign && d_gt_poses, true, d_out != nullptr, sc_frame_stride, grad_frame_stride);
+    bool shapes = c && c->stage.shapes_next;  // h_cams carries every frame's grid, p's H x W is the capacity (ragged_bwd_entry)
+    if (c) c->stage.shapes_next = false;
+    const char* const shapes_who = "esac_hip_backward_batch_dev_shapes";
+    int rc = check_batch_call("esac_hip_backward_batch", c != nullptr, p, B, d_sc && d_out_gradients && d_assign && d_gt_poses, true, d_out != nullptr, sc_frame_stride,
+                              shapes ? INT64_MAX : grad_frame_stride);
     if (rc) return rc;
+    esac_hip_params p1;
+    if (shapes) {
+        if ((rc = ragged_bwd_entry(shapes_who, true, true, p, B, h_cams, sc_frame_stride, grad_frame_stride, &p1, &shapes))) return rc;
+        if (!shapes) p = &p1;
+    }
     if ((rc = check_pose_arm("esac_hip_backward_batch_dev", arm, B))) return rc;
     // the chunking is known before anything is launched: cap is the worst case, so the first chunk is the largest
     const int N = p->N, P = p->H * p->W, cap = bwd_rows(N);
@@ -1333,7 +1397,9 @@ extern "C" int esac_hip_backward_batch_dev(esac_hip_ctx* c, int B, const float* 
     const esac_hip_params p0 = h_cams ? with_cam(*p, h_cams[0]) : *p;
     if ((rc = make_args(c, d_sc, d_assign, &p0, &a, chunk, sc_frame_stride, h_cams ? 0 : -1, true))) return rc;
     if ((rc = ensure_bws(c, N, P, cap, chunk))) return rc;
-    if (h_cams && (rc = stage_cams(c, &p0, h_cams, B, s))) return rc;  // (checks every record before the first launch)
+    bool all_vec = true;
+    if (h_cams && (rc = stage_cams(c, &p0, h_cams, B, s, sc_frame_stride, shapes ? &all_vec : nullptr, shapes_who, grad_frame_stride))) return rc;  // (checks every record before the first launch)
+    const int shapes_mode = !shapes ? 0 : all_vec ? 1 : 2;
     launch_bwd_gt_prepare(d_gt_poses, B, c->stage.d_gt_dev, c->stage.d_frame_status, s);
     if ((rc = check_launch("k_bwd_gt_prepare"))) return rc;
     BwdCall call = {d_out_gradients, grad_frame_stride, w_loss_rot, w_loss_trans, loss_cut};
@@ -1341,13 +1407,24 @@ extern "C" int esac_hip_backward_batch_dev(esac_hip_ctx* c, int B, const float* 
     call.frame_status = c->stage.d_frame_status; call.rec_dev = d_out;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = B - b0 < chunk ? B - b0 : chunk;
-        if ((rc = chunk_args(c, d_sc, sc_frame_stride, d_assign, p, h_cams, b0, nb, &a))) return rc;
+        if ((rc = chunk_args(c, d_sc, sc_frame_stride, d_assign, p, h_cams, b0, nb, &a, shapes_mode))) return rc;
         if ((rc = enqueue_bwd_sampling(c, a, s, true))) return rc;
         fill_bwd(c, a, call, b0, nb, cap, false);  // (the slot workspace was sized for the largest chunk above)
         if ((rc = enqueue_bwd_chain(c, a, s, nullptr))) return rc;  // k_bwd_loss writes frame b's record into d_out[b*4..]
     }
     c->train.last_dev_batch = B;
     return 0;
+}
+// ... of frames that differ in image size (esac_hip_backward_batch_shapes without a host inside the call)
+extern "C" int esac_hip_backward_batch_dev_shapes(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
+                                                  int64_t grad_frame_stride, const int64_t* d_assign, const float* d_gt_poses, const esac_hip_frame_cam* h_cams,
+                                                  float w_loss_rot, float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* d_out) {
+    if (int rc = check_bwd_shapes_entry("esac_hip_backward_batch_dev_shapes", h_cams != nullptr)) {
+        (void)take_pose_arm(c);  // (one-shot: taken by the call whether it runs or not)
+        return rc;
+    }
+    if (c) c->stage.shapes_next = true;
+    return esac_hip_backward_batch_dev(c, B, d_sc, sc_frame_stride, d_out_gradients, grad_frame_stride, d_assign, d_gt_poses, h_cams, w_loss_rot, w_loss_trans, loss_cut, p, stream, d_out);
 }
 
 // Asynchronous calls (no host result) cannot report an out-of-range hypAssignment themselves: this waits for the
@@ -1432,7 +1509,9 @@ extern "C" int esac_hip_read(esac_hip_ctx* c, int which, void* h_dst, size_t byt
         case ESAC_BUF_BWD_MAPS: src = c->train.ws.maps; break;
     }
     // slots the slab workspace holds (>= the slots of the last call); after a batch, frame 0's slabs: its per-frame cap
-    const ReadDims dims = {(size_t)c->lastN, P, (size_t)bwd_rows(c->lastN), c->lastB, c->train.last_frames,
+    // (after a ragged training batch the slabs and slot maps of frame 0 are read in units of that frame's own cells: its slots lie there)
+    const bool slot_read = which == ESAC_BUF_BWD_PATH1 || which == ESAC_BUF_BWD_PATH2 || which == ESAC_BUF_BWD_MAPS;
+    const ReadDims dims = {(size_t)c->lastN, slot_read && c->train.last_slot_cells ? c->train.last_slot_cells : P, (size_t)bwd_rows(c->lastN), c->lastB, c->train.last_frames,
                            c->train.last_batch_cap > 0 ? (size_t)c->train.last_batch_cap : (size_t)c->train.slots, c->keep_errs};
     size_t want = 0;
     if (int rc = read_size(which, bytes, src != nullptr, dims, &want)) return rc;

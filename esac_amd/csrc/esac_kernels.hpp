@@ -102,12 +102,12 @@ struct BwdArgs {
     int* arrived;                    // [1] workgroups of k_bwd_accumulate that are done: the last one delivers the call's record to the
                                      // pinned slot (KArgs::result_pin) and leaves this at zero
     // batched training calls (esac_hip_backward_batch): frame b = blockIdx.y (k_bwd_accumulate: blockIdx.z) works on its own
-    // slice of every buffer above (bwd_frame_view); null / 0 on a single call
+    // slice of every buffer above (bwd_frame_strides); null / 0 on a single call
     const double* gt_frames;         // [B,22] per-frame gt[16] | gt_pose[6] (replaces the inline fields)
     int* sel_max;                    // [1] the largest unclamped selection of any frame: > cap stops the accumulation of EVERY frame
     long long grad_frame_stride;     // elements between the gradient tensors of consecutive frames
     // esac_hip_backward_batch_dev (no host inside the call); null on every other call.  Both are indexed by the frame of the
-    // launch (the C ABI offsets them by the chunk's first frame), not moved by bwd_frame_view
+    // launch (the C ABI offsets them by the chunk's first frame), not moved by bwd_frame_strides
     int* frame_status;               // [B] 0, or 2: the frame's ground-truth pose is singular (k_bwd_gt_prepare) -- the frame selects
                                      // nothing and adds nothing; k_bwd_loss sets 1 when the frame's assignment was out of range
     double* rec_dev;                 // [B,4] the caller's device records: k_bwd_loss writes frame b's four values itself
@@ -234,10 +234,11 @@ struct KArgs {
     long long sc_frame_stride;  // elements between the coordinate tensors of consecutive frames
     const FrameCam* cams;       // per-frame cameras [B] (esac_hip_*_batch_cams), or null: every frame uses the inline shift_x .. ppy.
                                 // When set, the inline fields hold record 0 (frame_view resolves the others)
-    int shapes;                 // 0: every frame is the inline H x W.  A ragged batch (esac_hip_forward_batch_shapes; needs cams): the
+    int shapes;                 // 0: every frame is the inline H x W.  A ragged batch (esac_hip_forward_batch_shapes, esac_hip_backward_batch_shapes; needs cams): the
                                 // inline H x W is the CAPACITY -- what every per-frame buffer, stride and launch is sized by -- and
                                 // frame_view puts cams[b].h, .w, .margin into H, W, margin (frame 0 included) AFTER the strides are
-                                // taken.  1: every frame's w is a multiple of 4 (the 16-byte error pass is legal), 2: not all are
+                                // taken.  1: every frame's w is a multiple of 4 (the 16-byte error pass is legal), 2: not all are; 3 (set by
+                                // launch_refine_slots alone): as 2, and each slot-refinement kernel takes the frames of ITS error pass
     BwdArgs bwd;                // training path only
 };
 

@@ -473,8 +473,12 @@ __global__ __launch_bounds__(B) void k_refine(KArgs a) {
     double* const s_pow10 = lds.pow10;
     static_assert(B == REFINE_B, "corr_region() assumes the refinement workgroup size");
     if (threadIdx.x < 33) s_pow10[threadIdx.x] = pow10_int((int)threadIdx.x - 16);  // (visible after the barriers of the winner pick)
-    frame_view(a);
-    if (SLOTS) bwd_frame_view(a, (int)blockIdx.y);  // (a batch's slots: grid (cap, frames))
+    if (SLOTS) train_frame_view(a, (int)blockIdx.y);  // (a batch's slots: grid (cap, frames))
+    else       frame_view(a);
+    // a ragged training batch whose widths are not all multiples of 4 (KArgs::shapes == 3, launch_refine_slots): both error passes
+    // are launched, and a frame is refined by the one its SINGLE call takes -- the two hand the cells to the lanes in different
+    // orders, so the re-fit's sums round differently.  (Workgroup-uniform, ahead of every barrier.)
+    if (SLOTS && a.shapes == 3 && ((a.W & 3) == 0) != VEC) return;
     const int P = a.H * a.W;
     const Cam cam = make_cam(a);
     const PxMap pm{a.sub, a.sub / 2 - a.shift_x, a.sub / 2 - a.shift_y};
@@ -647,6 +651,21 @@ void launch_refine_slots(const KArgs& a, hipStream_t s) {
     const bool global_list = a.H * a.W > LDS_CAP;
     const bool vec = rows_vectorise(a) && (reinterpret_cast<uintptr_t>(a.sc) & 15) == 0 && (a.frames == 1 || (a.sc_frame_stride & 3) == 0);
     const dim3 grid(a.N < a.bwd.cap ? a.N : a.bwd.cap, a.frames);
+    // A ragged batch with widths of both kinds (shapes == 2): frame b must be what its single call computes, and that call takes the
+    // 16-byte pass when w_b % 4 == 0.  Both kernels go out over the same grid, each returns at once for the frames of the other
+    // kind (shapes = 3 tells them to look) -- the idiom of the team / one-workgroup pair in front of this launch.
+    if (a.shapes == 2 && (reinterpret_cast<uintptr_t>(a.sc) & 15) == 0 && (a.sc_frame_stride & 3) == 0) {
+        KArgs b = a;
+        b.shapes = 3;
+        if (global_list) {
+            hipLaunchKernelGGL((k_refine<B, true, true, true>), grid, dim3(B), 0, s, b);
+            hipLaunchKernelGGL((k_refine<B, true, false, true>), grid, dim3(B), 0, s, b);
+        } else {
+            hipLaunchKernelGGL((k_refine<B, false, true, true>), grid, dim3(B), 0, s, b);
+            hipLaunchKernelGGL((k_refine<B, false, false, true>), grid, dim3(B), 0, s, b);
+        }
+        return;
+    }
     if (global_list) {
         if (vec) hipLaunchKernelGGL((k_refine<B, true, true, true>), grid, dim3(B), 0, s, a);
         else     hipLaunchKernelGGL((k_refine<B, true, false, true>), grid, dim3(B), 0, s, a);

@@ -563,6 +563,118 @@ def train_step(image, gt_pose, gating, experts, focal_length, hypotheses=256, th
     return out
 
 
+def _train_focals_pads(B, focal_lengths, shifts, subsample, generator):
+    """train_batch's per-image focal lengths and shifts (given, or drawn within +-subsample/2)."""
+    focals = [float(f) for f in (focal_lengths.tolist() if isinstance(focal_lengths, (torch.Tensor, np.ndarray)) and
+                                 getattr(focal_lengths, "ndim", 0) > 0 else
+                                 focal_lengths if isinstance(focal_lengths, (list, tuple)) else [focal_lengths] * B)]
+    if len(focals) != B:
+        raise RuntimeError("train_batch: focal_lengths must hold one value per image (%d), found %d" % (B, len(focals)))
+    if shifts is None:
+        m = int(subsample / 2)
+        if generator is not None:
+            drawn = torch.randint(-m, m + 1, (B, 2), generator=generator, device=generator.device).cpu().tolist()
+            pads = [(int(x), int(y)) for x, y in drawn]
+        else:
+            import random
+            pads = [(random.randint(-m, m), random.randint(-m, m)) for _ in range(B)]
+    else:
+        pads = [(int(s[0]), int(s[1])) for s in shifts]
+        if len(pads) != B:
+            raise RuntimeError("train_batch: shifts must hold one pair per image (%d), found %d" % (B, len(pads)))
+    return focals, pads
+
+
+def _train_batch_ragged(images, gt_poses, gating, experts, focal_lengths, hypotheses, threshold, inlier_alpha, inlier_beta,
+                        max_reprojection, subsample, weight_rot, weight_trans, loss_cut, max_experts, expert_selection, shifts, e_hyps,
+                        generator, strict_training, asynchronous, all_experts, evaluate, gt_experts):
+    """train_batch over images of different sizes (training sets resized by their shorter edge).  The networks run once per group
+    of equally sized images, as in `_localize_ragged`; their predictions go into ONE packed buffer (esac.pack_frames' layout),
+    followed by ONE solver call (`esac.backward_batch_shapes` or `esac.backward_batch_shapes_async`) that accumulates into a packed
+    gradient buffer of the same layout, and ONE `torch.autograd.backward` over every group's outputs and the gating.  Every frame
+    has its own principal point (the image centre), focal length and shift.  Every option keeps train_batch's meaning.
+    The result dict is train_batch's with prediction / prediction_gradients = the packed [B,S] buffers and shapes = [(h_b, w_b)]."""
+    B, E = len(images), len(experts)
+    dev = images[0].device
+    pp_x = [float(im.size(3) / 2) for im in images]
+    pp_y = [float(im.size(2) / 2) for im in images]
+    shapes = [(math.ceil(im.size(2) / subsample), math.ceil(im.size(3) / subsample)) for im in images]
+    focals, pads = _train_focals_pads(B, focal_lengths, shifts, subsample, generator)
+    images = [torch.nn.functional.pad(im, (px, -px, py, -py)) for im, (px, py) in zip(images, pads)]
+    groups = {}  # image size -> frames, in order of first appearance
+    for b, im in enumerate(images):
+        groups.setdefault(tuple(im.shape[1:]), []).append(b)
+    stacked = {key: torch.cat([images[b] for b in members]) for key, members in groups.items()}
+    order = [b for members in groups.values() for b in members]  # frame of row r of the groups' outputs, one after the other
+    inverse = torch.as_tensor(sorted(range(B), key=order.__getitem__), device=dev)
+    gating_log_probs = torch.cat([gating(stacked[key]) for key in groups]).index_select(0, inverse)  # [B,E], frame order
+    expert = None
+    with torch.no_grad():
+        if e_hyps is not None:
+            e_hyps = torch.as_tensor(e_hyps, dtype=torch.int64).to(dev)
+            if e_hyps.dim() != 2 or e_hyps.size(0) != B:
+                raise RuntimeError("train_batch: e_hyps must be [B,N]")
+            if expert_selection:
+                expert = e_hyps[:, :1]
+        else:
+            gating_probs = torch.exp(gating_log_probs).clone()
+            for b in range(B):
+                clamp_probs(gating_probs[b], max_experts)
+            if expert_selection:
+                expert = torch.multinomial(gating_probs, 1, replacement=True, generator=generator)  # [B,1]
+                e_hyps = expert.expand((B, hypotheses))
+            else:
+                e_hyps = torch.multinomial(gating_probs, hypotheses, replacement=True, generator=generator)
+        e_hist = torch.zeros((B, E), device=dev).scatter_add_(1, e_hyps, torch.ones(e_hyps.shape, device=dev))
+        active = None if all_experts else (e_hist > 0).cpu().tolist()  # B x E flags: all that reaches the host before the call
+    packed = torch.zeros((B, api.packed_stride(E, shapes)), dtype=torch.float32, device=dev)
+    outputs = []  # (group's frames, expert, the expert's output on the group [n,3,h,w])
+    for key, members in groups.items():
+        for e in range(E):
+            if active is not None and not any(active[b][e] for b in members):
+                continue  # (rows of inactive experts are zeros, never read, and receive no gradient)
+            maps = experts[e](stacked[key])
+            outputs.append((members, e, maps))
+            with torch.no_grad():
+                for i, b in enumerate(members):
+                    api.unpack_frames(packed[b:b + 1], [shapes[b]], E)[0][e] = maps[i]
+    packed_gradients = torch.zeros_like(packed)
+    strict_before = api._state["strict_training"]
+    api.set_strict_training(strict_before or strict_training)
+    gt_t = torch.as_tensor(np.asarray(gt_poses, np.float32) if not isinstance(gt_poses, torch.Tensor) else gt_poses, dtype=torch.float32)
+    records = torch.zeros((B, api.RES_DOUBLES), dtype=torch.float64, device=dev) if evaluate else None
+    try:
+        solver = api.backward_batch_shapes_async if asynchronous else api.backward_batch_shapes
+        losses = solver(packed, packed_gradients, e_hyps.contiguous(), gt_t if asynchronous else gt_t.cpu(), weight_rot, weight_trans,
+                        loss_cut, [p[0] for p in pads], [p[1] for p in pads], focals, pp_x, pp_y, threshold, inlier_alpha, inlier_beta,
+                        max_reprojection, subsample, poseRecords=records, shapes=shapes, experts=E)
+    finally:
+        api.set_strict_training(strict_before)
+    ev = api.eval_batch(records, gt_t, gt_experts) if evaluate else None
+    loss_t = losses.to(torch.float32) if asynchronous else torch.tensor(losses, device=dev, dtype=torch.float32)
+    if expert_selection:
+        gating_grads = torch.zeros_like(gating_log_probs)
+        gating_grads.scatter_(1, expert, loss_t.unsqueeze(1).to(gating_log_probs.dtype))
+    else:
+        gating_grads = (loss_t.unsqueeze(1) * e_hist).to(gating_log_probs.dtype)
+    frame_grads = api.unpack_frames(packed_gradients, shapes, E)  # views: frame b's [E,3,h_b,w_b]
+    tensors, grads = [], []
+    for members, e, maps in outputs:
+        if maps.requires_grad:
+            tensors.append(maps)
+            grads.append(torch.stack([frame_grads[b][e] for b in members]))
+    if gating_log_probs.requires_grad:
+        tensors.append(gating_log_probs)
+        grads.append(gating_grads)
+    if tensors:
+        torch.autograd.backward(tensors, grads)
+    out = dict(losses=losses, e_hyps=e_hyps, e_hist=e_hist, prediction=packed, prediction_gradients=packed_gradients, shapes=shapes,
+               gating_log_probs=gating_log_probs, pads=pads)
+    if evaluate:
+        out["records"], out["eval"] = records, ev
+    return out
+
+
 def train_batch(images, gt_poses, gating, experts, focal_lengths, hypotheses=256, threshold=10.0, inlier_alpha=100.0,
                 inlier_beta=0.5, max_reprojection=100.0, subsample=8, weight_rot=1.0, weight_trans=100.0, loss_cut=100.0,
                 max_experts=-1, expert_selection=False, shifts=None, e_hyps=None, generator=None, strict_training=False,
@@ -590,30 +702,25 @@ def train_batch(images, gt_poses, gating, experts, focal_lengths, hypotheses=256
     device tensors (asynchronous: still no host synchronisation in the step, given a device `gt_experts` tensor or None).  A frame
     whose winner held no slot -- a singular ground truth on the asynchronous route among them -- has EVAL_STATUS 1 and NaN figures.
     Returns dict(losses (list of B floats; asynchronous: device tensor [B]), e_hyps [B,N], e_hist [B,E], prediction [B,E,3,h,w],
-    prediction_gradients, gating_log_probs [B,E], pads (list of B pairs))."""
+    prediction_gradients, gating_log_probs [B,E], pads (list of B pairs)).
+    images may also be a LIST of B images [1,3,H_b,W_b] (or [3,H_b,W_b]) of different sizes: a ragged mini-batch
+    (`_train_batch_ragged`; a list whose images share one size is stacked and takes the route above)."""
+    if isinstance(images, (list, tuple)):
+        images = [im if im.dim() == 4 else im.unsqueeze(0) for im in images]
+        if len(images) == 0 or any(im.dim() != 4 or im.size(0) != 1 for im in images):
+            raise RuntimeError("train_batch: images must be a [B,3,H,W] tensor or a non-empty list of [1,3,H,W] / [3,H,W] images")
+        if any(tuple(im.shape) != tuple(images[0].shape) for im in images):
+            return _train_batch_ragged(images, gt_poses, gating, experts, focal_lengths, hypotheses, threshold, inlier_alpha, inlier_beta,
+                                       max_reprojection, subsample, weight_rot, weight_trans, loss_cut, max_experts, expert_selection,
+                                       shifts, e_hyps, generator, strict_training, asynchronous, all_experts, evaluate, gt_experts)
+        images = torch.cat(images)
     dev = images.device
     B, E = int(images.size(0)), len(experts)
     pp_x = float(images.size(3) / 2)
     pp_y = float(images.size(2) / 2)
     pred_w = math.ceil(images.size(3) / subsample)
     pred_h = math.ceil(images.size(2) / subsample)
-    focals = [float(f) for f in (focal_lengths.tolist() if isinstance(focal_lengths, (torch.Tensor, np.ndarray)) and
-                                 getattr(focal_lengths, "ndim", 0) > 0 else
-                                 focal_lengths if isinstance(focal_lengths, (list, tuple)) else [focal_lengths] * B)]
-    if len(focals) != B:
-        raise RuntimeError("train_batch: focal_lengths must hold one value per image (%d), found %d" % (B, len(focals)))
-    if shifts is None:
-        m = int(subsample / 2)
-        if generator is not None:
-            drawn = torch.randint(-m, m + 1, (B, 2), generator=generator, device=generator.device).cpu().tolist()
-            pads = [(int(x), int(y)) for x, y in drawn]
-        else:
-            import random
-            pads = [(random.randint(-m, m), random.randint(-m, m)) for _ in range(B)]
-    else:
-        pads = [(int(s[0]), int(s[1])) for s in shifts]
-        if len(pads) != B:
-            raise RuntimeError("train_batch: shifts must hold one pair per image (%d), found %d" % (B, len(pads)))
+    focals, pads = _train_focals_pads(B, focal_lengths, shifts, subsample, generator)
     images = torch.cat([torch.nn.functional.pad(images[b:b + 1], (px, -px, py, -py)) for b, (px, py) in enumerate(pads)])
     gating_log_probs = gating(images)  # [B,E]
     expert = None

@@ -74,7 +74,8 @@ typedef struct esac_hip_params {
 typedef struct esac_hip_frame_cam {
     int32_t shift_x, shift_y; /* esac.cpp:67-68: the image's random shift (training) or 0 */
     float focal, ppx, ppy;    /* esac.cpp:69-71 */
-    int32_t reserved[3];      /* esac_hip_forward_batch_shapes: [0] rows h, [1] columns w of the frame's grid; [2] ignored */
+    int32_t reserved[3];      /* esac_hip_forward_batch_shapes, esac_hip_backward_batch_shapes, _dev_shapes: [0] rows h, [1] columns w
+                                 of the frame's grid; [2] ignored */
 } esac_hip_frame_cam;
 
 /* esac_hip_forward / _batch: score EVERY hypothesis in the reference's mixed float/double arithmetic
@@ -301,7 +302,7 @@ int esac_hip_forward_batch_cams(esac_hip_ctx* ctx, int B, const float* d_scene_c
  *   read-back esac_hip_read keeps the capacity stride: after the call, frame b's per-cell data is the first h_b * w_b entries
  *             of its slot of p->H * p->W (ESAC_BUF_INLIER_MAP, frame 0's: p->H * p->W bytes whose first h_0 * w_0 are the map).
  * A table whose shapes all equal p->H x p->W computes what esac_hip_forward_batch_cams computes, bit for bit.  B == 1 is the
- * single call on h_cams[0]'s grid.  h_result_out == NULL is the asynchronous form.  The training calls have no such form yet.
+ * single call on h_cams[0]'s grid.  h_result_out == NULL is the asynchronous form.  The training calls: esac_hip_backward_batch_shapes, _dev_shapes.
  */
 int esac_hip_forward_batch_shapes(esac_hip_ctx* ctx, int B, const float* d_scene_coords, int64_t sc_frame_stride,
                                   const int64_t* d_hyp_assign, const esac_hip_params* p, const esac_hip_frame_cam* h_cams,
@@ -478,6 +479,39 @@ int esac_hip_backward_batch_dev(esac_hip_ctx* ctx, int B, const float* d_scene_c
                                 float* d_out_gradients, int64_t grad_frame_stride, const int64_t* d_hyp_assign,
                                 const float* d_gt_poses, const esac_hip_frame_cam* h_cams, float w_loss_rot,
                                 float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* d_out);
+
+/*
+ * RAGGED training batches (new, additive: the ABI version stays): esac_hip_backward_batch_cams / esac_hip_backward_batch_dev whose
+ * frames also differ in image size, as in esac_hip_forward_batch_shapes.  Frame b's grid is h_cams[b].reserved[0] rows x
+ * reserved[1] columns (reserved[2] is ignored); h_cams is required (-1 without it).
+ *   layout    frame b's maps lie DENSE as [E,3,h_b,w_b] floats at d_scene_coords + b * sc_frame_stride, and its gradients DENSE
+ *             as [E,3,h_b,w_b] floats at d_out_gradients + b * grad_frame_stride, accumulated into (+=).  Nothing beyond the
+ *             3 * E * h_b * w_b floats of either slot is read or written.  sc_frame_stride as in esac_hip_forward_batch_shapes;
+ *             with B > 1, grad_frame_stride >= 3 * E * h_b * w_b for every frame (so >= 3 * E * max(h_b * w_b)).
+ *   capacity  p->H * p->W >= every h_b * w_b: what the slot workspace, its chunks within ESAC_BWD_BATCH_BUDGET_MB (a slot is
+ *             charged at the capacity whatever its frame's size -- a chunk of small frames could hold more of them) and every
+ *             launch are sized for.  The gradient stride is NOT held against the capacity.
+ *   contract  frame b is esac_hip_backward on that frame alone: its own maps, h_cams[b]'s camera, its ground truth, call p->call
+ *             + b; bit for bit under the conditions of esac_hip_backward_batch.  Chunks, the blocking call's re-run after a slot
+ *             overflow, the asynchronous call's worst-case slots, ESAC_FLAG_STRICT_TRAINING and armed pose records
+ *             (esac_hip_set_bwd_pose_records) work as in the shared-shape calls.
+ *   checks    those of the shared-shape call (its codes and messages), every frame as in esac_hip_forward_batch_shapes, and the
+ *             gradient slots; the error (-4) names the first offending frame.  All before anything is launched: the gradients
+ *             stay untouched.
+ *   read-back per-hypothesis and per-slot tables as after esac_hip_backward_batch.  ESAC_BUF_BWD_PATH1 / _PATH2 / _MAPS (frame
+ *             0 of the last chunk): inside a frame's region slot k lies at the frame's OWN cells p_0 = h_0 * w_0 -- slabs of
+ *             3 * p_0 doubles, slot maps of 2 * p_0 bytes -- and that is the unit these reads take after such a call.
+ * A table whose shapes all equal p->H x p->W computes what esac_hip_backward_batch_cams / _dev compute, bit for bit; B == 1 is
+ * that call with B == 1 on h_cams[0]'s grid.
+ */
+int esac_hip_backward_batch_shapes(esac_hip_ctx* ctx, int B, const float* d_scene_coords, int64_t sc_frame_stride,
+                                   float* d_out_gradients, int64_t grad_frame_stride, const int64_t* d_hyp_assign,
+                                   const float* h_gt_poses, const esac_hip_frame_cam* h_cams, float w_loss_rot,
+                                   float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* h_out);
+int esac_hip_backward_batch_dev_shapes(esac_hip_ctx* ctx, int B, const float* d_scene_coords, int64_t sc_frame_stride,
+                                       float* d_out_gradients, int64_t grad_frame_stride, const int64_t* d_hyp_assign,
+                                       const float* d_gt_poses, const esac_hip_frame_cam* h_cams, float w_loss_rot,
+                                       float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* d_out);
 
 /*
  * The winner's refined pose of a training call, as a forward record (new, additive: the ABI version stays).  A training call
