@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "esac_hip_set_bwd_pose_records",  # additive too
     "esac_hip_forward_batch_shapes",  # additive too
     "esac_hip_backward_batch_shapes", "esac_hip_backward_batch_dev_shapes",  # additive too
+    "esac_hip_set_refine_route",  # additive too
 ]
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
@@ -265,6 +266,7 @@ def load_library():
         lib.esac_hip_shard_balanced.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
         lib.esac_hip_set_wait.argtypes = [vp, i32]
         lib.esac_hip_set_refine_team.argtypes = [vp, i32]
+        lib.esac_hip_set_refine_route.argtypes = [vp, i32]
         lib.esac_hip_host_turn.argtypes = [vp, vp]
         lib.esac_hip_host_turn_mean.argtypes = [vp, vp, i32]
         lib.esac_hip_comm_unique_id.argtypes = [vp, C.c_size_t]
@@ -854,6 +856,11 @@ class Engine:
         10 on the 60x80 grid; esac_hip_set_refine_team)."""
         _check(self.lib.esac_hip_set_refine_team(self.ctx, int(members)), self.lib)
 
+    def set_refine_route(self, on=True):
+        """May a single frame's team run the kernel with the headline call's modes compiled in (esac_hip_set_refine_route)?
+        False: every team runs the general kernel -- same outputs, bit for bit."""
+        _check(self.lib.esac_hip_set_refine_route(self.ctx, 1 if on else 0), self.lib)
+
     def bwd_team_info(self):
         """Training path: were the slots of the last backward call refined by teams (ESAC_BUF_BWD_TEAM_INFO)."""
         v = self.read(BUF_BWD_TEAM_INFO)
@@ -867,7 +874,7 @@ class Engine:
         return {"mode": ("one_workgroup", "cooperating", "team")[int(v[0])] if 0 <= int(v[0]) <= 2 else int(v[0]),
                 "workgroups": int(v[1]),
                 "xcd_census": [(int(v[2]) >> (8 * x)) & 255 for x in range(4)] + [(int(v[7]) >> (8 * x)) & 255 for x in range(4)],
-                "same_xcd": bool(v[3]),
+                "same_xcd": bool(int(v[3]) & 1), "route_kernel": bool(int(v[3]) & 2),
                 "exchanges": int(v[4]), "timed_out": bool(v[5]), "team_fallbacks": int(v[6]) & 0x3fffffff,
                 "team_latched_off": bool(int(v[6]) & 0x40000000)}
 

@@ -127,6 +127,7 @@ struct esac_hip_ctx {
         bool was_team = false;                // the most recent forward's refinement launch was a team's
         TeamLatch latch;                      // the forward path's time-out latch (call_policy.hpp)
         bool fold_select = true;              // the team kernel may run the selection in its prologue (ESAC_FOLD_SELECT=0: measurement scripts)
+        bool route = true;                    // a single frame's team may run the route kernel (esac_hip_set_refine_route; ESAC_REFINE_ROUTE=0)
         int last_nsel = 0;                    // slots the most recent blocking esac_hip_backward refined (0: none yet; reported, decides nothing)
         bool slot_teams = true;               // training path: slots may be refined by teams (off after a time-out until
                                               // esac_hip_set_refine_team re-arms it; ESAC_SLOT_TEAMS=0)
@@ -288,6 +289,7 @@ extern "C" int esac_hip_create(esac_hip_ctx** out, int device) {
         c->team.members = g < 2 ? 0 : (g > ESAC_REFINE_TEAM_MAX ? ESAC_REFINE_TEAM_MAX : g);
     }
     if (const char* e = getenv("ESAC_FOLD_SELECT")) c->team.fold_select = atoi(e) != 0;
+    if (const char* e = getenv("ESAC_REFINE_ROUTE")) c->team.route = atoi(e) != 0;
     if (const char* e = getenv("ESAC_REFINE_TEAM_AUTO")) c->team.auto_env_off = atoi(e) == 0;
     if (c->team.auto_env_off || getenv("ESAC_REFINE_TEAM")) c->team.auto_size = false;  // (an explicit start value is an explicit size)
     if (const char* e = getenv("ESAC_SLOT_TEAMS")) c->team.slot_teams = atoi(e) != 0;
@@ -457,6 +459,7 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
     a.coop_max = c->coop_max; a.coop_extra = c->coop_stall ? 1 : 0;
     a.team = c->team.members;  // (the forward entry points fold the time-out latch in: forward_team)
     a.team_auto = c->team.auto_size ? 1 : 0; a.team_stride = c->team.spread ? 1 : 8;
+    a.route = c->team.route ? 1 : 0;
     a.solo = 0; a.spec_mode = 0; a.spec_gate = 0; a.spec_debug = 0;
     a.spec_flag = nullptr;  // (forward_impl hands the flags to the kernels of a speculative call only)
     a.epoch = c->epoch += 1.0;  // every call gets its own epoch: result hand-off word and the tag of the status word
@@ -1579,6 +1582,11 @@ extern "C" int esac_hip_set_refine_team(esac_hip_ctx* c, int members) {
     c->team.members = requested_team(members);
     c->team.latch.requested();  // an explicit request re-arms the forward teams and the training path's slot teams
     c->team.slot_teams = true;
+    return 0;
+}
+extern "C" int esac_hip_set_refine_route(esac_hip_ctx* c, int on) {
+    if (!c) return fail(-1, "null context");
+    c->team.route = on != 0;
     return 0;
 }
 extern "C" int esac_hip_set_debug(esac_hip_ctx* c, int flags) {

@@ -189,7 +189,9 @@ struct KArgs {
     int team_stride;                    // the team's members are the workgroups blockIdx.x % team_stride == 0 (8: one XCD; 1: debug, spread)
     int solo;                           // 1: launch_refine takes ONE workgroup per refinement whatever the shape (the retry after a shared
                                         // refinement timed out: neither a team nor cooperating workgroups, both need co-residency again)
-    int* refine_info;                   // [8] mode, members, XCD census (4 bits per XCD), same-XCD flag, exchanges, failed
+    int route;                          // 1: launch_refine_team may take the route kernel (k_refine_team_route: the headline call's modes compiled
+                                        // in) where refine_takes_route allows it; 0: always the general kernel (esac_hip_set_refine_route)
+    int* refine_info;                   // [8] mode, members, XCD census (4 bits per XCD), same-XCD flag | 2 * route kernel, exchanges, failed
     int fold_select;                    // 1: the team kernel also runs the selection (softmax statistics, band of contenders, their exact
                                         // re-score) in its prologue: no k_select_rescore launch in front of it (refine_folds_select);
                                         // 2: ESAC_FLAG_EXACT_SCORES -- every score is exact already, the prologue only takes the softmax
@@ -274,6 +276,7 @@ int refine_coop_slice(const KArgs& a);  // cells per cooperating refinement work
 int refine_team_members(const KArgs& a);  // members of the team that refines a small grid, 0: one workgroup refines
 unsigned long long launch_refine(const KArgs& a, hipStream_t s);  // returns the tag of a shared (cooperative / team) launch, 0 otherwise
 unsigned long long launch_refine_team(const KArgs& a, hipStream_t s);  // esac_refine_team.hip; requires refine_team_members(a) > 0
+void launch_refine_team_route(const KArgs& b, int cpl, int G, hipStream_t s);  // esac_refine_team_route.hip; launch_refine_team's, where refine_takes_route holds
 unsigned long long next_refine_tag();
 bool refine_folds_select(const KArgs& a);  // the refinement launch of this call can (and will) do the selection itself
 bool refine_folds_exact_stats(const KArgs& a);  // ... the softmax statistics of the exact scores (ESAC_FLAG_EXACT_SCORES)

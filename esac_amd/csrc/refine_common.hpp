@@ -557,10 +557,11 @@ __device__ __forceinline__ RecordInputs refine_record_inputs(const KArgs& a, dou
 }
 
 // Called by ALL 64 lanes of the first wavefront of the workgroup that owns the outputs.  s_rec: >= 36 doubles of LDS that
-// nobody else touches any more.  census: XCD census of a team (hex digit x = members on XCD x), 0 otherwise.
+// nobody else touches any more.  census: XCD census of a team (hex digit x = members on XCD x), 0 otherwise.  route: 1 when the
+// team's route kernel writes this record (bit 1 of the info word [3]).
 __device__ __forceinline__ void refine_write_record(const KArgs& a, const RecordInputs& in, const double (&pose)[6], int win, double win_score, int e,
                                                     int nc, int accepted, int last_inliers, int lm_total, int map_buf, int mode, const Coop& co,
-                                                    unsigned long long census, double* s_rec) {
+                                                    unsigned long long census, double* s_rec, int route = 0) {
     const int lane = threadIdx.x & 63;
     // an exchange between the workgroups sharing this refinement timed out: the record is not to be trusted
     const unsigned long long launch_tag = mode == REFINE_TEAM ? team_tag(co) : co.tag;
@@ -599,7 +600,7 @@ __device__ __forceinline__ void refine_write_record(const KArgs& a, const Record
             a.refine_info[1] = co.G;
             a.refine_info[2] = (int)lo;
             a.refine_info[7] = (int)hi;
-            a.refine_info[3] = mode == REFINE_TEAM ? same : 0;
+            a.refine_info[3] = mode == REFINE_TEAM ? same | (route << 1) : 0;
             a.refine_info[4] = (int)(mode == REFINE_TEAM ? co.arrivals & TEAM_COUNT_MASK : co.arrivals);
             a.refine_info[5] = coop_failed ? 1 : 0;
         }

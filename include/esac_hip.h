@@ -217,8 +217,8 @@ enum {
     ESAC_BUF_REFINE_INFO = 19      /* int32[8] how the most recent winner refinement ran (refineHyp, esac_util.h:378-454):
                                       [0] 0 one workgroup, 1 cooperating workgroups (grids beyond one LDS list), 2 a team on
                                       one XCD (small grids); [1] workgroups sharing it; [2] XCD census of a team: byte x = members
-                                      that ran on XCD x, x = 0..3, [7] the same for XCDs 4..7; [3] 1 when all members shared one
-                                      XCD; [4] exchanges between them; [5] 1 when an exchange timed out; [6] bits 0..29: blocking calls on this
+                                      that ran on XCD x, x = 0..3, [7] the same for XCDs 4..7; [3] bit 0: all members shared one
+                                      XCD, bit 1: the team ran the route kernel (esac_hip_set_refine_route); [4] exchanges between them; [5] 1 when an exchange timed out; [6] bits 0..29: blocking calls on this
                                       context so far whose team timed out and were refined again by one workgroup, bit 30: the
                                       context has stopped asking for teams (two time-outs in a row; esac_hip_set_refine_team)   */
 };
@@ -665,6 +665,12 @@ int esac_hip_set_debug(esac_hip_ctx* ctx, int flags);
  * path's slot teams stay at 8 per team (32 teams of 8 are the chip's 256 CUs).  A number asks for exactly that many. */
 #define ESAC_REFINE_TEAM_AUTO (-1)
 int esac_hip_set_refine_team(esac_hip_ctx* ctx, int members);
+/* A single frame's team of at most 16 members that refines a call with ESAC_FLAG_EXACT_SCORES in force (ESAC_FLAG_AUTO_EXACT
+ * where it applies), at most 256 hypotheses, one expert, no speculation and no debug knob runs a kernel with exactly that
+ * combination compiled in (same arithmetic, same outputs bit for bit; fewer instructions issued).  on = 0: every team runs
+ * the general kernel (A/B measurements, tests).  Default: on; the environment variable ESAC_REFINE_ROUTE=0 starts a context
+ * with it off. */
+int esac_hip_set_refine_route(esac_hip_ctx* ctx, int on);
 
 /* How a blocking call waits for its result record (written by the last kernel into pinned host memory):
  * ESAC_WAIT_SPIN (default) polls the epoch word -- lowest latency, one host core busy for the ~0.2 ms of the call;

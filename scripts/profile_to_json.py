@@ -50,7 +50,9 @@ def main():
         for k, c, n, mean in d.execute("select kernel_name, counter_name, count(*), avg(value) from counters_collection "
                                        "group by kernel_name, counter_name"):
             counters.setdefault(k, {})[c] = mean
-    steps = max([k["calls"] for n, k in kernels.items() if "k_refine" in n] + [1])
+    # a call's winner is refined by ONE of the team kernels (k_refine_team, or k_refine_team_route on the headline's route): their calls add up
+    steps = max([sum(k["calls"] for n, k in kernels.items() if "k_refine_team" in n)] +
+                [k["calls"] for n, k in kernels.items() if "k_refine" in n and "k_refine_team" not in n] + [1])
     for name, k in kernels.items():
         k["per_step_us"] = k["total_us"] / steps
         c = counters.get(name, {})
