@@ -248,7 +248,10 @@ __device__ __forceinline__ int error_pass_impl(const KArgs& a, const float* __re
 #pragma unroll
             for (int l = 0; l < L; l++) {
                 const int u = g * L + l;
-                errv[u] = errv[u] < a.max_reproj ? errv[u] : a.max_reproj;  // std::min(l, maxReproj), esac_util.h:358
+                // std::min(l, maxReproj) = (maxReproj < l) ? maxReproj : l, esac_util.h:358 -- in ITS operand order: the NaN of a
+                // non-finite cell stays NaN and is no inlier below, also where maxReproj < tau (the other order made it maxReproj:
+                // an inlier there, its NaN point in the re-fit's list; the team keeps such cells out through TeamCells::live)
+                errv[u] = a.max_reproj < errv[u] ? a.max_reproj : errv[u];
                 flag[u] = in_range && (errv[u] < a.tau);
             }
             if (in_range) {

@@ -107,7 +107,10 @@ __device__ __forceinline__ void team_pass(const KArgs& a, const TeamCells<CPL>& 
             for (int p = 0; p < CPL; p++) {
                 if (!__any(undecided[p])) continue;
                 float err = project_exact_err(Rx, param + 3, cam, (float)cl.X[p], (float)cl.Y[p], (float)cl.Z[p], (float)cl.px[p], (float)cl.py[p]);
-                err = err < band.max_reproj ? err : band.max_reproj;  // std::min(l, maxReproj), esac_util.h:358
+                // the clamp of esac_util.h:358.  Not std::min's operand order (maxReproj < l ? maxReproj : l, what error_pass_impl
+                // uses): the two differ for a NaN only, and no NaN gets here -- a non-finite point is not `live`, so never
+                // undecided -- nor could the clamp make an inlier: undecided implies !all_in, i.e. maxReproj >= tau
+                err = err < band.max_reproj ? err : band.max_reproj;
                 if (undecided[p] && err < band.tau) nset |= 1u << p;
             }
         }
