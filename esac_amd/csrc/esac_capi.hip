@@ -16,6 +16,7 @@
 
 #include "../../include/esac_hip.h"
 #include "call_policy.hpp"
+#include "batch_plan.hpp"
 #include "esac_kernels.hpp"
 #include "eval_math.hpp"
 #include "gt_math.hpp"
@@ -51,7 +52,9 @@ static_assert(POLICY_TILED_HC == ESAC_TILED_HC && POLICY_TILED_MAX_EXPERTS == ES
 // (torch and every other runtime user read the same thread-local "current device").
 struct DeviceGuard {
     int prev = -1;
-    explicit DeviceGuard(int dev) {
+    DeviceGuard() = default;  // (a call that learns its context's device behind its checks enters then: begin_bwd_batch)
+    explicit DeviceGuard(int dev) { enter(dev); }
+    void enter(int dev) {
         int cur = -1;
         if (hipGetDevice(&cur) == hipSuccess && cur != dev) prev = cur;
         if (cur != dev) (void)hipSetDevice(dev);
@@ -101,16 +104,25 @@ struct PoseArm {
     double* rec = nullptr;  // DEVICE [frames, ESAC_RES_DOUBLES], null: not armed
     int frames = 0;
 };
+// The most recent call on the context, as esac_hip_read and esac_hip_check need it.  make_args assigns the record as a whole (the
+// training-path fields of what the slot workspace still holds carried over); the writers behind it are named at their fields.
+struct LastCall {
+    int N = 0, H = 0, W = 0, B = 1;  // B: frames of the most recent launch set (B x the single-frame size reads the forward buffers of all)
+    size_t map1 = 0;        // where frame 0's SECOND inlier-map buffer starts in its slot: the cells of the grid frame 0's refinement ran on
+                            // (k_refine alternates maps + cur * P with ITS P) -- H * W, or frame 0's own h * w after a ragged batch (prepare_forward)
+    int bwd_frames = 1;     // frames whose training-path buffers the workspace holds (fill_bwd: the last launch set)
+    int batch_cap = 0;      // slots per frame of that launch set when it was a batch's (fill_bwd; 0: a single call)
+    size_t slot_cells = 0;  // a ragged training batch was the most recent call: the cells of its (last chunk's) frame 0, whose slots lie
+                            // that far apart (chunk_args; esac_hip_read of the slabs and the slot maps); 0 otherwise
+    int dev_batch = 0;      // B of the asynchronous training batch while it is the most recent call (esac_hip_check reads that many words)
+};
 struct esac_hip_ctx {
     int device = 0;
     int capN = 0, capP = 0, capB = 0;  // capN / capP count elements over ALL frames of a batch
     KArgs ws{};  // only the workspace pointers are kept here
     DevBufs fwd_bufs;    // the forward workspace (ensure_ws)
     DevBufs tiled_bufs;  // the tile-stationary score workspace (ensure_tiled_ws); dies with the forward workspace
-    int lastN = 0, lastH = 0, lastW = 0;
-    size_t last_map1 = 0;  // where frame 0's SECOND inlier-map buffer starts in its slot: the cells of the grid frame 0's refinement
-                           // ran on (k_refine alternates maps + cur * P with ITS P) -- lastH * lastW, or frame 0's own h * w after a ragged batch
-    int lastB = 1;  // frames of the most recent launch set (esac_hip_read: B x the single-frame size reads the per-frame forward buffers of all of them)
+    LastCall last;  // what esac_hip_read and esac_hip_check know of the most recent call
     bool keep_errs = false;  // esac_hip_set_debug: store the winner's error image
     PinView pin;
     double epoch = 0;         // bumped by every entry point: hand-off word of the pinned record
@@ -144,11 +156,6 @@ struct esac_hip_ctx {
         // batched training calls (esac_hip_backward_batch)
         int cap_batch = 0;                     // slots per frame the batches have needed so far
         long long budget = 2048LL << 20;       // bytes of slot workspace a batch may use (ESAC_BWD_BATCH_BUDGET_MB): beyond it, chunks of frames
-        int last_frames = 1;                   // frames whose training-path buffers the workspace holds (the last launch set)
-        int last_batch_cap = 0;                // slots per frame of the last launch set when it was a batch's (0: a single call)
-        size_t last_slot_cells = 0;            // a ragged training batch was the most recent call: the cells of its (last chunk's) frame 0, whose
-                                               // slots lie that far apart (esac_hip_read of the slabs and the slot maps); 0 otherwise
-        int last_dev_batch = 0;                // B of esac_hip_backward_batch_dev while it is the most recent call on the context (esac_hip_check reads that many words)
     } train;
     struct {  // per-call staging
         double* h_gt = nullptr;                // pinned staging of the per-frame ground truth [ESAC_MAX_BATCH,22]
@@ -159,11 +166,10 @@ struct esac_hip_ctx {
         // esac_hip_set_bwd_pose_records: what the NEXT training call writes its forward-format records to (one-shot: take_pose_arm)
         PoseArm pose_arm;
         // per-frame cameras of a batch (esac_hip_forward_batch_cams / esac_hip_backward_batch_cams)
-        FrameCam* h_cams = nullptr;            // pinned staging [ESAC_MAX_BATCH]: the caller's array is free when the call returns
+        esac_hip_frame_cam* h_cams = nullptr;  // pinned staging [ESAC_MAX_BATCH]: the caller's array is free when the call returns
         FrameCam* d_cams = nullptr;            // ... and the table the kernels read (KArgs::cams)
         hipEvent_t cams_ev = nullptr;          // recorded behind the most recent upload: the staging is rewritten only after it
         bool cams_queued = false;
-        bool shapes_next = false;              // esac_hip_backward_batch_dev_shapes: the esac_hip_backward_batch_dev call it makes is a ragged one (one-shot)
     } stage;
     float4* sc4 = nullptr;  // packed copy of the maps for the sampler (ensure_pack_ws), of sc4_cells cells
     long long sc4_cells = 0, tPart = 0;  // tN, tChunks, tPart: what the tile-stationary score workspace holds (ensure_tiled_ws)
@@ -418,12 +424,6 @@ static int ensure_tiled_ws(esac_hip_ctx* c, int N, int P, int E) {
     return 0;
 }
 
-static esac_hip_params with_cam(const esac_hip_params& p, const esac_hip_frame_cam& cam) {
-    esac_hip_params q = p;
-    q.shift_x = cam.shift_x; q.shift_y = cam.shift_y; q.focal = cam.focal; q.ppx = cam.ppx; q.ppy = cam.ppy;
-    return q;
-}
-
 // A call's argument block: checked (call_policy.hpp: check_args), the workspaces grown, pointers copied, the derived scalars
 // filled in (call_scalars), a fresh epoch
 static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign, const esac_hip_params* p, KArgs* out,
@@ -445,8 +445,8 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
         a.partials = nullptr;  // launch_score: per-hypothesis stream
     }
     a.frames = B; a.sc_frame_stride = sc_frame_stride;
-    a.cams = nullptr;  // (the _cams entry points set it after stage_cams)
-    a.shapes = 0;      // (esac_hip_forward_batch_shapes sets it with the table)
+    a.cams = nullptr;  // (the batch routes set both from their plan, behind stage_cams)
+    a.shapes = 0;
     a.sc = d_sc; a.assign = d_assign;
     a.E = p->E; a.H = p->H; a.W = p->W; a.N = p->N;
     a.shift_x = p->shift_x; a.shift_y = p->shift_y; a.sub = p->sub_sampling;
@@ -466,35 +466,19 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
     a.sample_epoch = c->sample_epoch;  // launches that sample call mark_sampling() and overwrite this
     // (device-side span stamps only on sampled calls in timing mode: forward_impl clears tstamps otherwise)
     if (!c->keep_errs) a.errs = nullptr;
-    c->lastN = p->N; c->lastH = p->H; c->lastW = p->W;
-    c->last_map1 = (size_t)P;  // (a ragged batch: prepare_forward puts frame 0's own cell count here)
-    c->lastB = B;
-    c->train.last_dev_batch = 0;  // (esac_hip_backward_batch_dev sets it again once its launches are queued)
-    c->train.last_slot_cells = 0; // (a ragged training batch sets it behind its chunk's arguments)
+    c->last = LastCall{p->N, p->H, p->W, B, (size_t)P, c->last.bwd_frames, c->last.batch_cap, 0, 0};
     *out = a;
     return 0;
 }
 
-// Per-frame cameras of a batch: every record checked like a single call's camera (p: the call's parameters, already validated by
-// make_args with record 0), then staged in pinned memory of the context's own and uploaded on `s` -- once per call; chunks and
-// re-runs offset the device pointer.  The staging is rewritten only after the previous upload has left it (an asynchronous
-// forward batch may still have its copy queued); the device table is rewritten in stream order behind its last readers.
-// shapes_vec != null: a ragged batch (esac_hip_forward_batch_shapes) -- every record is checked with its own grid (check_shapes),
-// staged with its own re-score margin (shape_record), and *shapes_vec says whether every frame's width is a multiple of 4.
-// bwd_who != null: the table of a ragged TRAINING batch (the entry point's name) -- the gradient slots are checked with it.
-static int stage_cams(esac_hip_ctx* c, const esac_hip_params* p, const esac_hip_frame_cam* h_cams, int B, hipStream_t s,
-                      int64_t sc_frame_stride = 0, bool* shapes_vec = nullptr, const char* bwd_who = nullptr, int64_t grad_frame_stride = 0) {
+// The table of a planned batch call (batch_plan.hpp: every record is checked), staged in pinned memory of the context's own and
+// uploaded on `s` -- once per call; chunks and re-runs offset the device pointer.  The staging is rewritten only after the previous
+// upload has left it (an asynchronous batch may still have its copy queued); the device table in stream order behind its last readers.
+static int stage_cams(esac_hip_ctx* c, const BatchPlan& plan, const esac_hip_frame_cam* h_cams, int B, hipStream_t s) {
     static_assert(sizeof(esac_hip_frame_cam) == sizeof(FrameCam) && offsetof(esac_hip_frame_cam, focal) == offsetof(FrameCam, focal) &&
                   offsetof(esac_hip_frame_cam, ppy) == offsetof(FrameCam, ppy), "esac_hip_frame_cam is the device record");
     static_assert(offsetof(esac_hip_frame_cam, reserved) == offsetof(FrameCam, h) && offsetof(FrameCam, w) == offsetof(FrameCam, h) + 4 &&
                   offsetof(FrameCam, margin) == offsetof(FrameCam, h) + 8, "reserved[0..2] = the frame's h, w and margin");
-    if (shapes_vec) {
-        if (int rc = bwd_who ? check_bwd_shapes(bwd_who, p, B, h_cams, sc_frame_stride, grad_frame_stride, shapes_vec)
-                             : check_shapes(p, B, h_cams, sc_frame_stride, shapes_vec)) return rc;
-    } else {
-        for (int b = 0; b < B; b++)
-            if (int rc = check_cam(p, h_cams[b].shift_x, h_cams[b].shift_y, h_cams[b].focal, b)) return rc;
-    }
     if (!c->stage.h_cams) {
         HIP_OK(hipHostMalloc((void**)&c->stage.h_cams, (size_t)ESAC_MAX_BATCH * sizeof(FrameCam), hipHostMallocDefault));
         HIP_OK(hipMalloc((void**)&c->stage.d_cams, (size_t)ESAC_MAX_BATCH * sizeof(FrameCam)));
@@ -504,12 +488,7 @@ static int stage_cams(esac_hip_ctx* c, const esac_hip_params* p, const esac_hip_
         HIP_OK(hipEventSynchronize(c->stage.cams_ev));
         c->stage.cams_queued = false;
     }
-    memcpy(c->stage.h_cams, h_cams, (size_t)B * sizeof(FrameCam));
-    if (shapes_vec)
-        for (int b = 0; b < B; b++) {
-            const esac_hip_frame_cam r = shape_record(p, h_cams[b]);
-            memcpy(c->stage.h_cams + b, &r, sizeof(r));
-        }
+    plan_records(plan, h_cams, B, c->stage.h_cams);
     HIP_OK(hipMemcpyAsync(c->stage.d_cams, c->stage.h_cams, (size_t)B * sizeof(FrameCam), hipMemcpyHostToDevice, s));
     HIP_OK(hipEventRecord(c->stage.cams_ev, s));
     c->stage.cams_queued = true;
@@ -622,23 +601,22 @@ static inline const char* enqueue_serial_stage(esac_hip_ctx* c, const KArgs& a, 
         default: c->team.refine_tag = launch_refine(a, s); return "k_refine";
     }
 }
-// A forward call up to its first launch (p carries record 0 of a per-frame camera table in its inline fields); *tm: the call is timed
+// A forward call up to its first launch (p: the plan's block where there is a table -- record 0 inline); *tm: the call is timed
 static int prepare_forward(esac_hip_ctx* c, const float* d_sc, long long sc_frame_stride, const int64_t* d_assign, const esac_hip_params* p,
-                           int B, hipStream_t s, const esac_hip_frame_cam* h_cams, bool shapes, double t_entry, KArgs* out, bool* tm) {
+                           int B, hipStream_t s, const esac_hip_frame_cam* h_cams, const BatchPlan& plan, double t_entry, KArgs* out, bool* tm) {
     KArgs& a = *out;
     int rc = make_args(c, d_sc, d_assign, p, &a, B, sc_frame_stride, h_cams ? 0 : -1);
     if (rc) return rc;
-    if (h_cams && B > 1) {  // (one frame: record 0 is the whole table)
-        // shapes: p's H x W is the capacity -- make_args has sized the workspaces, and every host decision below reads a.H * a.W as
-        // that (team size and cells per lane, LDS or global list, the selection's split, the sampler's plan); the kernels take the
-        // frame's own grid and margin from the table (device_common.hpp:frame_view)
-        bool all_vec = true;
-        if ((rc = stage_cams(c, p, h_cams, B, s, sc_frame_stride, shapes ? &all_vec : nullptr))) return rc;
+    if (plan.stage) {
+        // a ragged table: p's H x W is the capacity -- make_args has sized the workspaces, and every host decision below reads
+        // a.H * a.W as that (team size and cells per lane, LDS or global list, the selection's split, the sampler's plan); the
+        // kernels take the frame's own grid and margin from the table (device_common.hpp:frame_view)
+        if ((rc = stage_cams(c, plan, h_cams, B, s))) return rc;
         a.cams = c->stage.d_cams;
-        a.shapes = !shapes ? 0 : all_vec ? 1 : 2;
+        a.shapes = plan.shapes;
         // esac_hip_read(ESAC_BUF_INLIER_MAP): the one-workgroup refinement alternates its two map buffers P cells apart with the
         // P of the frame's OWN grid (the team kernel only ever writes buffer 0)
-        if (shapes) c->last_map1 = (size_t)h_cams[0].reserved[0] * (size_t)h_cams[0].reserved[1];
+        if (plan.cells0) c->last.map1 = plan.cells0;
     }
     c->team.latch.forward_call();
     forward_team(c, a);
@@ -790,29 +768,17 @@ static int collect_records(esac_hip_ctx* c, KArgs& a, int B, hipStream_t s, doub
 static int forward_impl(esac_hip_ctx* c, const float* d_sc, long long sc_frame_stride, const int64_t* d_assign,
                         const esac_hip_params* p, int B, void* stream, double* d_scores_out, double* d_result_out, double* h_result_out, const esac_hip_frame_cam* h_cams = nullptr,
                         bool shapes = false) {
+    BatchPlan plan;  // (without a table: a null check, and the call goes on with the caller's block)
+    int rc = plan_batch(BATCH_FORWARD, "esac_hip_forward_batch_shapes", c != nullptr, d_sc && d_assign, true, p, B, h_cams, shapes, sc_frame_stride, 0, &plan);
+    if (rc) return rc;
+    if (h_cams) p = &plan.p;
     if (!c) return fail(-1, "null context");
     const double t_entry = now_ns();
     DeviceGuard guard(c->device);
-    hipStream_t s = (hipStream_t)stream;
-    esac_hip_params p0;
-    if (h_cams && p) {  // the inline fields carry record 0 (device_common.hpp:frame_view)
-        p0 = with_cam(*p, h_cams[0]);
-        p = &p0;
-    }
-    if (shapes && p && B == 1) {
-        // a ragged batch of one frame IS the single call on that frame's grid: checked like any table, then record 0's shape
-        // stands in the parameter block and every single-frame route (tiled score, packed maps, speculation) is open to it
-        bool all_vec;
-        if (int rc0 = check_args(true, d_sc && d_assign, p, B, 0, false)) return rc0;
-        if (int rc0 = check_shapes(p, 1, h_cams, sc_frame_stride, &all_vec)) return rc0;
-        p0.H = h_cams[0].reserved[0];
-        p0.W = h_cams[0].reserved[1];
-        shapes = false;
-    }
+    const hipStream_t s = (hipStream_t)stream;
     KArgs a;
     bool tm = false;
-    int rc = prepare_forward(c, d_sc, sc_frame_stride, d_assign, p, B, s, h_cams, shapes, t_entry, &a, &tm);
-    if (rc) return rc;
+    if ((rc = prepare_forward(c, d_sc, sc_frame_stride, d_assign, p, B, s, h_cams, plan, t_entry, &a, &tm))) return rc;
     a.scores_user = d_scores_out; a.result_user = d_result_out;
     a.result_pin = h_result_out ? c->pin.d : nullptr;
     c->spec.last_epoch = 0;
@@ -1028,15 +994,12 @@ extern "C" int esac_hip_forward_batch(esac_hip_ctx* c, int B, const float* d_sc,
 }
 extern "C" int esac_hip_forward_batch_cams(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, const int64_t* d_assign, const esac_hip_params* p, const esac_hip_frame_cam* h_cams,
                                            void* stream, double* d_scores_out, double* d_result_out, double* h_result_out) {
-    if (h_cams && (B < 1 || B > ESAC_MAX_BATCH)) return fail(-4, "batch size %d outside [1,%d]", B, ESAC_MAX_BATCH);  // (before h_cams[0] is read)
     return forward_impl(c, d_sc, (long long)sc_frame_stride, d_assign, p, B, stream, d_scores_out, d_result_out, h_result_out, h_cams);
 }
 // Frames that differ in image size: esac_hip_forward_batch_cams with frame b's grid in h_cams[b].reserved[0..1]; p->H * p->W is
 // the capacity in cells (include/esac_hip.h).  reserved[2] is the library's (the frame's margin goes there on the way to the device).
 extern "C" int esac_hip_forward_batch_shapes(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, const int64_t* d_assign, const esac_hip_params* p, const esac_hip_frame_cam* h_cams,
                                              void* stream, double* d_scores_out, double* d_result_out, double* h_result_out) {
-    if (!h_cams) return fail(-1, "esac_hip_forward_batch_shapes: null frame table (h_cams carries every frame's grid)");
-    if (B < 1 || B > ESAC_MAX_BATCH) return fail(-4, "batch size %d outside [1,%d]", B, ESAC_MAX_BATCH);  // (before h_cams[0] is read)
     return forward_impl(c, d_sc, (long long)sc_frame_stride, d_assign, p, B, stream, d_scores_out, d_result_out, h_result_out, h_cams, true);
 }
 
@@ -1084,37 +1047,25 @@ static int enqueue_bwd_sampling(esac_hip_ctx* c, KArgs& a, hipStream_t s, bool p
     return check_launch("k_rescore(all)");
 }
 
-// The KArgs of a batch's chunk [b0, b0 + nb): camera record b0 in the inline fields, the call counter, the tensors and the camera
-// table offset by the chunk's first frame (validated, workspaces grown, a fresh epoch: make_args).  shapes: KArgs::shapes of a
-// ragged batch (p's H x W is the capacity), decided over the WHOLE table, so that every chunk takes the same refinement kernel
-static int chunk_args(esac_hip_ctx* c, const float* d_sc, int64_t sc_frame_stride, const int64_t* d_assign, const esac_hip_params* p, const esac_hip_frame_cam* h_cams, int b0, int nb, KArgs* a,
-                      int shapes = 0) {
-    esac_hip_params pc = h_cams ? with_cam(*p, h_cams[b0]) : *p;
-    pc.call = p->call + (uint64_t)b0;
-    if (int rc = make_args(c, d_sc + (size_t)b0 * sc_frame_stride, d_assign + (size_t)b0 * p->N, &pc, a, nb, sc_frame_stride, -1, true)) return rc;
-    if (h_cams) a->cams = c->stage.d_cams + b0;
-    a->shapes = shapes;
-    // esac_hip_read of the slabs / slot maps: frame 0 of this chunk keeps its slots at its OWN h*w (device_common.hpp:bwd_frame_strides)
-    if (shapes) c->train.last_slot_cells = (size_t)h_cams[b0].reserved[0] * (size_t)h_cams[b0].reserved[1];
-    return 0;
-}
+// A batched training call as its extern "C" signature carries it (gt_poses, out: host memory of the blocking entry points, device
+// memory of the asynchronous ones).  shapes: h_cams carries every frame's grid and p's H x W is the capacity (a ragged batch).
+struct BwdBatchIn {
+    int B; const float* d_sc; int64_t sc_frame_stride; float* d_out_gradients; int64_t grad_frame_stride; const int64_t* d_assign;
+    const float* gt_poses; const esac_hip_frame_cam* h_cams; float w_loss_rot, w_loss_trans, loss_cut;
+    const esac_hip_params* p; void* stream; double* out; bool shapes;
+};
 
-// A ragged training batch up to its table (both routes; who: the entry point).  p's H x W is the capacity: the workspaces, the
-// chunks (bwd_slot_bytes of the capacity -- a chunk of small frames could hold more of them; the charge is the safe side and
-// keeps the chunking a function of the parameters alone) and every launch are sized by it.  One frame IS the B = 1 batch on that
-// frame's grid: *p1 then carries the grid and the call goes on as a shared-shape one (*shapes = false).
-static int ragged_bwd_entry(const char* who, bool ctx, bool tensors, const esac_hip_params* p, int B, const esac_hip_frame_cam* h_cams,
-                            int64_t sc_frame_stride, int64_t grad_frame_stride, esac_hip_params* p1, bool* shapes) {
-    if (int rc = check_bwd_shapes_entry(who, h_cams != nullptr)) return rc;
-    if (!ctx || !p || B != 1) return 0;  // (check_batch_call reports the first two; B > 1: stage_cams checks the table)
-    const esac_hip_params p0 = with_cam(*p, h_cams[0]);
-    bool all_vec;
-    if (int rc = check_args(true, tensors, &p0, 1, 0, true)) return rc;
-    if (int rc = check_bwd_shapes(who, &p0, 1, h_cams, sc_frame_stride, grad_frame_stride, &all_vec)) return rc;
-    *p1 = *p;
-    p1->H = h_cams[0].reserved[0];
-    p1->W = h_cams[0].reserved[1];
-    *shapes = false;
+// The KArgs of a batch's chunk [b0, b0 + nb): camera record b0 in the inline fields, the call counter, the tensors and the camera
+// table offset by the chunk's first frame (validated, workspaces grown, a fresh epoch: make_args).  KArgs::shapes is the plan's,
+// decided over the WHOLE table, so that every chunk of a ragged batch takes the same refinement kernel
+static int chunk_args(esac_hip_ctx* c, const BwdBatchIn& in, const BatchPlan& plan, int b0, int nb, KArgs* a) {
+    esac_hip_params pc = in.h_cams ? with_cam(plan.p, in.h_cams[b0]) : plan.p;
+    pc.call = plan.p.call + (uint64_t)b0;
+    if (int rc = make_args(c, in.d_sc + (size_t)b0 * in.sc_frame_stride, in.d_assign + (size_t)b0 * pc.N, &pc, a, nb, in.sc_frame_stride, -1, true)) return rc;
+    if (in.h_cams) a->cams = c->stage.d_cams + b0;
+    a->shapes = plan.shapes;
+    // esac_hip_read of the slabs / slot maps: frame 0 of this chunk keeps its slots at its OWN h*w (device_common.hpp:bwd_frame_strides)
+    if (plan.shapes) c->last.slot_cells = (size_t)in.h_cams[b0].reserved[0] * (size_t)in.h_cams[b0].reserved[1];
     return 0;
 }
 
@@ -1145,8 +1096,8 @@ static int check_pose_arm(const char* who, const PoseArm& arm, int B) { return c
 // slot workspace (which ensure_bws has sized).  Every field a route does not use is null / 0 here, in this one place.
 // want_teams: refine the slots by teams where this call can (single blocking calls; a.bwd.team_max_slots != 0 says it will).
 static void fill_bwd(esac_hip_ctx* c, KArgs& a, const BwdCall& call, int b0, int frames, int cap, bool want_teams) {
-    c->train.last_frames = frames;
-    c->train.last_batch_cap = call.batch ? cap : 0;
+    c->last.bwd_frames = frames;
+    c->last.batch_cap = call.batch ? cap : 0;
     a.frames = frames;  // (a rerun after an overflow may take fewer frames: their samples stay where they are)
     a.bwd = c->train.ws;
     a.bwd.cap = cap;
@@ -1260,70 +1211,77 @@ extern "C" int esac_hip_backward(esac_hip_ctx* c, const float* d_sc, float* d_ou
     return 0;
 }
 
+// Where both batched training routes start: the pose arm taken, the call planned (batch_plan.hpp: every check before anything is
+// allocated or launched -- the caller's gradients stay untouched on an error), the context's GPU current, the parameters through
+// make_args once, the table on its way to the device, and what every chunk of the call shares.  Nothing in here waits for the
+// stream; the one wait is stage_cams' on the PREVIOUS call's table copy.
+struct BwdBatchStart {
+    DeviceGuard guard;
+    BatchPlan plan;   // plan.p is the call's parameter block from here on.  A ragged batch: its H x W is the capacity -- the workspaces,
+                      // the chunks (a chunk of small frames could hold more of them; the charge is the safe side and keeps the chunking
+                      // a function of the parameters alone) and every launch are sized by it
+    hipStream_t s;
+    KArgs a;
+    BwdCall call;     // (gt_frames, and the asynchronous route's frame_status and rec_dev, are the body's to set)
+    int N, P, worst;  // worst: the slots a frame can need, min(N, 1000)
+    long long slot_bytes;
+};
+static int begin_bwd_batch(esac_hip_ctx* c, const BwdBatchIn& in, BatchRoute route, BwdBatchStart* st) {
+    const PoseArm arm = take_pose_arm(c);
+    const bool async = route == BATCH_TRAIN_ASYNC;
+    int rc = plan_batch(route, async ? "esac_hip_backward_batch_dev_shapes" : "esac_hip_backward_batch_shapes", c != nullptr,
+                        in.d_sc && in.d_out_gradients && in.d_assign && in.gt_poses, in.out != nullptr, in.p, in.B, in.h_cams, in.shapes,
+                        in.sc_frame_stride, in.grad_frame_stride, &st->plan);
+    if (rc) return rc;
+    if ((rc = check_pose_arm(async ? "esac_hip_backward_batch_dev" : "esac_hip_backward_batch", arm, in.B))) return rc;
+    st->guard.enter(c->device);
+    st->s = (hipStream_t)in.stream;
+    if ((rc = make_args(c, in.d_sc, in.d_assign, &st->plan.p, &st->a, 1, 0, in.h_cams ? 0 : -1, true))) return rc;
+    if (st->plan.stage && (rc = stage_cams(c, st->plan, in.h_cams, in.B, st->s))) return rc;
+    st->call = BwdCall{in.d_out_gradients, in.grad_frame_stride, in.w_loss_rot, in.w_loss_trans, in.loss_cut};
+    st->call.batch = true; st->call.pose_rec = arm.rec;
+    st->N = st->plan.p.N; st->P = st->plan.p.H * st->plan.p.W; st->worst = bwd_rows(st->N);
+    st->slot_bytes = bwd_slot_bytes(st->P, corr_entries(st->P));
+    return 0;
+}
+
 // B independent frames of the training path in one set of launches per chunk (include/esac_hip.h).  Frame b is the b-th of B
 // consecutive esac_hip_backward calls (call p->call + b); its slots are refined with one workgroup each.  The slot workspace of
 // B x cap slots is bounded by the context's budget: beyond it the frames go in chunks of consecutive frames, each with its own
 // launch set (the frames are independent, so the chunking changes no result).  An overflow of the slot workspace in ANY frame
 // of a chunk stops the accumulation of every frame of it (one batch-wide word, BwdArgs::sel_max); the host grows `cap` to the
-// largest frame's count and runs selection .. accumulation of the chunk again, so nothing is added twice.
-extern "C" int esac_hip_backward_batch(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
-                                       int64_t grad_frame_stride, const int64_t* d_assign, const float* h_gt_poses, float w_loss_rot,
-                                       float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* h_out) {
-    return esac_hip_backward_batch_cams(c, B, d_sc, sc_frame_stride, d_out_gradients, grad_frame_stride, d_assign, h_gt_poses, nullptr, w_loss_rot, w_loss_trans, loss_cut, p, stream, h_out);
-}
-
-// ... with a camera per frame (h_cams: host, B records; NULL: the five fields of p for every frame).  Record b0 of a chunk goes
-// into the chunk's inline fields, the table pointer is offset by the chunk's first frame like gt_frames and the call counter.
-// shapes: esac_hip_backward_batch_shapes -- h_cams carries every frame's grid, p's H x W is the capacity (ragged_bwd_entry)
-static int backward_batch_impl(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
-                               int64_t grad_frame_stride, const int64_t* d_assign, const float* h_gt_poses, const esac_hip_frame_cam* h_cams,
-                               float w_loss_rot, float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* h_out, bool shapes) {
-    const PoseArm arm = take_pose_arm(c);
-    const char* const shapes_who = "esac_hip_backward_batch_shapes";
-    // (a ragged batch: the capacity is no bound of the gradient stride -- check_bwd_shapes holds it against every frame's own grid)
-    int rc = check_batch_call("esac_hip_backward_batch", c != nullptr, p, B, d_sc && d_out_gradients && d_assign && h_gt_poses, false, h_out != nullptr, sc_frame_stride,
-                              shapes ? INT64_MAX : grad_frame_stride);
+// largest frame's count and runs selection .. accumulation of the chunk again, so nothing is added twice.  A camera per frame
+// (in.h_cams: host, B records; NULL: p's five fields for every frame): chunk_args puts record b0 of a chunk into its inline fields.
+static int backward_batch_impl(esac_hip_ctx* c, const BwdBatchIn& in) {
+    BwdBatchStart st;
+    int rc = begin_bwd_batch(c, in, BATCH_TRAIN_BLOCKING, &st);
     if (rc) return rc;
-    esac_hip_params p1;
-    if (shapes) {
-        if ((rc = ragged_bwd_entry(shapes_who, true, true, p, B, h_cams, sc_frame_stride, grad_frame_stride, &p1, &shapes))) return rc;
-        if (!shapes) p = &p1;
-    }
-    if ((rc = check_pose_arm("esac_hip_backward_batch", arm, B))) return rc;
-    DeviceGuard guard(c->device);
-    hipStream_t s = (hipStream_t)stream;
+    const hipStream_t s = st.s;
+    KArgs& a = st.a;
+    double* const h_out = in.out;
     if (!c->stage.h_gt) {
         HIP_OK(hipHostMalloc((void**)&c->stage.h_gt, (size_t)ESAC_MAX_BATCH * ESAC_GT_DOUBLES * sizeof(double), hipHostMallocDefault));
         HIP_OK(hipMalloc((void**)&c->stage.d_gt, (size_t)ESAC_MAX_BATCH * ESAC_GT_DOUBLES * sizeof(double)));
     }
     HIP_OK(hipStreamSynchronize(s));  // (the staging buffer is free: a batch that failed half-way may have left its copy queued)
+    const int B = in.B;
     for (int b = 0; b < B; b++) {
         double* g = c->stage.h_gt + (size_t)b * ESAC_GT_DOUBLES;
-        if (!gt_from_pose(h_gt_poses + (size_t)b * 16, g, g + 16))
+        if (!gt_from_pose(in.gt_poses + (size_t)b * 16, g, g + 16))
             return fail(-4, "esac_hip_backward_batch: the ground-truth pose of frame %d is singular", b);
     }
-    // validation of the parameters (make_args) before anything is launched: the caller's gradients stay untouched on an error
-    KArgs a;
-    const esac_hip_params p0 = h_cams ? with_cam(*p, h_cams[0]) : *p;
-    if ((rc = make_args(c, d_sc, d_assign, &p0, &a, 1, 0, h_cams ? 0 : -1, true))) return rc;
-    bool all_vec = true;
-    if (h_cams && (rc = stage_cams(c, &p0, h_cams, B, s, sc_frame_stride, shapes ? &all_vec : nullptr, shapes_who, grad_frame_stride))) return rc;  // (checks every record before the first launch)
-    const int shapes_mode = !shapes ? 0 : all_vec ? 1 : 2;
     HIP_OK(hipMemcpyAsync(c->stage.d_gt, c->stage.h_gt, (size_t)B * ESAC_GT_DOUBLES * sizeof(double), hipMemcpyHostToDevice, s));
-    BwdCall call = {d_out_gradients, grad_frame_stride, w_loss_rot, w_loss_trans, loss_cut};
-    call.gt_frames = c->stage.d_gt; call.batch = true; call.pose_rec = arm.rec;
-    const int N = p->N, P = p->H * p->W, worst = bwd_rows(N);
-    int cap = start_cap(true, c->train.cap_batch, worst);
-    const long long slot_bytes = bwd_slot_bytes(P, corr_entries(P));
+    st.call.gt_frames = c->stage.d_gt;
+    int cap = start_cap(true, c->train.cap_batch, st.worst);
     bool any_bad = false;
     for (int b0 = 0; b0 < B;) {
-        int nb = chunk_frames(c->train.budget, cap, slot_bytes, B - b0);
-        if ((rc = chunk_args(c, d_sc, sc_frame_stride, d_assign, p, h_cams, b0, nb, &a, shapes_mode))) return rc;
+        int nb = chunk_frames(c->train.budget, cap, st.slot_bytes, B - b0);
+        if ((rc = chunk_args(c, in, st.plan, b0, nb, &a))) return rc;
         if ((rc = enqueue_bwd_sampling(c, a, s, true))) return rc;
         for (int attempt = 0;; attempt++) {
-            if ((rc = ensure_bws(c, N, P, cap, nb))) return rc;
+            if ((rc = ensure_bws(c, st.N, st.P, cap, nb))) return rc;
             if (cap > c->train.cap_batch) c->train.cap_batch = cap;
-            fill_bwd(c, a, call, b0, nb, cap, false);
+            fill_bwd(c, a, st.call, b0, nb, cap, false);
             if ((rc = enqueue_bwd_chain(c, a, s, c->pin.d))) return rc;  // one pinned slot per frame of the chunk
             if ((rc = wait_record(c, s, nb, a.epoch, "esac_hip_backward_batch: the accumulation kernel"))) return rc;
             __sync_synchronize();
@@ -1333,8 +1291,8 @@ static int backward_batch_impl(esac_hip_ctx* c, int B, const float* d_sc, int64_
                 for (int b = 0; b < nb; b++) c->pin.copy_out(b, h_out + (size_t)(b0 + b) * 4, 4);
                 break;
             }
-            cap = grown_cap(needed, worst);
-            const int fit = chunk_frames(c->train.budget, cap, slot_bytes, nb);
+            cap = grown_cap(needed, st.worst);
+            const int fit = chunk_frames(c->train.budget, cap, st.slot_bytes, nb);
             nb = fit < nb ? fit : nb;
             a.epoch = c->epoch += 1.0;
         }
@@ -1343,91 +1301,69 @@ static int backward_batch_impl(esac_hip_ctx* c, int B, const float* d_sc, int64_
     }
     if (any_bad)
         return fail(-10, "hypAssignment holds a value outside [0,%d) in at least one frame (h_out[b*4+3] = 1 names them; such "
-                         "hypotheses were scored against expert 0)", p->E);
+                         "hypotheses were scored against expert 0)", st.plan.p.E);
     return 0;
+}
+extern "C" int esac_hip_backward_batch(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
+                                       int64_t grad_frame_stride, const int64_t* d_assign, const float* h_gt_poses, float w_loss_rot,
+                                       float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* h_out) {
+    return backward_batch_impl(c, BwdBatchIn{B, d_sc, sc_frame_stride, d_out_gradients, grad_frame_stride, d_assign, h_gt_poses, nullptr, w_loss_rot, w_loss_trans, loss_cut, p, stream, h_out, false});
 }
 extern "C" int esac_hip_backward_batch_cams(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
                                             int64_t grad_frame_stride, const int64_t* d_assign, const float* h_gt_poses, const esac_hip_frame_cam* h_cams,
                                             float w_loss_rot, float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* h_out) {
-    return backward_batch_impl(c, B, d_sc, sc_frame_stride, d_out_gradients, grad_frame_stride, d_assign, h_gt_poses, h_cams, w_loss_rot, w_loss_trans, loss_cut, p, stream, h_out, false);
+    return backward_batch_impl(c, BwdBatchIn{B, d_sc, sc_frame_stride, d_out_gradients, grad_frame_stride, d_assign, h_gt_poses, h_cams, w_loss_rot, w_loss_trans, loss_cut, p, stream, h_out, false});
 }
 // Frames that differ in image size (include/esac_hip.h): frame b's grid in h_cams[b].reserved[0..1], its maps and its gradients
 // dense at the head of their slots; p->H * p->W is the capacity in cells.
 extern "C" int esac_hip_backward_batch_shapes(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
                                               int64_t grad_frame_stride, const int64_t* d_assign, const float* h_gt_poses, const esac_hip_frame_cam* h_cams,
                                               float w_loss_rot, float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* h_out) {
-    return backward_batch_impl(c, B, d_sc, sc_frame_stride, d_out_gradients, grad_frame_stride, d_assign, h_gt_poses, h_cams, w_loss_rot, w_loss_trans, loss_cut, p, stream, h_out, true);
+    return backward_batch_impl(c, BwdBatchIn{B, d_sc, sc_frame_stride, d_out_gradients, grad_frame_stride, d_assign, h_gt_poses, h_cams, w_loss_rot, w_loss_trans, loss_cut, p, stream, h_out, true});
 }
 
 // The asynchronous batch (include/esac_hip.h): ground truth, records and per-frame outcomes stay on the device, the host enqueues
-// and returns.  Nothing in here waits for the stream -- the one wait is stage_cams' on the PREVIOUS call's table copy -- and
-// nothing is run twice: every frame owns the worst-case min(N, 1000) slots, so no selection can overflow, and the frames go in
-// chunks of consecutive frames sized by that worst case, one launch set after the other on the stream (which serialises their
-// use of the workspace).  A workspace that has to grow is grown before the first launch (ensure_ws / ensure_bws: one device
-// synchronisation, on the first call of a shape only).
-// (esac_hip_backward_batch_dev_shapes is this function behind a one-shot mark on the context, taken here like the pose arm: the
-// asynchronous route keeps ONE body, which tests/test_backward_batch_async_api.py reads from this signature to its closing brace)
-extern "C" int esac_hip_backward_batch_dev(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
-                                           int64_t grad_frame_stride, const int64_t* d_assign, const float* d_gt_poses, const esac_hip_frame_cam* h_cams,
-                                           float w_loss_rot, float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* d_out) {
-    const PoseArm arm = take_pose_arm(c);
-    bool shapes = c && c->stage.shapes_next;  // h_cams carries every frame's grid, p's H x W is the capacity (ragged_bwd_entry)
-    if (c) c->stage.shapes_next = false;
-    const char* const shapes_who = "esac_hip_backward_batch_dev_shapes";
-    int rc = check_batch_call("esac_hip_backward_batch", c != nullptr, p, B, d_sc && d_out_gradients && d_assign && d_gt_poses, true, d_out != nullptr, sc_frame_stride,
-                              shapes ? INT64_MAX : grad_frame_stride);
+// and returns.  Nothing in here or in begin_bwd_batch waits for the stream, and nothing is run twice: every frame owns the worst-case
+// min(N, 1000) slots, so no selection can overflow, and the frames go in chunks of consecutive frames sized by that worst case, one
+// launch set after the other on the stream (which serialises their use of the workspace).  A workspace that has to grow is grown
+// before the first launch (ensure_ws / ensure_bws: one device synchronisation, on the first call of a shape only).
+static int backward_batch_dev_impl(esac_hip_ctx* c, const BwdBatchIn& in) {
+    BwdBatchStart st;
+    int rc = begin_bwd_batch(c, in, BATCH_TRAIN_ASYNC, &st);
     if (rc) return rc;
-    esac_hip_params p1;
-    if (shapes) {
-        if ((rc = ragged_bwd_entry(shapes_who, true, true, p, B, h_cams, sc_frame_stride, grad_frame_stride, &p1, &shapes))) return rc;
-        if (!shapes) p = &p1;
-    }
-    if ((rc = check_pose_arm("esac_hip_backward_batch_dev", arm, B))) return rc;
     // the chunking is known before anything is launched: cap is the worst case, so the first chunk is the largest
-    const int N = p->N, P = p->H * p->W, cap = bwd_rows(N);
-    const long long slot_bytes = bwd_slot_bytes(P, corr_entries(P));
-    if ((rc = check_async_budget(c->train.budget, cap, slot_bytes))) return rc;
-    const int chunk = chunk_frames(c->train.budget, cap, slot_bytes, B);
-    DeviceGuard guard(c->device);
-    hipStream_t s = (hipStream_t)stream;
+    const int B = in.B, cap = st.worst;
+    if ((rc = check_async_budget(c->train.budget, cap, st.slot_bytes))) return rc;
+    const int chunk = chunk_frames(c->train.budget, cap, st.slot_bytes, B);
     if (!c->stage.d_gt_dev) {
         HIP_OK(hipMalloc((void**)&c->stage.d_gt_dev, (size_t)ESAC_MAX_BATCH * ESAC_GT_DOUBLES * sizeof(double)));
         HIP_OK(hipMalloc((void**)&c->stage.d_frame_status, (size_t)ESAC_MAX_BATCH * sizeof(int)));
     }
-    // validation of the parameters and of every camera record, and the workspaces of the largest chunk, before anything is
-    // launched: the caller's gradients stay untouched on an error
-    KArgs a;
-    const esac_hip_params p0 = h_cams ? with_cam(*p, h_cams[0]) : *p;
-    if ((rc = make_args(c, d_sc, d_assign, &p0, &a, chunk, sc_frame_stride, h_cams ? 0 : -1, true))) return rc;
-    if ((rc = ensure_bws(c, N, P, cap, chunk))) return rc;
-    bool all_vec = true;
-    if (h_cams && (rc = stage_cams(c, &p0, h_cams, B, s, sc_frame_stride, shapes ? &all_vec : nullptr, shapes_who, grad_frame_stride))) return rc;  // (checks every record before the first launch)
-    const int shapes_mode = !shapes ? 0 : all_vec ? 1 : 2;
-    launch_bwd_gt_prepare(d_gt_poses, B, c->stage.d_gt_dev, c->stage.d_frame_status, s);
+    if ((rc = ensure_ws(c, st.N, st.P, chunk))) return rc;  // the workspaces of the largest chunk
+    if ((rc = ensure_bws(c, st.N, st.P, cap, chunk))) return rc;
+    launch_bwd_gt_prepare(in.gt_poses, B, c->stage.d_gt_dev, c->stage.d_frame_status, st.s);
     if ((rc = check_launch("k_bwd_gt_prepare"))) return rc;
-    BwdCall call = {d_out_gradients, grad_frame_stride, w_loss_rot, w_loss_trans, loss_cut};
-    call.gt_frames = c->stage.d_gt_dev; call.batch = true; call.pose_rec = arm.rec;
-    call.frame_status = c->stage.d_frame_status; call.rec_dev = d_out;
+    st.call.gt_frames = c->stage.d_gt_dev; st.call.frame_status = c->stage.d_frame_status; st.call.rec_dev = in.out;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = B - b0 < chunk ? B - b0 : chunk;
-        if ((rc = chunk_args(c, d_sc, sc_frame_stride, d_assign, p, h_cams, b0, nb, &a, shapes_mode))) return rc;
-        if ((rc = enqueue_bwd_sampling(c, a, s, true))) return rc;
-        fill_bwd(c, a, call, b0, nb, cap, false);  // (the slot workspace was sized for the largest chunk above)
-        if ((rc = enqueue_bwd_chain(c, a, s, nullptr))) return rc;  // k_bwd_loss writes frame b's record into d_out[b*4..]
+        if ((rc = chunk_args(c, in, st.plan, b0, nb, &st.a))) return rc;
+        if ((rc = enqueue_bwd_sampling(c, st.a, st.s, true))) return rc;
+        fill_bwd(c, st.a, st.call, b0, nb, cap, false);  // (the slot workspace was sized for the largest chunk above)
+        if ((rc = enqueue_bwd_chain(c, st.a, st.s, nullptr))) return rc;  // k_bwd_loss writes frame b's record into d_out[b*4..]
     }
-    c->train.last_dev_batch = B;
+    c->last.dev_batch = B;
     return 0;
+}
+extern "C" int esac_hip_backward_batch_dev(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
+                                           int64_t grad_frame_stride, const int64_t* d_assign, const float* d_gt_poses, const esac_hip_frame_cam* h_cams,
+                                           float w_loss_rot, float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* d_out) {
+    return backward_batch_dev_impl(c, BwdBatchIn{B, d_sc, sc_frame_stride, d_out_gradients, grad_frame_stride, d_assign, d_gt_poses, h_cams, w_loss_rot, w_loss_trans, loss_cut, p, stream, d_out, false});
 }
 // ... of frames that differ in image size (esac_hip_backward_batch_shapes without a host inside the call)
 extern "C" int esac_hip_backward_batch_dev_shapes(esac_hip_ctx* c, int B, const float* d_sc, int64_t sc_frame_stride, float* d_out_gradients,
                                                   int64_t grad_frame_stride, const int64_t* d_assign, const float* d_gt_poses, const esac_hip_frame_cam* h_cams,
                                                   float w_loss_rot, float w_loss_trans, float loss_cut, const esac_hip_params* p, void* stream, double* d_out) {
-    if (int rc = check_bwd_shapes_entry("esac_hip_backward_batch_dev_shapes", h_cams != nullptr)) {
-        (void)take_pose_arm(c);  // (one-shot: taken by the call whether it runs or not)
-        return rc;
-    }
-    if (c) c->stage.shapes_next = true;
-    return esac_hip_backward_batch_dev(c, B, d_sc, sc_frame_stride, d_out_gradients, grad_frame_stride, d_assign, d_gt_poses, h_cams, w_loss_rot, w_loss_trans, loss_cut, p, stream, d_out);
+    return backward_batch_dev_impl(c, BwdBatchIn{B, d_sc, sc_frame_stride, d_out_gradients, grad_frame_stride, d_assign, d_gt_poses, h_cams, w_loss_rot, w_loss_trans, loss_cut, p, stream, d_out, true});
 }
 
 // Asynchronous calls (no host result) cannot report an out-of-range hypAssignment themselves: this waits for the
@@ -1450,9 +1386,9 @@ extern "C" int esac_hip_check(esac_hip_ctx* c) {
         }
         return fail(-12, "the cooperating refinement workgroups of the most recent call could not synchronise (not all of them became resident)");
     }
-    if (c->train.last_dev_batch > 0) {  // esac_hip_backward_batch_dev was the most recent call: its per-frame outcomes
+    if (c->last.dev_batch > 0) {  // esac_hip_backward_batch_dev was the most recent call: its per-frame outcomes
         static thread_local int words[ESAC_MAX_BATCH];
-        const int B = c->train.last_dev_batch;
+        const int B = c->last.dev_batch;
         HIP_OK(hipMemcpy(words, c->stage.d_frame_status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
         for (int b = 0; b < B; b++)
             if (words[b] == 2) return fail(-4, "esac_hip_backward_batch_dev: the ground-truth pose of frame %d is singular", b);
@@ -1500,7 +1436,7 @@ extern "C" int esac_hip_set_wait(esac_hip_ctx* c, int mode) {
 extern "C" int esac_hip_read(esac_hip_ctx* c, int which, void* h_dst, size_t bytes) {
     if (!c || !h_dst) return fail(-1, "esac_hip_read: null argument");
     DeviceGuard guard(c->device);
-    const size_t P = (size_t)c->lastH * c->lastW;
+    const size_t P = (size_t)c->last.H * c->last.W;
     const void* src = nullptr;
     switch (which) {
 #define ESAC_READ_SRC(id, member, elem, count, frames) case id: src = c->member; break;
@@ -1514,8 +1450,9 @@ extern "C" int esac_hip_read(esac_hip_ctx* c, int which, void* h_dst, size_t byt
     // slots the slab workspace holds (>= the slots of the last call); after a batch, frame 0's slabs: its per-frame cap
     // (after a ragged training batch the slabs and slot maps of frame 0 are read in units of that frame's own cells: its slots lie there)
     const bool slot_read = which == ESAC_BUF_BWD_PATH1 || which == ESAC_BUF_BWD_PATH2 || which == ESAC_BUF_BWD_MAPS;
-    const ReadDims dims = {(size_t)c->lastN, slot_read && c->train.last_slot_cells ? c->train.last_slot_cells : P, (size_t)bwd_rows(c->lastN), c->lastB, c->train.last_frames,
-                           c->train.last_batch_cap > 0 ? (size_t)c->train.last_batch_cap : (size_t)c->train.slots, c->keep_errs};
+    const LastCall& last = c->last;
+    const ReadDims dims = {(size_t)last.N, slot_read && last.slot_cells ? last.slot_cells : P, (size_t)bwd_rows(last.N), last.B, last.bwd_frames,
+                           last.batch_cap > 0 ? (size_t)last.batch_cap : (size_t)c->train.slots, c->keep_errs};
     size_t want = 0;
     if (int rc = read_size(which, bytes, src != nullptr, dims, &want)) return rc;
     switch (which) {
@@ -1529,8 +1466,8 @@ extern "C" int esac_hip_read(esac_hip_ctx* c, int which, void* h_dst, size_t byt
                 memset(h_dst, 0, P);
                 return 0;
             }
-            // (after a ragged batch the P bytes are frame 0's slot view: its map is the first h_0 * w_0 of them; last_map1 + P <= 2 P)
-            HIP_OK(hipMemcpy(h_dst, c->ws.inlier_map + (which_buf > 0.5 ? c->last_map1 : 0), P, hipMemcpyDeviceToHost));
+            // (after a ragged batch the P bytes are frame 0's slot view: its map is the first h_0 * w_0 of them; last.map1 + P <= 2 P)
+            HIP_OK(hipMemcpy(h_dst, c->ws.inlier_map + (which_buf > 0.5 ? c->last.map1 : 0), P, hipMemcpyDeviceToHost));
             return 0;
         }
         case ESAC_BUF_BWD_TEAM_INFO: {
@@ -1572,7 +1509,7 @@ extern "C" int esac_hip_write_hyps(esac_hip_ctx* c, const double* h_hyps, int N)
     // the fp32 [R | t] rows of the streaming score are relative to each expert map's origin (device_common.hpp:
     // map_centre): they are rebuilt by the next esac_hip_score, which knows the maps
     c->rt32_stale = true;
-    c->lastN = N;
+    c->last.N = N;
     return 0;
 }
 

@@ -1,9 +1,9 @@
 // ragged_policy.hpp -- the C ABI host's checks of a RAGGED batch (esac_hip_forward_batch_shapes: frames that differ in image size)
 // and the per-frame record its kernels read.  Part of call_policy.hpp (which includes it at its end: plain C++ over
 // include/esac_hip.h, no HIP header); a file of its own because tests/test_call_policy_host.py holds every message of
-// call_policy.hpp against a recording that predates this entry point -- tests/native/ragged_policy_probe.cpp reads this one.
-// The checks of a ragged TRAINING batch (esac_hip_backward_batch_shapes, _dev_shapes) are at its end; tests/native/
-// ragged_backward_policy_probe.cpp reads those.
+// call_policy.hpp against a recording that predates this entry point.  The checks of a ragged TRAINING batch
+// (esac_hip_backward_batch_shapes, _dev_shapes) are at its end.  batch_plan.hpp (plan_batch) is their one caller and sets their
+// order; the host and tests/native/ragged_policy_probe.cpp, ragged_backward_policy_probe.cpp reach them through it.
 #pragma once
 #include "call_policy.hpp"
 
@@ -43,8 +43,8 @@ inline esac_hip_frame_cam shape_record(const esac_hip_params* p, const esac_hip_
 }
 
 // ---------------------------------------------------------------- ragged TRAINING batches
-// esac_hip_backward_batch_shapes / esac_hip_backward_batch_dev_shapes (who): the table is required, and checked like a forward
-// table; then the gradient slots.  Frame b's gradients are the dense [E,3,h_b,w_b] tensor at d_out_gradients + b *
+// esac_hip_backward_batch_shapes / esac_hip_backward_batch_dev_shapes (who): the table is required (check_bwd_shapes_entry: the
+// first check of every ragged route, forward included), and checked like a forward table; then the gradient slots.  Frame b's gradients are the dense [E,3,h_b,w_b] tensor at d_out_gradients + b *
 // grad_frame_stride, so with B > 1 every frame's 3*E*h_b*w_b floats must fit the stride -- the first frame that does not is
 // named, and the stride is then >= 3*E*max(h_b*w_b): no two frames share an element.  (One frame has no stride to fit.)  The
 // capacity H*W plays no part: it may exceed the largest frame, and a gradient slot need not hold it.

@@ -1,7 +1,9 @@
-// ragged_policy_probe.cpp -- stand-alone host program over esac_amd/csrc/ragged_policy.hpp (no HIP header, no GPU): the checks of
-// a ragged batch (check_shapes) and the per-frame re-score margin (shape_record) as tests/test_ragged_policy_host.py drives them.
+// ragged_policy_probe.cpp -- stand-alone host program over esac_amd/csrc/batch_plan.hpp and ragged_policy.hpp (no HIP header, no
+// GPU): the forward route's plan of a ragged batch (plan_batch: the function the C ABI host calls, so the order of checks is the
+// library's) and the per-frame re-score margin (shape_record) as tests/test_ragged_policy_host.py drives them.
 // One request per input line, one answer per output line:
 //   check E H W sub stride B  {shift_x shift_y focal h w} x B   ->  check|<status>|<all_vec or -1>|<message>
+//       (all_vec: KArgs::shapes == 1; of one frame, which the plan hands to the single call: that call's width is a multiple of 4)
 //   margin alpha rescore_margin H W h w                         ->  margin|<bits of the frame's record>|<bits of call_scalars on h x w>
 #include <inttypes.h>
 #include <stdio.h>
@@ -11,7 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "../../esac_amd/csrc/ragged_policy.hpp"
+#include "../../esac_amd/csrc/batch_plan.hpp"
 
 using namespace esac;
 
@@ -36,7 +38,8 @@ int main() {
             int E, H, W, sub, B;
             long long stride;
             in >> E >> H >> W >> sub >> stride >> B;
-            std::vector<esac_hip_frame_cam> cams((size_t)B);
+            std::vector<esac_hip_frame_cam> cams((size_t)(B > 0 ? B : 0));
+            cams.reserve(1);  // (B = 0: still a table)
             for (auto& c : cams) {
                 memset(&c, 0, sizeof(c));
                 in >> c.shift_x >> c.shift_y >> c.focal >> c.reserved[0] >> c.reserved[1];
@@ -46,9 +49,9 @@ int main() {
             if (!in) { printf("check|bad row\n"); continue; }
             const esac_hip_params p = params(E, H, W, sub);
             g_err[0] = 0;
-            bool all_vec = false;
-            int rc = check_args(true, true, &p, B, -1, false);
-            if (!rc) rc = check_shapes(&p, B, cams.data(), (int64_t)stride, &all_vec);
+            BatchPlan plan;
+            const int rc = plan_batch(BATCH_FORWARD, "esac_hip_forward_batch_shapes", true, true, true, &p, B, cams.data(), true, (int64_t)stride, 0, &plan);
+            const bool all_vec = plan.shapes ? plan.shapes == 1 : (plan.p.W & 3) == 0;
             printf("check|%d|%d|%s\n", rc, rc ? -1 : (int)all_vec, rc ? g_err : "");
         } else if (kind == "margin") {
             float alpha, rescore;

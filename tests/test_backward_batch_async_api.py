@@ -31,22 +31,32 @@ def test_the_abi_version_is_still_6():
 
 
 def test_the_call_path_holds_no_host_wait():
-    """esac_hip_backward_batch_dev and the helpers on its launch path (the chunk prologue, the sampling prologue, the fill of
-    a.bwd and the selection .. accumulation chain, each from its signature to its closing brace): no stream synchronisation, no
-    blocking copy, no polling of a pinned record, and no second pass.  The accumulation is launched from one place in the file,
-    so no entry point has a chain of its own beside the shared one."""
+    """The one body behind esac_hip_backward_batch_dev and esac_hip_backward_batch_dev_shapes, the prologue it shares with the
+    blocking batch, and the helpers on its launch path (the chunk prologue, the sampling prologue, the fill of a.bwd and the
+    selection .. accumulation chain, each from its signature to its closing brace): no stream synchronisation, no blocking copy,
+    no polling of a pinned record, and no second pass.  The accumulation is launched from one place in the file, so no entry
+    point has a chain of its own beside the shared one; both entry points call that one body with all they were given, and
+    nothing reaches it through the context."""
     with open(os.path.join(ROOT, "esac_amd", "csrc", "esac_capi.hip")) as fh:
         text = fh.read()
     bodies = []
-    for signature in ('extern "C" int esac_hip_backward_batch_dev(', "static int chunk_args(", "static int enqueue_bwd_sampling(",
-                      "static void fill_bwd(", "static int enqueue_bwd_chain("):
+
+    def body_of(signature):
         assert text.count(signature) == 1, signature
         start = text.index(signature)
-        bodies.append(text[start:text.index("\n}\n", start) + 3])
+        return text[start:text.index("\n}\n", start) + 3]
+
+    for signature in ("static int backward_batch_dev_impl(", "static int begin_bwd_batch(", "static int chunk_args(",
+                      "static int enqueue_bwd_sampling(", "static void fill_bwd(", "static int enqueue_bwd_chain("):
+        bodies.append(body_of(signature))
         assert bodies[-1].count("\n") > 5, signature  # (a body, not a declaration)
     dev = bodies[0]
-    for helper in ("chunk_args(", "enqueue_bwd_sampling(", "fill_bwd(", "enqueue_bwd_chain("):
+    for helper in ("begin_bwd_batch(", "chunk_args(", "enqueue_bwd_sampling(", "fill_bwd(", "enqueue_bwd_chain("):
         assert helper in dev, helper
+    for entry in ('extern "C" int esac_hip_backward_batch_dev(', 'extern "C" int esac_hip_backward_batch_dev_shapes('):
+        wrapper = body_of(entry)
+        assert wrapper.count("return backward_batch_dev_impl(c, BwdBatchIn{") == 1 and wrapper.count(";") == 1, wrapper
+    assert "shapes_next" not in text
     body = "\n".join(bodies)
     assert "launch_bwd_accumulate" in body and "launch_bwd_gt_prepare" in body
     for word in ("hipStreamSynchronize", "hipDeviceSynchronize", "hipMemcpy(", "wait_record", "hipEventSynchronize", "attempt"):

@@ -103,7 +103,7 @@ def _run_ragged(eng, frames, has, gts, g0, alpha=ALPHA, call0=CALL0, asynchronou
     tails = {k: kw.pop(k) for k in ("map_tail", "grad_tail", "grad_stride") if k in kw}
     held = kw.pop("frames_held", B)  # frames of the last chunk: what the per-frame buffers hold afterwards
     packed, grads, shapes = _pack(eng, frames, g0, **tails)
-    H, W = api.capacity_shape(shapes)
+    H, W = kw.pop("capacity", None) or api.capacity_shape(shapes)  # (a capacity of the caller's own may exceed every frame)
     p = _table_params(eng, experts, H, W, n, alpha, call0, **kw)
     ha = torch.from_numpy(np.stack(has)).to(eng.device)
     if asynchronous:
@@ -238,6 +238,34 @@ def test_uniform_table_is_backward_batch_cams_bit_for_bit(solo, shape):
     np.testing.assert_array_equal(one["grads"][0], new["grads"][0])
 
 
+def _run_single(eng, f, ha, gt, g0, call, n):
+    """`backward_device` on one frame's dense tensors: (record [4], gradients [E,3,h,w])."""
+    g = torch.from_numpy(g0.copy()).to(eng.device)
+    out = eng.backward_device(torch.from_numpy(f["coords"]).to(eng.device), g, torch.from_numpy(ha).to(eng.device), gt, *LOSS,
+                              _frame_params(eng, f, n, ALPHA, call))
+    return out, g.cpu().numpy()
+
+
+@pytest.mark.parametrize("asynchronous", [False, True], ids=["blocking", "async"])
+def test_one_ragged_frame_is_the_single_backward_on_its_grid(solo, asynchronous):
+    """B = 1 under a capacity larger than the frame (12x18 over 9x14): the host hands the call to the shared-shape route on the
+    frame's OWN grid.  14 is no multiple of 4 -- a call that kept the ragged mode of such a table, or the capacity's row
+    length, would not give the single call's bits.  (test_uniform_table_is_backward_batch_cams_bit_for_bit holds B = 1 against
+    backward_batch at the capacity's own shape, blocking only.)"""
+    n = 16
+    frames, has, gts = _inputs([(9, 14)], experts=1, n=n, first=975)  # (the oracle selects 12 of the 16, none near the threshold)
+    g0 = _g0(frames, seed=14)
+    got = _run_ragged(solo, frames, has, gts, g0, call0=600, asynchronous=asynchronous, capacity=(12, 18))
+    _conditions(got, g0)
+    want_out, want_g = _run_single(solo, frames[0], has[0], gts[0], g0[0], 600, n)
+    print("record: ragged", got["out"][0], "single", want_out, "max |gradient difference|", np.abs(got["grads"][0] - want_g).max())
+    np.testing.assert_array_equal(got["out"][0], want_out)
+    assert got["grads"][0].shape == (1, 3, 9, 14)
+    np.testing.assert_array_equal(got["grads"][0], want_g)
+    for which in FRAME_BUFS:
+        np.testing.assert_array_equal(got[which][0], solo.read(which), err_msg="buffer %d" % which)
+
+
 # ---------------------------------------------------------------- 4. slot tails are untouched
 def test_slot_tails_are_neither_read_nor_written(solo, mixed):
     SENTINEL = -4242.5
@@ -276,6 +304,48 @@ def test_chunks_of_two_equal_one_chunk(solo, monkeypatch):
         np.testing.assert_array_equal(got["grads"][b], whole["grads"][b], err_msg="frame %d" % b)
     for which in FRAME_BUFS:  # the last chunk's frame 0 is the batch's frame 4: its table pointer and counter moved with the chunk
         np.testing.assert_array_equal(got[which][0], whole[which][4])
+
+
+def test_slot_reads_after_a_chunked_batch_are_the_last_chunks_frame_0(solo, monkeypatch):
+    """esac_hip_read of the slot maps and the slabs after a batch that went in chunks: the slots of the LAST chunk's frame 0 (here
+    the batch's frame 2, 12x18) in that frame's own 216 cells -- not the batch's frame 0 (192 cells), not the capacity (234).
+    A slot is charged 50 P bytes at the capacity P = 13 * 18, a fresh context starts with 64 slots per frame: 2 MiB hold two
+    frames and not three, so B = 3 goes as 2 + 1.  The yardstick is the single call on frame 2, whose bits the batch gives."""
+    shapes = [(12, 16), (9, 14), (12, 18)]
+    per_frame = 50 * 234 * 64
+    assert 2 * per_frame <= 2 << 20 < 3 * per_frame
+    frames, has, gts = _inputs(shapes, first=980)  # (the oracle selects 40, 37 and 30 of the 64: no overflow rerun)
+    g0 = _g0(frames, seed=15)
+    monkeypatch.setenv("ESAC_BWD_BATCH_BUDGET_MB", "2")
+    monkeypatch.setenv("ESAC_SLOT_TEAMS", "0")
+    small = api.Engine(0)
+    got = _run_ragged(small, frames, has, gts, g0, call0=500, frames_held=1, capacity=(13, 18))
+    _conditions(got, g0)
+    with pytest.raises(RuntimeError):
+        small.read_frames(api.BUF_BWD_PROBS, 2)  # the last chunk holds ONE frame
+    k = int(got["out"][2][1])
+    assert 1 <= k <= 64
+    info = small.read_frames(api.BUF_BWD_SLOT_INFO, 1)[0][:k]
+    maps = small.read_maps(k, shape=shapes[2])
+    slabs = [small.read_slabs(w, k, shape=shapes[2]) for w in (api.BUF_BWD_PATH1, api.BUF_BWD_PATH2)]
+    for other in (shapes[0], (13, 18)):  # a slot is 2 * 216 bytes: one slot in the batch's frame 0's unit, or the capacity's, is refused
+        with pytest.raises(RuntimeError, match="whole slots of 432 bytes"):
+            small.read_maps(1, shape=other)
+    want_out, want_g = _run_single(solo, frames[2], has[2], gts[2], g0[2], 502, N)
+    np.testing.assert_array_equal(got["out"][2], want_out)
+    np.testing.assert_array_equal(got["grads"][2], want_g)
+    want_info = solo.read(api.BUF_BWD_SLOT_INFO)[:k]
+    want_maps = solo.read_maps(k)
+    print("slots", k, "accepted maps", int((info[:, 0] >= 0).sum()), "inliers", info[:, 1].tolist())
+    np.testing.assert_array_equal(info, want_info)
+    assert (info[:, 0] >= 0).sum() >= 1
+    for s in range(k):
+        if info[s, 0] >= 0:  # (the other buffer of a slot holds an earlier iteration's set, or an earlier call's)
+            np.testing.assert_array_equal(maps[s, info[s, 0]], want_maps[s, info[s, 0]], err_msg="slot %d" % s)
+            assert maps[s, info[s, 0]].any(), s
+    for w, have in zip((api.BUF_BWD_PATH1, api.BUF_BWD_PATH2), slabs):
+        np.testing.assert_array_equal(have, solo.read_slabs(w, k), err_msg="slabs %d" % w)
+        assert np.abs(have).max() > 0
 
 
 # ---------------------------------------------------------------- 6. overflow rerun

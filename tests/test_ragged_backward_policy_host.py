@@ -1,7 +1,10 @@
 """The host's decisions about a ragged TRAINING batch (esac_hip_backward_batch_shapes / esac_hip_backward_batch_dev_shapes;
 esac_amd/csrc/ragged_policy.hpp) through a stand-alone host program -- tests/native/ragged_backward_policy_probe.cpp, built with
 the host compiler under AddressSanitizer and UBSan, its own process, no GPU: every new fail() message, the gradient-slot check
-on both sides of its bound (held against every frame's OWN grid, never the capacity), and the chunking by the capacity's slot."""
+on both sides of its bound (held against every frame's OWN grid, never the capacity), and the chunking by the capacity's slot.
+The probe calls plan_batch (esac_amd/csrc/batch_plan.hpp), the function the library's three batch routes call: the order of the
+checks is the library's, and what the plan hands on (parameter block, staging, KArgs::shapes, frame 0's cells, the records) is held
+here too."""
 import os
 import re
 import subprocess
@@ -12,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "ragged_backward_policy_probe.cpp")
 EXE = os.path.join(HERE, "native", "ragged_backward_policy_probe_san")
 POLICY = os.path.join(HERE, "..", "esac_amd", "csrc", "ragged_policy.hpp")
-DEPS = [SRC, POLICY, os.path.join(HERE, "..", "esac_amd", "csrc", "call_policy.hpp"), os.path.join(HERE, "..", "include", "esac_hip.h")]
+DEPS = [SRC, POLICY, os.path.join(HERE, "..", "esac_amd", "csrc", "batch_plan.hpp"), os.path.join(HERE, "..", "esac_amd", "csrc", "call_policy.hpp"), os.path.join(HERE, "..", "include", "esac_hip.h")]
 BLOCKING, ASYNC = "esac_hip_backward_batch_shapes", "esac_hip_backward_batch_dev_shapes"
 
 
@@ -111,3 +114,71 @@ def test_chunks_are_sized_by_the_capacity(probe):
     assert [int(r[1]) for r in rows] == [2, 1, 1, 5, 2]
     assert int(rows[0][2]) == slot
     assert int(rows[4][2]) == 2 * 8448 + 48 * 8448 + 16 * 10240  # 8448 cells: 5 trips of 2048 -> a list of 10240 entries
+
+
+FORWARD, TRAIN, TRAIN_ASYNC = 0, 1, 2
+
+
+def _plan(route, ragged, E, H, W, sc_stride, grad_stride, frames, table=1, sub=8):
+    return "plan %d %d %d %d %d %d %d %d %d %d " % (route, ragged, table, E, H, W, sub, sc_stride, grad_stride, len(frames)) + \
+        " ".join("%d %d %r %d %d" % f for f in frames)
+
+
+SAME = [F(12, 18), F(12, 18), F(12, 18)]
+# (request, status, (stage, shapes, H, W, frame 0's cells) or what the message must contain)
+PLAN_CASES = [
+    # a ragged call of ONE frame is the single call on that frame's grid: its H x W in the block, shapes 0 (a width that is no
+    # multiple of 4 must not leave mode 2 set), no frame-0 cells; the forward route has record 0 inline and stages nothing
+    (_plan(FORWARD, 1, 1, 12, 18, 648, 0, [F(9, 14)]), 0, (0, 0, 9, 14, 0)),
+    (_plan(TRAIN, 1, 1, 12, 18, 648, 0, [F(9, 14)]), 0, (1, 0, 9, 14, 0)),
+    (_plan(TRAIN_ASYNC, 1, 1, 12, 18, 648, 0, [F(9, 14)]), 0, (1, 0, 9, 14, 0)),
+    # shapes over the WHOLE table: 1 when every width is a multiple of 4, 2 when any is not; the block keeps the capacity
+    (_plan(TRAIN, 1, 3, 12, 18, 1944, 1944, [F(12, 16), F(16, 12)]), 0, (1, 1, 12, 18, 192)),
+    (_plan(TRAIN_ASYNC, 1, 3, 12, 18, 1944, 1944, MIXED), 0, (1, 2, 12, 18, 192)),
+    (_plan(TRAIN, 1, 3, 12, 18, 1944, 1944, [F(12, 16), F(16, 12), F(12, 16), F(9, 14)]), 0, (1, 2, 12, 18, 192)),  # the last width alone
+    (_plan(FORWARD, 1, 3, 12, 18, 1944, 0, [F(9, 14), F(12, 16)]), 0, (1, 2, 12, 18, 126)),  # frame 0's OWN cells
+    (_plan(FORWARD, 1, 3, 12, 18, 1944, 0, [F(16, 12), F(12, 16)]), 0, (1, 1, 12, 18, 192)),
+    # a shared-shape table: staged as it is (forward: from two frames on), no mode, no cells
+    (_plan(FORWARD, 0, 3, 12, 18, 1944, 0, SAME), 0, (1, 0, 12, 18, 0)),
+    (_plan(FORWARD, 0, 3, 12, 18, 1944, 0, SAME[:1]), 0, (0, 0, 12, 18, 0)),
+    (_plan(TRAIN, 0, 3, 12, 18, 1944, 1944, SAME[:1]), 0, (1, 0, 12, 18, 0)),
+    (_plan(TRAIN_ASYNC, 0, 3, 12, 18, 1944, 1944, SAME), 0, (1, 0, 12, 18, 0)),
+    # no table: nothing to stage
+    (_plan(FORWARD, 0, 3, 12, 18, 1944, 0, [], table=0), 0, (0, 0, 12, 18, 0)),
+    (_plan(TRAIN, 0, 3, 12, 18, 1944, 1944, SAME, table=0), 0, (0, 0, 12, 18, 0)),
+    # a shared-shape table with a bad camera in frame b names frame b, on every route
+    (_plan(FORWARD, 0, 3, 12, 18, 1944, 0, [F(12, 18), F(12, 18), F(12, 18, focal=0.0)]), -4, ["focal length must be positive in frame 2"]),
+    (_plan(TRAIN, 0, 3, 12, 18, 1944, 1944, [F(12, 18), F(12, 18, focal=-1.0), F(12, 18, focal=0.0)]), -4, ["focal length must be positive in frame 1"]),
+    (_plan(TRAIN_ASYNC, 0, 3, 12, 18, 1944, 1944, [F(12, 18), F(12, 18, shift_x=-(2**31 - 1))]), -4, ["pixel positions overflow int32", "in frame 1"]),
+    (_plan(TRAIN, 0, 3, 12, 18, 1944, 1944, [F(12, 18, focal=0.0)]), -4, ["focal length must be positive in frame 0"]),
+    # a null table wins over every other bad argument of a ragged call, B = 0 included, on both training routes and forward
+    (_plan(TRAIN, 1, 3, 12, 18, 1944, 1944, [], table=0), -1, [BLOCKING + ": null frame table"]),
+    (_plan(TRAIN_ASYNC, 1, 3, 12, 18, 1944, 1944, [], table=0), -1, [ASYNC + ": null frame table"]),
+    (_plan(TRAIN, 1, 70000, 12, 18, -4, 1944, MIXED, table=0), -1, [BLOCKING + ": null frame table"]),
+    (_plan(FORWARD, 1, 3, 12, 18, 1944, 0, [], table=0), -1, ["esac_hip_forward_batch_shapes: null frame table"]),
+    # ... and B is held to its range before record 0 is read
+    (_plan(FORWARD, 1, 3, 12, 18, 1944, 0, []), -4, ["batch size 0 outside [1,"]),
+    (_plan(FORWARD, 0, 3, 12, 18, 1944, 0, []), -4, ["batch size 0 outside [1,"]),
+    (_plan(TRAIN_ASYNC, 0, 3, 12, 18, 1944, 1944, []), -4, ["esac_hip_backward_batch: batch size 0 outside"]),
+    # the shared-shape training call still holds the gradient stride against E*3*H*W
+    (_plan(TRAIN, 0, 3, 12, 18, 1944, 1943, SAME), -4, ["gradient frame stride 1943 < E*3*H*W = 1944"]),
+]
+
+
+def test_what_the_plan_hands_on(probe):
+    rows = probe([c[0] for c in PLAN_CASES])
+    for (req, status, want), row in zip(PLAN_CASES, rows):
+        assert row[0] == "plan" and int(row[1]) == status, (req, row)
+        if status:
+            for n in want:
+                assert n in row[8], (req, n, row)
+            continue
+        assert tuple(int(v) for v in row[2:7]) == want and row[8] == "", (req, row)
+        stage, shapes = want[0], want[1]
+        pairs = [m.split(":") for m in row[7].split(",")] if row[7] else []
+        assert len(pairs) == (int(req.split()[10]) if stage else 0), (req, row)
+        for got, single in pairs:
+            # a ragged table's record carries the margin of the single call on that frame's grid, bit for bit; any other table
+            # goes up as the caller wrote it (the probe's reserved[2] is 0x7fc00000)
+            assert got == (single if shapes else "7fc00000"), (req, row)
+    assert {c[1] for c in PLAN_CASES} == {0, -1, -4}

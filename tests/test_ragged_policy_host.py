@@ -1,4 +1,5 @@
-"""The host's decisions about a ragged batch (esac_hip_forward_batch_shapes; esac_amd/csrc/ragged_policy.hpp) through a
+"""The host's decisions about a ragged batch (esac_hip_forward_batch_shapes; esac_amd/csrc/ragged_policy.hpp, in the order of
+batch_plan.hpp's plan_batch -- the function the library's forward route calls, and the probe with it) through a
 stand-alone host program -- tests/native/ragged_policy_probe.cpp, built with the host compiler under AddressSanitizer and UBSan,
 its own process, no GPU: every rejection of check_shapes names the frame, accepted tables pass on both sides of every bound, and
 the per-frame re-score margin is call_scalars' margin of a single call on that frame's grid, bit for bit."""
@@ -10,7 +11,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "ragged_policy_probe.cpp")
 EXE = os.path.join(HERE, "native", "ragged_policy_probe_san")
-DEPS = [SRC] + [os.path.join(HERE, "..", "esac_amd", "csrc", h) for h in ("ragged_policy.hpp", "call_policy.hpp")] + \
+DEPS = [SRC] + [os.path.join(HERE, "..", "esac_amd", "csrc", h) for h in ("batch_plan.hpp", "ragged_policy.hpp", "call_policy.hpp")] + \
     [os.path.join(HERE, "..", "include", "esac_hip.h")]
 
 
@@ -70,6 +71,11 @@ CASES = [
     (_check(3, 32, 40, 11520, [F(32, 40), F(30, 30, focal=0.0)]), -4, -1, ["focal length must be positive in frame 1"]),
     # the capacity shape itself must be a legal grid (check_args)
     (_check(3, 2, 640, 11520, [F(32, 40)]), -4, -1, ["grid 2x640 too small"]),
+    # B is held to its range before record 0 is read
+    (_check(3, 32, 40, 11520, []), -4, -1, ["batch size 0 outside [1,"]),
+    # one frame: the single call on that frame's grid, whose width decides (41 is no multiple of 4, 32 is)
+    (_check(3, 32, 40, 11520, [F(24, 41)]), 0, 0, None),
+    (_check(3, 32, 40, 11520, [F(40, 32)]), 0, 1, None),
     # the first offending frame is the one named
     (_check(3, 32, 40, 11520, [F(32, 40), F(2, 2), F(99, 99)]), -4, -1, ["grid 2x2 too small", "in frame 1"]),
 ]
