@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "esac_hip_forward_batch_shapes",  # additive too
     "esac_hip_backward_batch_shapes", "esac_hip_backward_batch_dev_shapes",  # additive too
     "esac_hip_set_refine_route",  # additive too
+    "esac_hip_set_front_route", "esac_hip_front_route_taken", "esac_hip_read_rotations",  # additive too
 ]
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
@@ -267,6 +268,9 @@ def load_library():
         lib.esac_hip_set_wait.argtypes = [vp, i32]
         lib.esac_hip_set_refine_team.argtypes = [vp, i32]
         lib.esac_hip_set_refine_route.argtypes = [vp, i32]
+        lib.esac_hip_set_front_route.argtypes = [vp, i32]
+        lib.esac_hip_front_route_taken.argtypes = [vp]
+        lib.esac_hip_read_rotations.argtypes = [vp, vp, i32]
         lib.esac_hip_host_turn.argtypes = [vp, vp]
         lib.esac_hip_host_turn_mean.argtypes = [vp, vp, i32]
         lib.esac_hip_comm_unique_id.argtypes = [vp, C.c_size_t]
@@ -860,6 +864,23 @@ class Engine:
         """May a single frame's team run the kernel with the headline call's modes compiled in (esac_hip_set_refine_route)?
         False: every team runs the general kernel -- same outputs, bit for bit."""
         _check(self.lib.esac_hip_set_refine_route(self.ctx, 1 if on else 0), self.lib)
+
+    def set_front_route(self, on=True):
+        """May a single frame's forward call sample and score with the kernels that have the headline call's modes compiled in
+        (esac_hip_set_front_route)?  False: every call runs the general kernels -- same outputs, bit for bit."""
+        _check(self.lib.esac_hip_set_front_route(self.ctx, 1 if on else 0), self.lib)
+
+    def front_route_taken(self):
+        """Did the most recent forward call on this engine sample and score with the route kernels (esac_hip_front_route_taken)?"""
+        rc = self.lib.esac_hip_front_route_taken(self.ctx)
+        _check(min(rc, 0), self.lib)
+        return rc == 1
+
+    def read_rotations(self, N):
+        """The [N,3,3] rotation matrices the sampler stored beside the hypotheses of the most recent call (esac_hip_read_rotations)."""
+        out = np.zeros((int(N), 3, 3), np.float64)
+        _check(self.lib.esac_hip_read_rotations(self.ctx, out.ctypes.data_as(C.c_void_p), int(N)), self.lib)
+        return out
 
     def bwd_team_info(self):
         """Training path: were the slots of the last backward call refined by teams (ESAC_BUF_BWD_TEAM_INFO)."""

@@ -18,6 +18,7 @@
 #include "call_policy.hpp"
 #include "batch_plan.hpp"
 #include "esac_kernels.hpp"
+#include "front_route_policy.hpp"
 #include "eval_math.hpp"
 #include "gt_math.hpp"
 #include "pose_math.hpp"
@@ -174,7 +175,11 @@ struct esac_hip_ctx {
     float4* sc4 = nullptr;  // packed copy of the maps for the sampler (ensure_pack_ws), of sc4_cells cells
     long long sc4_cells = 0, tPart = 0;  // tN, tChunks, tPart: what the tile-stationary score workspace holds (ensure_tiled_ws)
     int tN = 0, tChunks = 0;
-    bool rt32_stale = false;  // esac_hip_write_hyps ran: the fp32 [R|t] rows are rebuilt by the next esac_hip_score
+    bool rt32_stale = false;  // esac_hip_write_hyps ran, or the front route sampled: the fp32 [R|t] rows are rebuilt by the next esac_hip_score
+    struct {  // the front route (front_route_policy.hpp): k_sample_route + k_rescore_route in front of a single frame's team
+        bool on = true;      // esac_hip_set_front_route; ESAC_FRONT_ROUTE=0
+        bool taken = false;  // the most recent forward call ran them (esac_hip_front_route_taken)
+    } front;
     struct {  // host timing (and the phase events of esac_hip_set_timing)
         bool on = false;
         int period = 1;       // record the phase events / device-side stamps on every period-th forward call
@@ -296,6 +301,7 @@ extern "C" int esac_hip_create(esac_hip_ctx** out, int device) {
     }
     if (const char* e = getenv("ESAC_FOLD_SELECT")) c->team.fold_select = atoi(e) != 0;
     if (const char* e = getenv("ESAC_REFINE_ROUTE")) c->team.route = atoi(e) != 0;
+    if (const char* e = getenv("ESAC_FRONT_ROUTE")) c->front.on = atoi(e) != 0;
     if (const char* e = getenv("ESAC_REFINE_TEAM_AUTO")) c->team.auto_env_off = atoi(e) == 0;
     if (c->team.auto_env_off || getenv("ESAC_REFINE_TEAM")) c->team.auto_size = false;  // (an explicit start value is an explicit size)
     if (const char* e = getenv("ESAC_SLOT_TEAMS")) c->team.slot_teams = atoi(e) != 0;
@@ -589,6 +595,14 @@ static void apply_auto_exact(KArgs& a, int B) { a.flags = auto_exact_flags(a.fla
 static int serial_fold(const esac_hip_ctx* c, const KArgs& a) {
     return !c->team.fold_select ? 0 : refine_folds_select(a) ? 1 : refine_folds_exact_stats(a) ? 2 : 0;
 }
+// The serial route's first two stages on the route kernels?  (a: the call's arguments as its first launch will see them;
+// table: the caller handed a camera table in -- also where a single frame's record 0 went inline)
+static bool front_route_eligible(const esac_hip_ctx* c, const KArgs& a, bool table) {
+    static_assert(FRONT_FLAG_EXACT_SCORES == ESAC_FLAG_EXACT_SCORES, "mirror of include/esac_hip.h");
+    const FrontRouteQuery q{c->front.on, true, a.frames, a.N, a.E, a.H, a.W, a.flags, a.max_tries, a.first_try, a.hyp_offset, table || a.cams != nullptr,
+                            a.shapes, a.sc4 != nullptr, a.hyp_index != nullptr, a.spec_flag != nullptr, a.tstamps != nullptr, a.errs != nullptr};
+    return front_takes_route(q);
+}
 // Stage k of the serial route (0: sample, 1: score, 2: select, 3: refine); returns the name check_launch reports it under.
 // ESAC_FLAG_EXACT_SCORES: every hypothesis scored in the reference's arithmetic (esac_util.h:235-260), softmax
 // statistics from those scores -- the score vector, probability and entropy are then the reference's own values
@@ -782,6 +796,7 @@ static int forward_impl(esac_hip_ctx* c, const float* d_sc, long long sc_frame_s
     a.scores_user = d_scores_out; a.result_user = d_result_out;
     a.result_pin = h_result_out ? c->pin.d : nullptr;
     c->spec.last_epoch = 0;
+    c->front.taken = false;
     const bool spec = speculation_eligible(c, a, B, s);
     if (spec && (rc = ensure_spec_streams(c))) return rc;
     if (tm) HIP_OK(hipEventRecord(c->timing.ev[0], s));
@@ -790,9 +805,16 @@ static int forward_impl(esac_hip_ctx* c, const float* d_sc, long long sc_frame_s
         if ((rc = enqueue_speculative(c, a, s, tm, t_entry))) return rc;
     } else {
         constexpr int stamp[4] = {1, 2, 0, 3};  // the host_ns slot stamped behind stage k (the selection has none)
+        // the front route: the sampler and the exact score with this call's modes compiled in.  Its sampler stores no fp32
+        // rows -- no kernel of this call reads them, and the next stage that does rebuilds them (ensure_rt32)
+        const bool front = c->front.taken = front_route_eligible(c, a, h_cams != nullptr);
+        if (front) c->rt32_stale = true;
         for (int k = 0; k < 4; k++) {
             if (k == 2) a.fold_select = serial_fold(c, a);
-            const char* what = enqueue_serial_stage(c, a, k, s);
+            const char* what;
+            if (front && k == 0)      launch_sample_route(a, s), what = "k_sample_route";
+            else if (front && k == 1) launch_rescore_route(a, s), what = "k_rescore_route";
+            else                      what = enqueue_serial_stage(c, a, k, s);
             if (k == 3) c->team.was_team = refine_team_members(a) > 0;
             if ((rc = check_launch(what))) return rc;
             if (stamp[k]) c->timing.host_ns[stamp[k]] = now_ns() - t_entry;
@@ -1524,6 +1546,23 @@ extern "C" int esac_hip_set_refine_team(esac_hip_ctx* c, int members) {
 extern "C" int esac_hip_set_refine_route(esac_hip_ctx* c, int on) {
     if (!c) return fail(-1, "null context");
     c->team.route = on != 0;
+    return 0;
+}
+extern "C" int esac_hip_set_front_route(esac_hip_ctx* c, int on) {
+    if (!c) return fail(-1, "null context");
+    c->front.on = on != 0;
+    return 0;
+}
+extern "C" int esac_hip_front_route_taken(esac_hip_ctx* c) {
+    if (!c) return fail(-1, "null context");
+    return c->front.taken ? 1 : 0;
+}
+extern "C" int esac_hip_read_rotations(esac_hip_ctx* c, double* h_dst, int N) {
+    if (!c || !h_dst || N <= 0) return fail(-1, "esac_hip_read_rotations: bad argument");
+    if (N > c->last.N || !c->ws.hyps_R) return fail(-2, "esac_hip_read_rotations: the workspace holds %d hypotheses", c->last.N);
+    DeviceGuard guard(c->device);
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(h_dst, c->ws.hyps_R, (size_t)N * 9 * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 extern "C" int esac_hip_set_debug(esac_hip_ctx* c, int flags) {

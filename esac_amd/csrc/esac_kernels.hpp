@@ -265,6 +265,10 @@ int tiled_sub_tiles(int P);
 void launch_select_rescore(const KArgs& a, hipStream_t s);
 void launch_rescore_all(const KArgs& a, hipStream_t s, bool per_frame_shape = false);
 void launch_stats_exact(const KArgs& a, hipStream_t s);
+// esac_front_route.hip: the sampler and the exact score of a call for which front_takes_route (front_route_policy.hpp) holds.
+// launch_sample_route stores no KArgs::rt32 rows: whoever calls it marks them stale
+void launch_sample_route(const KArgs& a, hipStream_t s);
+void launch_rescore_route(const KArgs& a, hipStream_t s);
 void launch_pick_record(const double* records, int world, double* pin, double epoch, double* zero, int n_zero, hipStream_t s);
 void launch_shard_balanced(const int64_t* assign, int N, int E, int world, int rank, int expert_base, int32_t* index_out,
                            int64_t* assign_out, int32_t* info_out, hipStream_t s);

@@ -4,6 +4,10 @@
 // ESAC_FLAG_STRICT_REFERENCE kernels are the same loops around the reference's own alignment.
 // The including file defines ESAC_K_SAMPLE_FIRST, ESAC_K_SAMPLE (the kernels' names), ESAC_SAMPLE_ALIGN and
 // ESAC_SAMPLE_FIRST_ATTR (attributes of the first-pass kernel); no include guard on purpose.
+// ESAC_SAMPLE_ROUTE (0 / 1), k_sample only: 1 = the headline call's modes as constants (esac_front_route.hip; what makes a call
+// eligible: front_route_policy.hpp) -- one frame, one expert, no table, no packed maps, no index list, from try 0, no hand-over,
+// no speculation.  ESAC_SAMPLE_RT32 (0 / 1): k_sample stores the fp32 rows of the streaming score (1 everywhere but on the front
+// route).  The loop, the draws and the arithmetic are these tokens either way.
 
 // Throughput shape, first phase (see sample_plan.hpp: FIRST_PHASE_TRIES)
 template <int TRIES>
@@ -56,7 +60,11 @@ __global__ __launch_bounds__(SAMPLE_B) void ESAC_K_SAMPLE(KArgs a) {
     constexpr int CPLN = 4 / LPT;  // candidates per lane in the shared rounds
     __shared__ int s_first[2][SAMPLE_B / 64];
     __shared__ double s_pose[CPLN > 1 ? SAMPLE_B * 12 : 1];  // [value][lane]: the best candidate's pose so far, per lane
+#if ESAC_SAMPLE_ROUTE
+    front_route_modes(a);
+#else
     frame_view(a);
+#endif
     const int h = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int e = expert_of(a, h);
@@ -68,7 +76,9 @@ __global__ __launch_bounds__(SAMPLE_B) void ESAC_K_SAMPLE(KArgs a) {
     const double tau = (double)a.tau;
     if (a.first_try > 0 && a.tries[h] != SAMPLE_PENDING) return;  // phase 2 of the throughput shape: done in phase 1
     if (a.first_try == 0 && threadIdx.x == 0) flag_bad_assignment(a, h);
+#if !ESAC_SAMPLE_ROUTE
     if (a.handover != 0x7fffffff && threadIdx.x == 0 && expert_stats_on(a)) atomicAdd(expert_stats(a, e), 1);  // (see expert_stats)
+#endif
 
     int parity = 0;
     for (int base = a.first_try, TRIES = 0; base < a.max_tries; base += TRIES, parity ^= 1) {
@@ -164,13 +174,15 @@ __global__ __launch_bounds__(SAMPLE_B) void ESAC_K_SAMPLE(KArgs a) {
             writer = a.max_tries - 1;  // budget exhausted: state of the last try remains
         }
         if (writer >= 0) {
-            if (t == writer && holder) store_hypothesis(a, h, map, rvec, T, R, cx, cy, tries_val);
+            if (t == writer && holder) store_hypothesis_rows<ESAC_SAMPLE_RT32>(a, h, map, rvec, T, R, cx, cy, tries_val);
             if (a.spec_flag && threadIdx.x == 0) a.spec_flag[h] = 0;  // settled by this pass
             return;
         }
+#if !ESAC_SAMPLE_ROUTE
         if (base + TRIES >= a.handover) {  // a straggler (wrong expert): the spread, screened search takes over from here
             if (threadIdx.x < 64) mark_pending(a, h, e, threadIdx.x == 0);
             return;
         }
+#endif
     }
 }

@@ -671,6 +671,21 @@ int esac_hip_set_refine_team(esac_hip_ctx* ctx, int members);
  * the general kernel (A/B measurements, tests).  Default: on; the environment variable ESAC_REFINE_ROUTE=0 starts a context
  * with it off. */
 int esac_hip_set_refine_route(esac_hip_ctx* ctx, int on);
+/* The two kernels in front of that team -- the sampler and the exact score -- have a route form too: a blocking or asynchronous
+ * esac_hip_forward of a single frame with one expert, at most 256 hypotheses on a grid of at most 8192 cells,
+ * ESAC_FLAG_EXACT_SCORES in force (ESAC_FLAG_AUTO_EXACT where it applies) and not ESAC_FLAG_STRICT_REFERENCE, no hyp_offset /
+ * d_hyp_index, no speculation and no debug knob runs kernels with exactly that combination compiled in (same draws, same
+ * arithmetic, same outputs bit for bit).  The route sampler does not store the fp32 pose rows of the streaming score, which
+ * nothing on such a call reads; the next stage call that does (esac_hip_score, esac_hip_select) rebuilds them first.
+ * on = 0: every call runs the general kernels (A/B measurements, tests).  Default: on; the environment variable
+ * ESAC_FRONT_ROUTE=0 starts a context with it off.  The stage entry points, the batches and the training path always run the
+ * general kernels. */
+int esac_hip_set_front_route(esac_hip_ctx* ctx, int on);
+/* 1: the most recent esac_hip_forward* call on this context sampled and scored with the route kernels; 0: with the general ones. */
+int esac_hip_front_route_taken(esac_hip_ctx* ctx);
+/* Tests: the [N,9] row-major rotation matrices the sampler stored beside the hypotheses of the most recent call (what the exact
+ * score multiplies with), N at most that call's; synchronises the device. */
+int esac_hip_read_rotations(esac_hip_ctx* ctx, double* h_dst, int N);
 
 /* How a blocking call waits for its result record (written by the last kernel into pinned host memory):
  * ESAC_WAIT_SPIN (default) polls the epoch word -- lowest latency, one host core busy for the ~0.2 ms of the call;

@@ -34,6 +34,8 @@ HEADLINE = {
     "k_rescoreILi1024E": "esac_kernels.hip",
     "k_refine_teamILi2ELi0ELi16EE": "esac_refine_team.hip",
     "k_refine_team_routeILi2ELi16EE": "esac_refine_team_route.hip",
+    "k_sample_routeILi256ELi2E": "esac_front_route.hip",
+    "k_rescore_routeILi1024ELi5E": "esac_front_route.hip",
 }
 FP64_ARITH = re.compile(r"^v_(?!mov)\w*_f64")
 CLASSES = ("total", "fp64", "agpr", "spill_lane", "v_mov", "s_nop", "s_waitcnt")

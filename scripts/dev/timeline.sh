@@ -24,7 +24,7 @@ for r in rows:
     n = short(r[0])
     if "esac" not in r[0] and cur is None:
         continue
-    start = n.startswith(("k_pack_cells", "k_sample_first", "k_sample<")) or (n.startswith("k_pending_list") and not prev.startswith("k_sample_first"))
+    start = n.startswith(("k_pack_cells", "k_sample_first", "k_sample<", "k_sample_route<")) or (n.startswith("k_pending_list") and not prev.startswith("k_sample_first"))
     if start and prev.startswith("k_pack_cells"):
         start = False
     if start:
