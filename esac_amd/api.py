@@ -42,6 +42,12 @@ RES_VALID = 31  # device records only: 1 a record, 3 the refinement team timed o
 # one row of esac_hip_eval_batch (include/esac_hip.h: ESAC_EVAL_*)
 EVAL_ROT_DEG, EVAL_TRANS_CM, EVAL_POSE_OK, EVAL_CLASS_OK, EVAL_QUAT, EVAL_INV_T, EVAL_EXPERT, EVAL_HYP, EVAL_STATUS = 0, 1, 2, 3, 4, 8, 11, 12, 13
 EVAL_DOUBLES = 16
+# one row of esac_hip_verify_batch (include/esac_hip.h: ESAC_VERIFY_*)
+VERIFY_SCORE, VERIFY_N, VERIFY_SSE, VERIFY_SIGMA2, VERIFY_STATUS, VERIFY_A, VERIFY_C = 0, 1, 2, 3, 4, 6, 28
+VERIFY_DOUBLES = 64
+VERIFY_MAX_POSES = 1024
+VERIFY_OK, VERIFY_FEW, VERIFY_PINV, VERIFY_BAD_POSE, VERIFY_BAD_EXPERT = 0, 1, 2, 3, 4
+VERIFY_POSE_RT, VERIFY_POSE_4X4 = 0, 1
 
 ABI_SYMBOLS = [
     "esac_hip_abi_version", "esac_hip_last_error", "esac_hip_device_count", "esac_hip_create", "esac_hip_destroy",
@@ -60,6 +66,7 @@ ABI_SYMBOLS = [
     "esac_hip_backward_batch_shapes", "esac_hip_backward_batch_dev_shapes",  # additive too
     "esac_hip_set_refine_route",  # additive too
     "esac_hip_set_front_route", "esac_hip_front_route_taken", "esac_hip_read_rotations",  # additive too
+    "esac_hip_verify_batch",  # additive too
 ]
 COMM_ID_BYTES = 128
 ABI_VERSION = 6
@@ -254,6 +261,7 @@ def load_library():
         lib.esac_hip_backward_batch_shapes.argtypes = lib.esac_hip_backward_batch_cams.argtypes
         lib.esac_hip_backward_batch_dev_shapes.argtypes = lib.esac_hip_backward_batch_dev.argtypes
         lib.esac_hip_eval_batch.argtypes = [vp, i32, vp, vp, vp, C.c_float, C.c_float, vp, vp]
+        lib.esac_hip_verify_batch.argtypes = [vp, i32, i32, vp, C.c_int64, vp, i32, vp, pp, vp, i32, vp, vp]
         lib.esac_hip_set_bwd_pose_records.argtypes = [vp, vp, i32]
         lib.esac_hip_read.argtypes = [vp, i32, vp, C.c_size_t]
         lib.esac_hip_write_hyps.argtypes = [vp, vp, i32]
@@ -702,6 +710,51 @@ class Engine:
         if rc != 0:
             _check(rc, self.lib)
         self._keep_eval = (records, gt, ge, out)  # alive until the kernel has run
+        return out
+
+    def verify_batch(self, scene_coords, poses, experts, params, cams=None, shapes=None, out=None):
+        """K given poses per frame against the maps (esac_hip_verify_batch): score, inlier count, SSE, normal matrix and pose
+        covariance of each.  scene_coords float32 [B,E,3,H,W], [E,3,H,W] (shared by all frames) or, with shapes, the packed
+        [B,S] tensor of pack_frames; poses float64 [B,K,6] (rvec | tvec, scene -> camera) or float32 [B,K,4,4] (camera poses as
+        outPose / gtPoses carry them); experts int32 / int64 [B,K], or [B]: one expert per frame for all K.  params: one frame
+        (make_params; E, the grid or a ragged batch's capacity, the camera, the score parameters, strict_reference).  cams /
+        shapes: as in forward_batch.  One launch on torch's current stream, behind whatever wrote the inputs; nothing is waited
+        for; host poses / experts are uploaded asynchronously on that stream.  Returns the device float64 [B,K,64] of rows
+        (`out` when given; columns: VERIFY_*)."""
+        who = "esac.verify_batch"
+        B, K, fmt = _check_verify_args(who, scene_coords, poses, experts, shapes, out)
+        sc = scene_coords if scene_coords.is_cuda else scene_coords.to(self.device, non_blocking=True)
+        sc = sc.contiguous()
+        po = poses if poses.is_cuda else self._upload(poses, poses.dtype)
+        po = po.contiguous()
+        ex = experts if isinstance(experts, torch.Tensor) and experts.is_cuda else \
+            self._upload(torch.as_tensor(np.asarray(experts, np.int64) if not isinstance(experts, torch.Tensor) else experts).clamp(-1, 2 ** 31 - 1), torch.int32)
+        if ex.dtype != torch.int32:
+            # on the device, in stream order; clamped first: an int64 beyond int32 must stay outside [0,E), not wrap into it
+            ex = ex.clamp(-1, 2 ** 31 - 1).to(torch.int32)
+        if ex.dim() == 1:
+            ex = ex.unsqueeze(1).expand(B, K)
+        ex = ex.contiguous()
+        for name, t in (("sceneCoordinates", sc), ("poses", po), ("experts", ex)) + ((("out", out),) if out is not None else ()):
+            if t.device != self.device:
+                raise RuntimeError("%s: %s lives on %s, this engine on %s" % (who, name, t.device, self.device))
+        if out is None:
+            out = torch.empty((B, K, VERIFY_DOUBLES), dtype=torch.float64, device=self.device)
+        table, ragged = None, 0
+        if shapes is not None:
+            shapes = _shapes_arg(who, shapes, B)
+            if cams is None:
+                cams = make_cams([params.shift_x] * B, [params.shift_y] * B, [params.focal] * B, [params.ppx] * B, [params.ppy] * B)
+            else:
+                cams = _cams_arg(cams, B, who).copy()  # (the caller's table keeps its padding)
+            cams["reserved"][:, :2] = np.asarray(shapes, np.int32)
+            table, ragged = cams, 1
+        elif cams is not None:
+            table = _cams_arg(cams, B, who)  # (the library copies the table before it returns)
+        stride = int(sc.stride(0)) if sc.dim() in (5, 2) else 0
+        self._call(self.lib.esac_hip_verify_batch, B, K, sc.data_ptr(), stride, po.data_ptr(), fmt, ex.data_ptr(), C.byref(params),
+                   table.ctypes.data if table is not None else None, ragged, self._stream(), out.data_ptr())
+        self._keep_verify = (sc, po, ex, out)  # alive until the kernel has run
         return out
 
     def read_frames(self, which, B):
@@ -1645,6 +1698,99 @@ def eval_batch(records, gtPoses, gtExperts=None, rotThreshold=5.0, transThreshol
     harness.rerun_frames; 1 no record)."""
     _check_eval_args("esac.eval_batch", records, gtPoses, gtExperts, rotThreshold, transThreshold)
     return engine(records.device.index).eval_batch(records, gtPoses, gtExperts, rotThreshold, transThreshold)
+
+
+# ---------------------------------------------------------------- pose verification
+def _check_verify_args(who, sceneCoordinates, poses, experts, shapes=None, out=None):
+    """Types, dtypes and shapes of a verify_batch call; returns (B, K, pose format).  Raises RuntimeError naming the argument;
+    touches no device."""
+    if not isinstance(poses, torch.Tensor):
+        raise RuntimeError("%s: poses must be a torch.Tensor (float64 [B,K,6] or float32 [B,K,4,4])" % who)
+    if poses.dtype == torch.float64 and poses.dim() == 3 and poses.size(2) == 6:
+        fmt = VERIFY_POSE_RT
+    elif poses.dtype == torch.float32 and poses.dim() == 4 and tuple(poses.shape[2:]) == (4, 4):
+        fmt = VERIFY_POSE_4X4
+    else:
+        raise RuntimeError("%s: poses must be float64 [B,K,6] (rvec | tvec) or float32 [B,K,4,4] (camera poses), found %s %s"
+                           % (who, poses.dtype, list(poses.shape)))
+    B, K = int(poses.size(0)), int(poses.size(1))
+    if B < 1 or B > MAX_BATCH:
+        raise RuntimeError("%s: poses hold %d frames, 1 to %d per call" % (who, B, MAX_BATCH))
+    if K < 1 or K > VERIFY_MAX_POSES:
+        raise RuntimeError("%s: poses hold %d poses per frame, 1 to %d per call" % (who, K, VERIFY_MAX_POSES))
+    if isinstance(experts, torch.Tensor):
+        if experts.dtype not in (torch.int32, torch.int64):
+            raise RuntimeError("%s: expected scalar type torch.int32 or torch.int64 for experts but found %s" % (who, experts.dtype))
+        shape = tuple(experts.shape)
+    else:
+        try:
+            arr = np.asarray(experts)
+        except (TypeError, ValueError):
+            raise RuntimeError("%s: experts must be a tensor or a sequence of integers" % who)
+        if arr.dtype.kind not in "iu":
+            raise RuntimeError("%s: experts must hold integers, found dtype %s" % (who, arr.dtype))
+        shape = tuple(arr.shape)
+    if shape != (B, K) and shape != (B,):
+        raise RuntimeError("%s: experts must be [B,K] = [%d,%d] (poses) or [B], found %s" % (who, B, K, list(shape)))
+    if not isinstance(sceneCoordinates, torch.Tensor) or sceneCoordinates.dtype != torch.float32:
+        raise RuntimeError("%s: sceneCoordinates must be a float32 tensor" % who)
+    if shapes is None:
+        if sceneCoordinates.dim() not in (4, 5) or sceneCoordinates.size(-3) != 3:
+            raise RuntimeError("%s: sceneCoordinates must be float32 [B,E,3,H,W] or [E,3,H,W], found %s" % (who, list(sceneCoordinates.shape)))
+        if sceneCoordinates.dim() == 5 and sceneCoordinates.size(0) != B:
+            raise RuntimeError("%s: batch sizes of sceneCoordinates (%d) and poses (%d) differ" % (who, sceneCoordinates.size(0), B))
+    else:
+        _shapes_arg(who, shapes, B)
+        if sceneCoordinates.dim() != 2 or sceneCoordinates.size(0) != B:
+            raise RuntimeError("%s: with shapes, sceneCoordinates must be the packed [B,S] tensor (pack_frames), found %s"
+                               % (who, list(sceneCoordinates.shape)))
+    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == torch.float64
+                                and tuple(out.shape) == (B, K, VERIFY_DOUBLES)):
+        raise RuntimeError("%s: out must be a dense float64 device tensor [B,K,%d] = [%d,%d,%d]" % (who, VERIFY_DOUBLES, B, K, VERIFY_DOUBLES))
+    return B, K, fmt
+
+
+def verify_batch(sceneCoordinates, poses, experts, shiftX, shiftY, focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha,
+                 inlierBeta, maxReproj, subSampling, shapes=None, out=None):
+    """How well do the scene-coordinate maps support GIVEN poses, and how certain are they (esac_hip_verify_batch)?
+    sceneCoordinates float32 [B,E,3,H,W] or [E,3,H,W] (shared by all frames); with shapes (B (h, w) pairs: a ragged batch) the
+    packed [B,S] tensor of `pack_frames` or a list of B [E,3,h_b,w_b] maps.  poses: float64 [B,K,6], rvec | tvec scene -> camera
+    (RES_RVEC of a record, BUF_HYPS), or float32 [B,K,4,4], camera poses as outPose / gtPoses carry them (inverted on the device);
+    experts int32 / int64 [B,K], or [B] for all K poses of a frame.  The five camera arguments are scalars or length-B sequences,
+    as in forward_batch; the score parameters are forward's.  Honours set_strict_reference (a non-finite cell: NaN score).
+    Enqueued on torch's current stream -- right behind a forward_batch_async whose records it may read --; nothing is waited for;
+    host poses / experts are uploaded asynchronously.  Draws no RNG stream: the call counter stays.
+    Returns a device float64 [B,K,64] (`out` when given): VERIFY_SCORE (what RES_SCORE holds for the winner), VERIFY_N (cells with
+    err < tau, the refinement's rule) and over those cells VERIFY_SSE, VERIFY_A (21 upper-triangle sums of J^T J, row-major, d /
+    d(rvec, tvec)), VERIFY_SIGMA2 = SSE / (2n - 6), VERIFY_C (6x6 covariance sigma^2 A^-1, row-major); VERIFY_STATUS: VERIFY_OK,
+    VERIFY_FEW (n < 4: sigma^2 and C are NaN), VERIFY_PINV (rank-deficient A: pseudo-inverse), VERIFY_BAD_POSE (not finite, or a
+    singular 4x4) and VERIFY_BAD_EXPERT (outside [0,E)): every figure of that row is NaN, the other rows are unaffected."""
+    who = "esac.verify_batch"
+    if isinstance(sceneCoordinates, (list, tuple)):
+        if shapes is None:
+            raise RuntimeError("%s: a list of maps is a ragged batch: shapes is required" % who)
+        if not isinstance(poses, torch.Tensor) or poses.dim() < 2:
+            raise RuntimeError("%s: poses must be a torch.Tensor (float64 [B,K,6] or float32 [B,K,4,4])" % who)
+        E, shapes = _ragged_args(who, sceneCoordinates, int(poses.size(0)), shapes, None)
+        B, K, _ = _check_verify_args(who, torch.empty((int(poses.size(0)), 0), dtype=torch.float32), poses, experts, shapes, out)
+    else:
+        B, K, _ = _check_verify_args(who, sceneCoordinates, poses, experts, shapes, out)
+        if shapes is not None:
+            E, shapes = _ragged_args(who, sceneCoordinates, B, shapes, None)
+        else:
+            E = int(sceneCoordinates.shape[-4])
+    (shiftX, shiftY, focalLength, ppointX, ppointY), cams = _per_frame_cams(who, B, shiftX, shiftY, focalLength, ppointX, ppointY)
+    on_dev = [t.device.index for t in (list(sceneCoordinates) if isinstance(sceneCoordinates, (list, tuple)) else [sceneCoordinates]) + [poses]
+              if isinstance(t, torch.Tensor) and t.is_cuda]
+    eng = engine(on_dev[0] if on_dev else None)
+    if isinstance(sceneCoordinates, (list, tuple)):
+        sceneCoordinates, _ = pack_frames(sceneCoordinates, device=eng.device)
+    H, W = capacity_shape(shapes) if shapes is not None else (int(sceneCoordinates.shape[-2]), int(sceneCoordinates.shape[-1]))
+    shape_before = eng._shape
+    p = eng.make_params(E, H, W, K, shiftX, shiftY, focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha, inlierBeta, maxReproj,
+                        subSampling, strict_reference=_state["strict_reference"])
+    eng._shape = shape_before  # (read_forward_frames keeps reading the last forward call's buffers)
+    return eng.verify_batch(sceneCoordinates, poses, experts, p, cams=cams, shapes=shapes, out=out)
 
 
 def forward_batch_async(sceneCoordinates, hypAssignment, shiftX, shiftY, focalLength, ppointX, ppointY,

@@ -13,7 +13,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libesac_hip.so")
-SOURCES = ["esac_kernels.hip", "esac_score_tiled.hip", "esac_refine.hip", "esac_refine_team.hip", "esac_refine_team_route.hip", "esac_front_route.hip", "esac_backward.hip", "esac_eval.hip",
+SOURCES = ["esac_kernels.hip", "esac_score_tiled.hip", "esac_refine.hip", "esac_refine_team.hip", "esac_refine_team_route.hip", "esac_front_route.hip", "esac_backward.hip", "esac_eval.hip", "esac_verify.hip",
            "esac_capi.hip"]
 # every header under csrc/ (a new one must not be forgotten here: a stale library would be tested against new headers)
 HEADERS = sorted(os.path.basename(h) for h in glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join("..", "..", "include", "esac_hip.h")]

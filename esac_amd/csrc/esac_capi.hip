@@ -22,6 +22,8 @@
 #include "eval_math.hpp"
 #include "gt_math.hpp"
 #include "pose_math.hpp"
+#include "verify_math.hpp"
+#include "verify_policy.hpp"
 
 using namespace esac;
 
@@ -117,6 +119,19 @@ struct LastCall {
                             // that far apart (chunk_args; esac_hip_read of the slabs and the slot maps); 0 otherwise
     int dev_batch = 0;      // B of the asynchronous training batch while it is the most recent call (esac_hip_check reads that many words)
 };
+// A frame table on its way to the device (stage_cams): pinned staging of the context's own, the table the kernels read, and the
+// event behind the most recent upload -- the staging is rewritten only after it
+struct CamTable {
+    esac_hip_frame_cam* h_cams = nullptr;  // pinned staging [ESAC_MAX_BATCH]: the caller's array is free when the call returns
+    FrameCam* d_cams = nullptr;            // ... and the table the kernels read (KArgs::cams)
+    hipEvent_t cams_ev = nullptr;
+    bool cams_queued = false;
+    void release() {
+        if (d_cams) (void)hipFree(d_cams);
+        if (h_cams) (void)hipHostFree(h_cams);
+        if (cams_ev) (void)hipEventDestroy(cams_ev);
+    }
+};
 struct esac_hip_ctx {
     int device = 0;
     int capN = 0, capP = 0, capB = 0;  // capN / capP count elements over ALL frames of a batch
@@ -158,7 +173,7 @@ struct esac_hip_ctx {
         int cap_batch = 0;                     // slots per frame the batches have needed so far
         long long budget = 2048LL << 20;       // bytes of slot workspace a batch may use (ESAC_BWD_BATCH_BUDGET_MB): beyond it, chunks of frames
     } train;
-    struct {  // per-call staging
+    struct : CamTable {  // per-call staging; the table: per-frame cameras of a batch (esac_hip_forward_batch_cams / esac_hip_backward_batch_cams)
         double* h_gt = nullptr;                // pinned staging of the per-frame ground truth [ESAC_MAX_BATCH,22]
         double* d_gt = nullptr;                // ... and its device copy
         // esac_hip_backward_batch_dev: nothing of the call is staged on the host
@@ -166,12 +181,8 @@ struct esac_hip_ctx {
         int* d_frame_status = nullptr;         // [ESAC_MAX_BATCH] per-frame outcome of the most recent such call (BwdArgs::frame_status)
         // esac_hip_set_bwd_pose_records: what the NEXT training call writes its forward-format records to (one-shot: take_pose_arm)
         PoseArm pose_arm;
-        // per-frame cameras of a batch (esac_hip_forward_batch_cams / esac_hip_backward_batch_cams)
-        esac_hip_frame_cam* h_cams = nullptr;  // pinned staging [ESAC_MAX_BATCH]: the caller's array is free when the call returns
-        FrameCam* d_cams = nullptr;            // ... and the table the kernels read (KArgs::cams)
-        hipEvent_t cams_ev = nullptr;          // recorded behind the most recent upload: the staging is rewritten only after it
-        bool cams_queued = false;
     } stage;
+    CamTable verify_cams;  // esac_hip_verify_batch's own table: a forward or training batch in flight keeps the one it reads
     float4* sc4 = nullptr;  // packed copy of the maps for the sampler (ensure_pack_ws), of sc4_cells cells
     long long sc4_cells = 0, tPart = 0;  // tN, tChunks, tPart: what the tile-stationary score workspace holds (ensure_tiled_ws)
     int tN = 0, tChunks = 0;
@@ -327,9 +338,8 @@ extern "C" int esac_hip_destroy(esac_hip_ctx* c) {
     if (c->stage.d_gt) (void)hipFree(c->stage.d_gt);
     if (c->stage.d_gt_dev) (void)hipFree(c->stage.d_gt_dev);
     if (c->stage.d_frame_status) (void)hipFree(c->stage.d_frame_status);
-    if (c->stage.d_cams) (void)hipFree(c->stage.d_cams);
-    if (c->stage.h_cams) (void)hipHostFree(c->stage.h_cams);
-    if (c->stage.cams_ev) (void)hipEventDestroy(c->stage.cams_ev);
+    c->stage.release();
+    c->verify_cams.release();
     if (c->stage.h_gt) (void)hipHostFree(c->stage.h_gt);
     if (c->sc4) (void)hipFree(c->sc4);
     drop_comm(c);
@@ -480,25 +490,28 @@ static int make_args(esac_hip_ctx* c, const float* d_sc, const int64_t* d_assign
 // The table of a planned batch call (batch_plan.hpp: every record is checked), staged in pinned memory of the context's own and
 // uploaded on `s` -- once per call; chunks and re-runs offset the device pointer.  The staging is rewritten only after the previous
 // upload has left it (an asynchronous batch may still have its copy queued); the device table in stream order behind its last readers.
-static int stage_cams(esac_hip_ctx* c, const BatchPlan& plan, const esac_hip_frame_cam* h_cams, int B, hipStream_t s) {
+static int stage_cams(CamTable& t, const BatchPlan& plan, const esac_hip_frame_cam* h_cams, int B, hipStream_t s) {
     static_assert(sizeof(esac_hip_frame_cam) == sizeof(FrameCam) && offsetof(esac_hip_frame_cam, focal) == offsetof(FrameCam, focal) &&
                   offsetof(esac_hip_frame_cam, ppy) == offsetof(FrameCam, ppy), "esac_hip_frame_cam is the device record");
     static_assert(offsetof(esac_hip_frame_cam, reserved) == offsetof(FrameCam, h) && offsetof(FrameCam, w) == offsetof(FrameCam, h) + 4 &&
                   offsetof(FrameCam, margin) == offsetof(FrameCam, h) + 8, "reserved[0..2] = the frame's h, w and margin");
-    if (!c->stage.h_cams) {
-        HIP_OK(hipHostMalloc((void**)&c->stage.h_cams, (size_t)ESAC_MAX_BATCH * sizeof(FrameCam), hipHostMallocDefault));
-        HIP_OK(hipMalloc((void**)&c->stage.d_cams, (size_t)ESAC_MAX_BATCH * sizeof(FrameCam)));
-        HIP_OK(hipEventCreateWithFlags(&c->stage.cams_ev, hipEventDisableTiming));
+    if (!t.h_cams) {
+        HIP_OK(hipHostMalloc((void**)&t.h_cams, (size_t)ESAC_MAX_BATCH * sizeof(FrameCam), hipHostMallocDefault));
+        HIP_OK(hipMalloc((void**)&t.d_cams, (size_t)ESAC_MAX_BATCH * sizeof(FrameCam)));
+        HIP_OK(hipEventCreateWithFlags(&t.cams_ev, hipEventDisableTiming));
     }
-    if (c->stage.cams_queued) {
-        HIP_OK(hipEventSynchronize(c->stage.cams_ev));
-        c->stage.cams_queued = false;
+    if (t.cams_queued) {
+        HIP_OK(hipEventSynchronize(t.cams_ev));
+        t.cams_queued = false;
     }
-    plan_records(plan, h_cams, B, c->stage.h_cams);
-    HIP_OK(hipMemcpyAsync(c->stage.d_cams, c->stage.h_cams, (size_t)B * sizeof(FrameCam), hipMemcpyHostToDevice, s));
-    HIP_OK(hipEventRecord(c->stage.cams_ev, s));
-    c->stage.cams_queued = true;
+    plan_records(plan, h_cams, B, t.h_cams);
+    HIP_OK(hipMemcpyAsync(t.d_cams, t.h_cams, (size_t)B * sizeof(FrameCam), hipMemcpyHostToDevice, s));
+    HIP_OK(hipEventRecord(t.cams_ev, s));
+    t.cams_queued = true;
     return 0;
+}
+static int stage_cams(esac_hip_ctx* c, const BatchPlan& plan, const esac_hip_frame_cam* h_cams, int B, hipStream_t s) {
+    return stage_cams(c->stage, plan, h_cams, B, s);
 }
 
 static void forward_team(const esac_hip_ctx* c, KArgs& a) { forward_team(c->team.latch, a.flags, &a.team, &a.solo); }
@@ -1447,6 +1460,41 @@ extern "C" int esac_hip_eval_batch(esac_hip_ctx* c, int B, const double* d_recor
     DeviceGuard guard(c->device);
     launch_eval_batch(B, d_records, d_gt_poses, d_gt_experts, (double)rot_thresh_deg, (double)trans_thresh_cm, d_out, (hipStream_t)stream);
     return check_launch("k_eval_batch");
+}
+
+// K given poses per frame against the maps (esac_verify.hip; include/esac_hip.h): one launch on the caller's stream, no workspace
+// of the context's but a frame table of its own -- the hypothesis, score and result buffers of a forward or training call, and
+// the table such a call in flight reads, stay as they are.
+static_assert(ESAC_VERIFY_SCORE == ESAC_VERIFY_SCORE_K && ESAC_VERIFY_N == ESAC_VERIFY_N_K && ESAC_VERIFY_SSE == ESAC_VERIFY_SSE_K &&
+                  ESAC_VERIFY_SIGMA2 == ESAC_VERIFY_SIGMA2_K && ESAC_VERIFY_STATUS == ESAC_VERIFY_STATUS_K && ESAC_VERIFY_A == ESAC_VERIFY_A_K &&
+                  ESAC_VERIFY_C == ESAC_VERIFY_C_K && ESAC_VERIFY_DOUBLES == ESAC_VERIFY_DOUBLES_K && ESAC_VERIFY_OK == ESAC_VERIFY_OK_K &&
+                  ESAC_VERIFY_FEW == ESAC_VERIFY_FEW_K && ESAC_VERIFY_PINV == ESAC_VERIFY_PINV_K && ESAC_VERIFY_BAD_POSE == ESAC_VERIFY_BAD_POSE_K &&
+                  ESAC_VERIFY_BAD_EXPERT == ESAC_VERIFY_BAD_EXPERT_K && ESAC_VERIFY_POSE_RT == ESAC_VERIFY_POSE_RT_K &&
+                  ESAC_VERIFY_POSE_4X4 == ESAC_VERIFY_POSE_4X4_K && ESAC_VERIFY_MAX_POSES == VERIFY_MAX_POSES,
+              "verify row layout drifted between include/esac_hip.h, verify_math.hpp and verify_policy.hpp");
+extern "C" int esac_hip_verify_batch(esac_hip_ctx* c, int B, int K, const float* d_sc, int64_t sc_frame_stride, const void* d_poses,
+                                     int pose_format, const int32_t* d_experts, const esac_hip_params* p, const esac_hip_frame_cam* cams,
+                                     int ragged, void* stream, double* d_out) {
+    BatchPlan plan;
+    if (int rc = plan_verify(c != nullptr, B, K, d_sc != nullptr, sc_frame_stride, d_poses != nullptr, pose_format, d_experts != nullptr, p, cams,
+                             ragged != 0, d_out != nullptr, &plan)) return rc;
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const esac_hip_params& q = plan.p;
+    KArgs a{};  // (no workspace pointer is set: the kernel reads the maps, the camera and the score parameters)
+    a.sc = d_sc; a.frames = B; a.sc_frame_stride = sc_frame_stride;
+    a.E = q.E; a.H = q.H; a.W = q.W; a.N = K;
+    a.shift_x = q.shift_x; a.shift_y = q.shift_y; a.sub = q.sub_sampling;
+    a.focal = q.focal; a.ppx = q.ppx; a.ppy = q.ppy;
+    a.tau = q.inlier_thresh; a.alpha = q.inlier_alpha; a.beta = q.inlier_beta; a.max_reproj = q.max_reproj;
+    a.flags = q.flags;
+    if (plan.stage) {
+        if (int rc = stage_cams(c->verify_cams, plan, cams, B, s)) return rc;
+        a.cams = c->verify_cams.d_cams;
+        a.shapes = plan.shapes;
+    }
+    launch_verify_batch(a, VerifyArgs{d_poses, d_experts, d_out, K, pose_format}, s);
+    return check_launch("k_verify_batch");
 }
 
 extern "C" int esac_hip_set_wait(esac_hip_ctx* c, int mode) {

@@ -275,6 +275,16 @@ void launch_shard_balanced(const int64_t* assign, int N, int E, int world, int r
 // esac_eval.hip: records [B,32] + ground truth -> the test loop's figures [B,16] (eval_math.hpp), one lane per frame, in stream order
 void launch_eval_batch(int B, const double* records, const float* gt_poses, const int64_t* gt_experts, double rot_thresh_deg,
                        double trans_thresh_cm, double* out, hipStream_t s);
+// esac_verify.hip: K given poses per frame against one expert's map each -> rows [B,K,64] (verify_math.hpp), grid (K, a.frames),
+// one launch in stream order.  Of `a` the kernel reads the maps, the grid, the camera (frame table included), tau, alpha, beta,
+// max_reproj, sub and the strict flag; no workspace pointer
+struct VerifyArgs {
+    const void* poses;       // format 0: double [B,K,6] rvec | tvec; 1: float [B,K,4,4] camera poses
+    const int32_t* experts;  // [B,K]; a value outside [0,E) is that row's status, never an address
+    double* out;             // [B,K,64]
+    int K, format;
+};
+void launch_verify_batch(const KArgs& a, const VerifyArgs& v, hipStream_t s);
 int refine_coop_capacity();              // resident workgroups of the cooperative refinement kernel on the current device
 int refine_coop_slice(const KArgs& a);  // cells per cooperating refinement workgroup, 0: one workgroup refines
 int refine_team_members(const KArgs& a);  // members of the team that refines a small grid, 0: one workgroup refines

@@ -146,7 +146,7 @@ def _focal_list(who, focal_lengths, B):
 def localize_batch(images, gating, experts, focal_lengths, gt_poses=None, gt_experts=None, hypotheses=256, threshold=10.0,
                    inlier_alpha=100.0, inlier_beta=0.5, max_reprojection=100.0, subsample=8, e_hyps=None, expert_selection=False,
                    oracle_experts=None, generator=None, asynchronous=False, all_experts=False, strict_reference=False,
-                   rot_threshold_deg=5.0, trans_threshold_cm=5.0):
+                   rot_threshold_deg=5.0, trans_threshold_cm=5.0, verify_gt=False):
     """The test-loop counterpart of `train_batch`: B images of one size through ONE forward batch (`esac.forward_batch_async`) and,
     when `gt_poses` is given, ONE `esac.eval_batch` that turns the records into the loop's figures on the device.
 
@@ -157,6 +157,10 @@ def localize_batch(images, gating, experts, focal_lengths, gt_poses=None, gt_exp
     read).  all_experts: every expert runs and the `.cpu()` of the B x E activity flags is skipped.
     gt_poses [B,4,4] and gt_experts [B] (tensors on either side, arrays, lists) feed eval_batch; host values are uploaded
     asynchronously.  strict_reference: as in `localize`.
+    verify_gt (needs gt_poses): ONE `esac.verify_batch` (K = 1, the 4x4 format) of the ground-truth poses is enqueued behind the
+    forward batch -- on the map of gt_experts[b] when given, else of the winner's expert, read from the device records without a
+    host synchronisation -- and the dict gains gt_verify [B,1,64] (device): does the ground truth score higher than the winner
+    (VERIFY_SCORE against RES_SCORE: sampling failed), or not (scoring or the expert failed)?
     asynchronous=True with all_experts=True and device inputs: NO host synchronisation in this function; every result stays on
     the device.  A frame whose refinement team timed out then carries EVAL_STATUS / RES_VALID = 3: `frames_to_rerun` finds
     them in the host copy of `eval`, `rerun_frames` runs them again.
@@ -169,7 +173,7 @@ def localize_batch(images, gating, experts, focal_lengths, gt_poses=None, gt_exp
     if isinstance(images, (list, tuple)):
         return _localize_ragged(list(images), gating, experts, focal_lengths, gt_poses, gt_experts, hypotheses, threshold, inlier_alpha,
                                 inlier_beta, max_reprojection, subsample, e_hyps, expert_selection, oracle_experts, generator,
-                                asynchronous, all_experts, strict_reference, rot_threshold_deg, trans_threshold_cm)
+                                asynchronous, all_experts, strict_reference, rot_threshold_deg, trans_threshold_cm, verify_gt)
     dev = images.device
     B, E = int(images.size(0)), len(experts)
     pp_x = float(images.size(3) / 2)
@@ -188,7 +192,8 @@ def localize_batch(images, gating, experts, focal_lengths, gt_poses=None, gt_exp
     outputs = [experts[e](images) if on else torch.zeros((B, 3, pred_h, pred_w), device=dev) for e, on in enumerate(active_any)]
     prediction = torch.stack(outputs, dim=1)  # [B,E,3,h,w]; rows of inactive experts are never read
     return _solve_batch(prediction, None, e_hyps, e_hist, active_count, focals, pp_x, pp_y, gt_poses, gt_experts, threshold, inlier_alpha,
-                        inlier_beta, max_reprojection, subsample, asynchronous, strict_reference, rot_threshold_deg, trans_threshold_cm, start)
+                        inlier_beta, max_reprojection, subsample, asynchronous, strict_reference, rot_threshold_deg, trans_threshold_cm, start,
+                        verify_gt)
 
 
 def _draw_hyps(gating_probs_of, B, dev, e_hyps, hypotheses, expert_selection, oracle_experts, generator):
@@ -214,9 +219,11 @@ def _draw_hyps(gating_probs_of, B, dev, e_hyps, hypotheses, expert_selection, or
 
 
 def _solve_batch(prediction, shapes, e_hyps, e_hist, active_count, focals, pp_x, pp_y, gt_poses, gt_experts, threshold, inlier_alpha,
-                 inlier_beta, max_reprojection, subsample, asynchronous, strict_reference, rot_threshold_deg, trans_threshold_cm, start):
-    """The solver half of localize_batch: ONE forward batch, ONE eval_batch, the result dict.  shapes: None and prediction
-    [B,E,3,h,w], or the B grids of a ragged batch with prediction the packed [B,S] buffer (pp_x, pp_y then hold B values)."""
+                 inlier_beta, max_reprojection, subsample, asynchronous, strict_reference, rot_threshold_deg, trans_threshold_cm, start,
+                 verify_gt=False):
+    """The solver half of localize_batch: ONE forward batch, ONE eval_batch, (verify_gt) ONE verify_batch, the result dict.
+    shapes: None and prediction [B,E,3,h,w], or the B grids of a ragged batch with prediction the packed [B,S] buffer (pp_x, pp_y
+    then hold B values)."""
     B, E = int(e_hyps.shape[0]), int(e_hist.shape[1])
     e_hyps = e_hyps.contiguous()
     strict_before = api._state["strict_reference"]
@@ -226,6 +233,15 @@ def _solve_batch(prediction, shapes, e_hyps, e_hist, active_count, focals, pp_x,
         ragged = {} if shapes is None else dict(shapes=shapes, experts=E)
         fwd = api.forward_batch_async(prediction, e_hyps, 0, 0, focals, pp_x, pp_y, threshold, inlier_alpha, inlier_beta,
                                       max_reprojection, subsample, **ragged)
+        gt_verify = None
+        if verify_gt:
+            if gt_poses is None:
+                raise RuntimeError("localize_batch: verify_gt needs gt_poses")
+            gt = gt_poses if isinstance(gt_poses, torch.Tensor) else torch.from_numpy(np.asarray(gt_poses, np.float32))
+            # the true expert's map, or the winner's: column RES_EXPERT of the device records, in stream order
+            on = gt_experts if gt_experts is not None else fwd["records"][:, api.RES_EXPERT].to(torch.int32)
+            gt_verify = api.verify_batch(prediction, gt.to(torch.float32).reshape(B, 1, 4, 4), on, 0, 0, focals, pp_x, pp_y, threshold,
+                                         inlier_alpha, inlier_beta, max_reprojection, subsample, shapes=shapes)
     finally:
         api.set_strict_reference(strict_before)
     ev = None
@@ -237,6 +253,8 @@ def _solve_batch(prediction, shapes, e_hyps, e_hist, active_count, focals, pp_x,
                            max_reprojection=max_reprojection, subsample=subsample, strict_reference=strict,
                            max_tries=api._state["max_tries"], max_ref_steps=api._state["max_ref_steps"],
                            rot_threshold_deg=rot_threshold_deg, trans_threshold_cm=trans_threshold_cm))
+    if verify_gt:
+        out["gt_verify"] = gt_verify
     if not asynchronous:
         rec = fwd["records"].cpu().numpy()  # the one wait of the blocking form
         out["records_host"] = rec
@@ -255,7 +273,7 @@ def _solve_batch(prediction, shapes, e_hyps, e_hist, active_count, focals, pp_x,
 @torch.no_grad()
 def _localize_ragged(images, gating, experts, focal_lengths, gt_poses, gt_experts, hypotheses, threshold, inlier_alpha, inlier_beta,
                      max_reprojection, subsample, e_hyps, expert_selection, oracle_experts, generator, asynchronous, all_experts,
-                     strict_reference, rot_threshold_deg, trans_threshold_cm):
+                     strict_reference, rot_threshold_deg, trans_threshold_cm, verify_gt=False):
     """localize_batch over images of different sizes (test sets resized by their shorter edge).  The networks run once per group
     of equally sized images and write straight into the packed buffer of a ragged batch (esac.pack_frames' layout: frame b's
     [E,3,h_b,w_b] dense at the head of row b); every frame gets its own principal point (the image centre) and focal length; then
@@ -296,7 +314,8 @@ def _localize_ragged(images, gating, experts, focal_lengths, gt_poses, gt_expert
             for i, b in enumerate(members):
                 packed[b, :3 * E * h * w].view(E, 3, h, w)[e] = maps[i]
     return _solve_batch(packed, shapes, e_hyps, e_hist, active_count, focals, pp_x, pp_y, gt_poses, gt_experts, threshold, inlier_alpha,
-                        inlier_beta, max_reprojection, subsample, asynchronous, strict_reference, rot_threshold_deg, trans_threshold_cm, start)
+                        inlier_beta, max_reprojection, subsample, asynchronous, strict_reference, rot_threshold_deg, trans_threshold_cm, start,
+                        verify_gt)
 
 
 def frames_to_rerun(eval_host):
@@ -372,7 +391,7 @@ def _statistics(E, scenes_r, scenes_t, scenes_c, trans_threshold_cm, rot_thresho
 
 
 def evaluate(samples, gating, experts, trans_threshold_cm=5.0, rot_threshold_deg=5.0, pose_log=None, batch_size=1,
-             asynchronous=False, **kw):
+             asynchronous=False, verify_gt=False, **kw):
     """The statistics block of test_esac.py:249-289 over `samples` = iterable of
     (name, image, focal_length, gt_pose [4,4], gt_expert).
     batch_size > 1: batch_size consecutive samples form a batch (the last one may be short) and each batch goes through
@@ -382,11 +401,15 @@ def evaluate(samples, gating, experts, trans_threshold_cm=5.0, rot_threshold_deg
     host ONCE, after the last batch; frames whose status is 3 are run again (`rerun_frames`); the statistics and the pose-log lines
     (the format string of `pose_file_line` over the row's quaternion and translation) follow from the rows.  asynchronous: the
     batches are enqueued without a host synchronisation (localize_batch(asynchronous=True, all_experts=True)), given device images.
-    `oracle_expert=k` in **kw applies to every image, as with batch_size 1."""
+    `oracle_expert=k` in **kw applies to every image, as with batch_size 1.
+    verify_gt: every batch also scores its ground-truth poses on the true experts' maps (localize_batch(verify_gt=True); the frames
+    go through the batched route whatever batch_size is) and the result gains gt_score_higher: the share of frames whose ground
+    truth scores higher than the winner the solver returned (VERIFY_SCORE > RES_SCORE) -- frames on which the sampling failed, not
+    the scoring or the expert."""
     E = len(experts)
-    if int(batch_size) > 1:
-        return _evaluate_batched(samples, gating, experts, trans_threshold_cm, rot_threshold_deg, pose_log, int(batch_size),
-                                 asynchronous, kw)
+    if int(batch_size) > 1 or verify_gt:
+        return _evaluate_batched(samples, gating, experts, trans_threshold_cm, rot_threshold_deg, pose_log, max(int(batch_size), 1),
+                                 asynchronous, kw, verify_gt)
     scenes_r, scenes_t, scenes_c = [[] for _ in range(E)], [[] for _ in range(E)], [[] for _ in range(E)]
     avg_active = max_active = avg_time = n = 0
     for name, image, focal, gt_pose, gt_expert in samples:
@@ -404,7 +427,8 @@ def evaluate(samples, gating, experts, trans_threshold_cm=5.0, rot_threshold_deg
     return _statistics(E, scenes_r, scenes_t, scenes_c, trans_threshold_cm, rot_threshold_deg, avg_active, max_active, avg_time, n)
 
 
-def _evaluate_batched(samples, gating, experts, trans_threshold_cm, rot_threshold_deg, pose_log, batch_size, asynchronous, kw):
+def _evaluate_batched(samples, gating, experts, trans_threshold_cm, rot_threshold_deg, pose_log, batch_size, asynchronous, kw,
+                      verify_gt=False):
     E = len(experts)
     kw = dict(kw)
     oracle_expert = kw.pop("oracle_expert", None)
@@ -421,7 +445,7 @@ def _evaluate_batched(samples, gating, experts, trans_threshold_cm, rot_threshol
         out = localize_batch(images, gating, experts, [float(g[2]) for g in group], gt_poses=gts,
                              gt_experts=[int(g[4]) for g in group], asynchronous=asynchronous,
                              oracle_experts=None if oracle_expert is None else [int(oracle_expert)] * len(group),
-                             rot_threshold_deg=rot_threshold_deg, trans_threshold_cm=trans_threshold_cm, **kw)
+                             rot_threshold_deg=rot_threshold_deg, trans_threshold_cm=trans_threshold_cm, verify_gt=verify_gt, **kw)
         batches.append(out)
         names.extend(g[0] for g in group)
         gt_exp.extend(int(g[4]) for g in group)
@@ -442,15 +466,22 @@ def _evaluate_batched(samples, gating, experts, trans_threshold_cm, rot_threshol
         # one copy for the whole test set: the eval rows and the active-expert counts of every batch
         both = torch.cat([torch.cat([b["eval"], b["active_experts"].to(torch.float64).unsqueeze(1)], dim=1) for b in batches]).cpu().numpy()
         rows, active = both[:, :api.EVAL_DOUBLES].copy(), both[:, api.EVAL_DOUBLES]
+        if verify_gt:  # (a second copy, of two columns: the winners' scores and the ground truths')
+            win_gt = torch.cat([torch.stack([b["records"][:, api.RES_SCORE], b["gt_verify"][:, 0, api.VERIFY_SCORE]], dim=1) for b in batches]).cpu().numpy()
         first = 0
         for b in batches:
             size = int(b["records"].shape[0])
             for f, redo in rerun_frames(b, frames_to_rerun(rows[first:first + size])).items():
                 rows[first + f] = redo["eval"]
+                if verify_gt:
+                    win_gt[first + f, 0] = redo["record"][api.RES_SCORE]
             first += size
     else:
         rows = np.concatenate([b["eval"] for b in batches])
         active = np.concatenate([np.asarray(b["active_experts"], np.float64) for b in batches])
+        if verify_gt:
+            win_gt = np.concatenate([np.stack([b["records_host"][:, api.RES_SCORE], b["gt_verify"][:, 0, api.VERIFY_SCORE].cpu().numpy()], axis=1)
+                                     for b in batches])
     scenes_r, scenes_t, scenes_c = [[] for _ in range(E)], [[] for _ in range(E)], [[] for _ in range(E)]
     for name, ge, row in zip(names, gt_exp, rows):
         scenes_r[ge].append(float(row[api.EVAL_ROT_DEG]))
@@ -458,8 +489,11 @@ def _evaluate_batched(samples, gating, experts, trans_threshold_cm, rot_threshol
         scenes_c[ge].append(bool(row[api.EVAL_CLASS_OK] == 1.0))
         if pose_log is not None:
             pose_log.write(POSE_LINE_FORMAT % ((name,) + tuple(float(v) for v in row[api.EVAL_QUAT:api.EVAL_QUAT + 7])))
-    return _statistics(E, scenes_r, scenes_t, scenes_c, trans_threshold_cm, rot_threshold_deg, float(active.sum()),
-                       int(active.max()), time.time() - start, n)
+    stats = _statistics(E, scenes_r, scenes_t, scenes_c, trans_threshold_cm, rot_threshold_deg, float(active.sum()),
+                        int(active.max()), time.time() - start, n)
+    if verify_gt:
+        stats["gt_score_higher"] = float(np.mean(win_gt[:, 1] > win_gt[:, 0]))
+    return stats
 
 
 # ---------------------------------------------------------------- training glue (train_esac.py:104-200)

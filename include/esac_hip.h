@@ -392,6 +392,58 @@ int esac_hip_eval_batch(esac_hip_ctx* ctx, int B, const double* d_records /* [B,
                         float rot_thresh_deg, float trans_thresh_cm, void* stream, double* d_out /* DEVICE [B,ESAC_EVAL_DOUBLES] */);
 
 /*
+ * Pose verification (new, additive: the ABI version stays): how well do the scene-coordinate maps support a GIVEN pose, and how
+ * certain is it?  K poses per frame -- a ground-truth pose, the previous frame's, an odometry prediction, a hypothesis read back --
+ * each evaluated against ONE expert's map of its frame, on that frame's grid and camera.  Row [b,k] of ESAC_VERIFY_DOUBLES doubles:
+ *   ESAC_VERIFY_SCORE   the reference-arithmetic soft-inlier score (esac_util.h:235-260): what ESAC_RES_SCORE holds for the winner.
+ *                       A non-finite cell is an outlier at max_reproj; under ESAC_FLAG_STRICT_REFERENCE the score is NaN.
+ *   ESAC_VERIFY_N       cells with err < tau, err the clamped float reprojection error: the refinement's inlier rule (a NaN error is
+ *                       never an inlier).  Over THESE cells, in fp64, with (ex, ey) = projection - pixel and its Jacobian rows Ju, Jv
+ *                       with respect to (rvec, tvec) -- the LM's own parameters:
+ *   ESAC_VERIFY_SSE     sum of ex^2 + ey^2
+ *   ESAC_VERIFY_A       the 21 upper-triangle entries, row-major, of A = sum of Ju^T Ju + Jv^T Jv
+ *   ESAC_VERIFY_SIGMA2  SSE / (2 n - 6)
+ *   ESAC_VERIFY_C       the 6x6 covariance sigma^2 A^-1 of (rvec, tvec), row-major, both triangles
+ *   ESAC_VERIFY_STATUS  ESAC_VERIFY_OK; _FEW: n < 4 -- score, n, SSE and A stand, sigma^2 and C are NaN; _PINV: A is rank deficient
+ *                       to rounding (e.g. collinear inliers) and C is sigma^2 times its pseudo-inverse (eigenvalues below 2 eps
+ *                       sum|w| dropped); _BAD_POSE: the pose is not finite, or its 4x4 is singular; _BAD_EXPERT: the expert is
+ *                       outside [0,E).  Under the last two every figure is NaN.  They are outcomes of THAT row, like the record
+ *                       flags of esac_hip_backward_batch_dev: the other rows of the call are unaffected and nothing is read out of
+ *                       bounds (the expert is checked before an address is formed from it).
+ *   doubles 5 and 27 are reserved and written 0.
+ * d_sc         DEVICE, frame b's [E,3,H,W] maps at d_sc + b * sc_frame_stride (elements; 0: every frame reads the same maps); a
+ *              ragged call: the packed rows of esac_hip_forward_batch_shapes, dense [E,3,h_b,w_b] per frame.
+ * d_poses      DEVICE.  ESAC_VERIFY_POSE_RT: double [B,K,6], rvec | tvec, scene -> camera (ESAC_RES_RVEC, ESAC_BUF_HYPS);
+ *              ESAC_VERIFY_POSE_4X4: float [B,K,4,4] CAMERA poses as outPose and gtPoses carry them, inverted on the device (general
+ *              inverse, nearest rotation, Rodrigues: the training path's treatment of a ground-truth pose).
+ * d_experts    DEVICE int32 [B,K]: the map each pose is held against.
+ * p            ONE frame, as in esac_hip_forward_batch.  Read: E, H, W, shift_x, shift_y, focal, ppx, ppy, inlier_thresh,
+ *              inlier_alpha, inlier_beta, max_reproj, sub_sampling and ESAC_FLAG_STRICT_REFERENCE of flags (the flag word must
+ *              be a legal forward call's).  Everything else is ignored, N included.
+ * cams         HOST, B records or NULL, as in esac_hip_forward_batch_cams (copied before the call returns; the five camera fields of
+ *              p are then ignored).  ragged != 0: reserved[0..1] of record b is frame b's grid h_b x w_b and p's H * W the capacity,
+ *              with the layout and the per-frame checks of esac_hip_forward_batch_shapes; the table is then required.
+ * d_out        DEVICE double [B,K,ESAC_VERIFY_DOUBLES].
+ * One launch on `stream`, asynchronous, a workgroup per row: no allocation on the calling path after the first call with a table,
+ * no wait but the one on the PREVIOUS verify call's table copy having left its staging buffer.  Everything is read in stream
+ * order, so the call may be enqueued right behind an asynchronous esac_hip_forward_batch* and read its records' poses.  It touches
+ * no hypothesis, score or result workspace of the context: esac_hip_read after it returns what it returned before.  A row is a
+ * function of its pose, map, grid and camera alone (fixed summation order): the same in any batch, run to run.
+ * -1: null ctx or p.  -4 before anything is launched, naming the argument: B outside [1,ESAC_MAX_BATCH], K outside
+ * [1,ESAC_VERIFY_MAX_POSES], an unknown pose_format, a null d_sc, d_poses, d_experts or d_out, ragged without a table, a negative
+ * stride; then the parameter block, the table and the grids with the codes and messages of the forward batch calls.
+ */
+#define ESAC_VERIFY_DOUBLES 64
+#define ESAC_VERIFY_MAX_POSES 1024
+enum { ESAC_VERIFY_SCORE = 0, ESAC_VERIFY_N = 1, ESAC_VERIFY_SSE = 2, ESAC_VERIFY_SIGMA2 = 3, ESAC_VERIFY_STATUS = 4 /* 5 reserved */,
+       ESAC_VERIFY_A = 6 /* 21 values; 27 reserved */, ESAC_VERIFY_C = 28 /* 36 values */ };
+enum { ESAC_VERIFY_OK = 0, ESAC_VERIFY_FEW = 1, ESAC_VERIFY_PINV = 2, ESAC_VERIFY_BAD_POSE = 3, ESAC_VERIFY_BAD_EXPERT = 4 };
+enum { ESAC_VERIFY_POSE_RT = 0, ESAC_VERIFY_POSE_4X4 = 1 };
+int esac_hip_verify_batch(esac_hip_ctx* ctx, int B, int K, const float* d_sc, int64_t sc_frame_stride, const void* d_poses,
+                          int pose_format, const int32_t* d_experts, const esac_hip_params* p, const esac_hip_frame_cam* cams,
+                          int ragged, void* stream, double* d_out);
+
+/*
  * esac_backward (esac.cpp:213-520): expected pose loss over the hypothesis distribution and its gradient wrt the
  * scene coordinates, everything on the device.
  * Status -10: hypAssignment held a value outside [0,E) (the reference reads out of bounds there).
