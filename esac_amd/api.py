@@ -168,6 +168,28 @@ def packed_stride(E, shapes):
     return (3 * int(E) * max(h * w for h, w in shapes) + 3) // 4 * 4
 
 
+def _frame_table(who, params, cams, shapes, B):
+    """The per-frame table whose pointer goes to the library, and the call's ragged flag: (None, 0) without cams and shapes;
+    (the B records of cams, 0) with cams alone -- not copied: the library copies the table before it returns --; with shapes
+    (a ragged call) a table of this call's own, flag 1: a COPY of cams (the caller's table keeps its padding), or the camera
+    of `params` broadcast to B records, with frame b's (h, w) in reserved[b, :2].  shapes: what _shapes_arg returned -- every
+    caller has judged them where its own order of checks wants it (a second pass costs 10 us per 32 frames).  Raises
+    RuntimeError naming cams."""
+    if shapes is None:
+        return (None if cams is None else _cams_arg(cams, B, who)), 0
+    if cams is None:
+        table = make_cams([params.shift_x] * B, [params.shift_y] * B, [params.focal] * B, [params.ppx] * B, [params.ppy] * B)
+    else:
+        table = _cams_arg(cams, B, who).copy()
+    table["reserved"][:, :2] = np.asarray(shapes, np.int32)
+    return table, 1
+
+
+def _frame_stride(sc):
+    """Floats from one frame's maps to the next: the row stride of [B,E,3,H,W] or of a packed [B,S]; 0: one [E,3,H,W] shared by all."""
+    return int(sc.stride(0)) if sc.dim() in (5, 2) else 0
+
+
 def _ragged_maps(who, maps):
     """A list of B float32 [E,3,h_b,w_b] tensors with one E.  Returns (E, shapes); RuntimeError naming sceneCoordinates otherwise."""
     if not isinstance(maps, (list, tuple)) or len(maps) == 0:
@@ -415,6 +437,10 @@ class Engine:
         # accessor<> honours strides (incl. the stride-0 expand() of test_esac.py:171-173); the kernels want dense
         return (sc if sc.is_contiguous() else sc.contiguous()), (ha if ha.is_contiguous() else ha.contiguous())
 
+    def _on_device(self, t):
+        """`t` dense on a device: as it is when it lives on one, else uploaded to this engine's (non_blocking)."""
+        return (t if t.is_cuda else t.to(self.device, non_blocking=True)).contiguous()
+
     # -- whole path
     def forward_device(self, scene_coords, hyp_assign, params, scores_out=None, result_out=None, want_host=True):
         """scene_coords [E,3,H,W] f32 / hyp_assign [N] i64 on this device. Returns host result (np.float64[32]) or None."""
@@ -437,32 +463,22 @@ class Engine:
         frame b uses cams[b] and the five fields of `params` are ignored (esac_hip_forward_batch_cams).
         shapes: None, or B (h, w) pairs -- a ragged batch (esac_hip_forward_batch_shapes): scene_coords is the packed [B,S] tensor
         of pack_frames, params.H * params.W the capacity in cells (capacity_shape), frame b's grid is shapes[b]."""
-        sc = scene_coords if scene_coords.is_cuda else scene_coords.to(self.device, non_blocking=True)
-        ha = hyp_assign if hyp_assign.is_cuda else hyp_assign.to(self.device, non_blocking=True)
-        sc, ha = sc.contiguous(), ha.contiguous()
+        who = "esac.forward_batch"
+        sc, ha = self._on_device(scene_coords), self._on_device(hyp_assign)
         B = int(ha.shape[0])
-        stride = int(sc.stride(0)) if sc.dim() == 5 else 0
         host = np.zeros((B, RES_DOUBLES), np.float64) if want_host else None
         outs = (scores_out.data_ptr() if scores_out is not None else None,
                 result_out.data_ptr() if result_out is not None else None, host.ctypes.data if want_host else None)
         if shapes is not None:
-            who = "esac.forward_batch"
             shapes = _shapes_arg(who, shapes, B)
             if sc.dim() != 2 or sc.shape[0] != B:
                 raise RuntimeError("%s: with shapes, scene_coords must be the packed [B,S] tensor (pack_frames), found %s" % (who, list(sc.shape)))
-            if cams is None:
-                cams = make_cams([params.shift_x] * B, [params.shift_y] * B, [params.focal] * B, [params.ppx] * B, [params.ppy] * B)
-            else:
-                cams = _cams_arg(cams, B, who).copy()  # (the caller's table keeps its padding)
-            cams["reserved"][:, :2] = np.asarray(shapes, np.int32)
-            self._call(self.lib.esac_hip_forward_batch_shapes, B, sc.data_ptr(), int(sc.stride(0)), ha.data_ptr(), C.byref(params),
-                       cams.ctypes.data, self._stream(), *outs)
-        elif cams is None:
-            self._call(self.lib.esac_hip_forward_batch, B, sc.data_ptr(), stride, ha.data_ptr(), C.byref(params), self._stream(), *outs)
+        table, ragged = _frame_table(who, params, cams, shapes, B)
+        if table is None:
+            self._call(self.lib.esac_hip_forward_batch, B, sc.data_ptr(), _frame_stride(sc), ha.data_ptr(), C.byref(params), self._stream(), *outs)
         else:
-            cams = _cams_arg(cams, B, "esac.forward_batch")  # (the library copies the table before it returns)
-            self._call(self.lib.esac_hip_forward_batch_cams, B, sc.data_ptr(), stride, ha.data_ptr(), C.byref(params),
-                       cams.ctypes.data, self._stream(), *outs)
+            self._call(self.lib.esac_hip_forward_batch_shapes if ragged else self.lib.esac_hip_forward_batch_cams, B, sc.data_ptr(),
+                       _frame_stride(sc), ha.data_ptr(), C.byref(params), table.ctypes.data, self._stream(), *outs)
         self._keep = (sc, ha)
         return host
 
@@ -480,10 +496,10 @@ class Engine:
         armed, self._pose_arm = self._pose_arm, None
         return given if given is not None else armed
 
-    def _arm_pose_records(self, who, name, records, B, device_only):
-        """Arms the next training call (esac_hip_set_bwd_pose_records) with `records` -- or, for a CPU tensor, with a device
-        staging tensor the caller copies back from after the call's own wait.  Returns the device tensor the kernel writes."""
-        _check_pose_records(who, name, records, B, device_only, self.device)
+    def _arm_pose_records(self, records, B):
+        """Arms the next training call (esac_hip_set_bwd_pose_records) with `records` (checked by the caller: _check_pose_records)
+        -- or, for a CPU tensor, with a device staging tensor the caller copies back from after the call's own wait.  Returns the
+        device tensor the kernel writes."""
         dev = records if records.is_cuda else torch.empty(tuple(records.shape), dtype=torch.float64, device=self.device)
         self._call(self.lib.esac_hip_set_bwd_pose_records, dev.data_ptr(), 1 if B is None else int(B))
         return dev
@@ -504,7 +520,7 @@ class Engine:
             raise RuntimeError("esac.backward: the gradient tensor must be a dense float32 device tensor shaped like sceneCoordinates")
         gt = np.ascontiguousarray(np.asarray(gt_pose, np.float32).reshape(16))
         host = np.zeros(4, np.float64) if want_host else None
-        rec_dev = self._arm_pose_records("esac.backward", "poseRecord", pose_record, None, not want_host) if pose_record is not None else None
+        rec_dev = self._arm_pose_records(pose_record, None) if pose_record is not None else None
         # (the library makes the context's GPU current itself: no torch device guard on the call path, as in forward_device)
         rc = self.lib.esac_hip_backward(
             self.ctx, sc.data_ptr(), out_gradients.data_ptr(), ha.data_ptr(), gt.ctypes.data,
@@ -520,23 +536,19 @@ class Engine:
     def _batch_inputs(self, who, scene_coords, out_gradients, hyp_assign):
         """The device inputs of a batched training call: dense scene coordinates and assignment on this device, the checked
         gradient tensor's batch size B and the coordinates' frame stride (0: one [E,3,H,W] shared by all frames)."""
-        sc = scene_coords if scene_coords.is_cuda else scene_coords.to(self.device, non_blocking=True)
-        ha = hyp_assign if hyp_assign.is_cuda else hyp_assign.to(self.device, non_blocking=True)
-        sc, ha = sc.contiguous(), ha.contiguous()
+        sc, ha = self._on_device(scene_coords), self._on_device(hyp_assign)
         B = int(ha.shape[0])
         if not (out_gradients.is_cuda and out_gradients.is_contiguous() and out_gradients.dtype == torch.float32
                 and out_gradients.dim() == 5 and out_gradients.shape[0] == B and tuple(out_gradients.shape[1:]) == tuple(sc.shape[-4:])):
             raise RuntimeError("%s: the gradient tensor must be a dense float32 device tensor [B,E,3,H,W]" % who)
-        return sc, ha, B, int(sc.stride(0)) if sc.dim() == 5 else 0
+        return sc, ha, B, _frame_stride(sc)
 
-    def _ragged_batch_inputs(self, who, scene_coords, out_gradients, hyp_assign, params, cams, shapes):
-        """The device inputs of a ragged training batch: the packed maps and the packed gradients (both [B,S'] float32 on this
-        device, rows contiguous; frame b dense at the head of row b) and the camera table with every frame's grid in it."""
-        sc = scene_coords if scene_coords.is_cuda else scene_coords.to(self.device, non_blocking=True)
-        ha = hyp_assign if hyp_assign.is_cuda else hyp_assign.to(self.device, non_blocking=True)
-        sc, ha = sc.contiguous(), ha.contiguous()
+    def _ragged_batch_inputs(self, who, scene_coords, out_gradients, hyp_assign, params, shapes):
+        """The device inputs of a ragged training batch: the packed maps and the checked packed gradients (both [B,S'] float32 on
+        this device, rows contiguous; frame b dense at the head of row b), B and the maps' frame stride.  shapes: the (h, w) pairs
+        the public method has checked (_shapes_arg)."""
+        sc, ha = self._on_device(scene_coords), self._on_device(hyp_assign)
         B = int(ha.shape[0])
-        shapes = _shapes_arg(who, shapes, B)
         if sc.dim() != 2 or sc.shape[0] != B:
             raise RuntimeError("%s: with shapes, scene_coords must be the packed [B,S] tensor (pack_frames), found %s" % (who, list(sc.shape)))
         g = out_gradients
@@ -544,12 +556,7 @@ class Engine:
                 and g.shape[0] == B and g.is_contiguous() and g.shape[1] >= 3 * params.E * max(h * w for h, w in shapes)):
             raise RuntimeError("%s: with shapes, the gradient tensor must be a packed float32 [B,S] tensor on this device, contiguous, "
                                "S >= 3*E*max(h*w)" % who)
-        if cams is None:
-            cams = make_cams([params.shift_x] * B, [params.shift_y] * B, [params.focal] * B, [params.ppx] * B, [params.ppy] * B)
-        else:
-            cams = _cams_arg(cams, B, who).copy()  # (the caller's table keeps its padding)
-        cams["reserved"][:, :2] = np.asarray(shapes, np.int32)
-        return sc, ha, B, cams
+        return sc, ha, B, _frame_stride(sc)
 
     def backward_batch(self, scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, cams=None,
                        pose_records=None):
@@ -576,31 +583,26 @@ class Engine:
     def _backward_batch(self, scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, cams, pose_records, shapes):
         pose_records = self._take_pose_arm(pose_records)
         if shapes is not None:
-            sc, ha, B, cams = self._ragged_batch_inputs("esac.backward_batch_shapes", scene_coords, out_gradients, hyp_assign, params, cams, shapes)
-            sc_stride = int(sc.stride(0))
+            who = "esac.backward_batch_shapes"
+            sc, ha, B, sc_stride = self._ragged_batch_inputs(who, scene_coords, out_gradients, hyp_assign, params, shapes)
+            table, ragged = _frame_table(who, params, cams, shapes, B)
         else:
             sc, ha, B, sc_stride = self._batch_inputs("esac.backward_batch", scene_coords, out_gradients, hyp_assign)
         gt = np.ascontiguousarray(np.asarray(gt_poses, np.float32).reshape(-1))
         if gt.size != 16 * B:
             raise RuntimeError("esac.backward_batch: gtPoses must hold B 4x4 poses")
         host = np.zeros((B, 4), np.float64)
-        if cams is not None and shapes is None:
-            cams = _cams_arg(cams, B, "esac.backward_batch")
-        rec_dev = self._arm_pose_records("esac.backward_batch", "poseRecords", pose_records, B, False) if pose_records is not None else None
-        if shapes is not None:
-            rc = self.lib.esac_hip_backward_batch_shapes(
-                self.ctx, B, sc.data_ptr(), sc_stride, out_gradients.data_ptr(), int(out_gradients.stride(0)), ha.data_ptr(),
-                gt.ctypes.data, cams.ctypes.data, float(w_rot), float(w_trans), float(loss_cut), C.byref(params), self._stream(),
-                host.ctypes.data)
-        elif cams is None:
-            rc = self.lib.esac_hip_backward_batch(
-                self.ctx, B, sc.data_ptr(), sc_stride, out_gradients.data_ptr(), int(out_gradients.stride(0)), ha.data_ptr(),
-                gt.ctypes.data, float(w_rot), float(w_trans), float(loss_cut), C.byref(params), self._stream(), host.ctypes.data)
-        else:
-            rc = self.lib.esac_hip_backward_batch_cams(
-                self.ctx, B, sc.data_ptr(), sc_stride, out_gradients.data_ptr(), int(out_gradients.stride(0)), ha.data_ptr(),
-                gt.ctypes.data, cams.ctypes.data, float(w_rot), float(w_trans), float(loss_cut), C.byref(params), self._stream(),
-                host.ctypes.data)
+        if shapes is None:  # (a shared-shape call's cams are judged behind its gtPoses, as ever)
+            table, ragged = _frame_table("esac.backward_batch", params, cams, None, B)
+        rec_dev = None
+        if pose_records is not None:
+            _check_pose_records("esac.backward_batch", "poseRecords", pose_records, B, False, self.device)
+            rec_dev = self._arm_pose_records(pose_records, B)
+        fn = self.lib.esac_hip_backward_batch if table is None else \
+            self.lib.esac_hip_backward_batch_shapes if ragged else self.lib.esac_hip_backward_batch_cams
+        rc = fn(self.ctx, B, sc.data_ptr(), sc_stride, out_gradients.data_ptr(), int(out_gradients.stride(0)), ha.data_ptr(),
+                gt.ctypes.data, *(() if table is None else (table.ctypes.data,)), float(w_rot), float(w_trans), float(loss_cut),
+                C.byref(params), self._stream(), host.ctypes.data)
         self._keep = (sc, ha, out_gradients, rec_dev)
         if rec_dev is not None and rec_dev is not pose_records and rc in (0, -10):  # (-10: raised after every frame has run)
             pose_records.copy_(rec_dev)
@@ -634,22 +636,15 @@ class Engine:
     def _backward_batch_async(self, scene_coords, out_gradients, hyp_assign, gt_poses, w_rot, w_trans, loss_cut, params, cams, out, shapes):
         pose_records = self._take_pose_arm(None)
         if shapes is not None:
-            sc, ha, B, ragged_cams = self._ragged_batch_inputs("esac.backward_batch_shapes_async", scene_coords, out_gradients, hyp_assign, params, cams, shapes)
-            sc_stride = int(sc.stride(0))
+            who = "esac.backward_batch_shapes_async"
+            sc, ha, B, sc_stride = self._ragged_batch_inputs(who, scene_coords, out_gradients, hyp_assign, params, shapes)
+            table, ragged = _frame_table(who, params, cams, shapes, B)
         else:
             sc, ha, B, sc_stride = self._batch_inputs("esac.backward_batch_async", scene_coords, out_gradients, hyp_assign)
         if pose_records is not None:
             _check_pose_records("esac.backward_batch_async", "poseRecords", pose_records, B, True, self.device)
-        if isinstance(gt_poses, torch.Tensor) and gt_poses.is_cuda:
-            gt = gt_poses
-        else:
-            # through pinned staging (torch's caching host allocator keeps it until the copy has run): the caller's array is free
-            # when the call returns, and the upload is a true asynchronous copy on the launch stream
-            host = gt_poses.detach() if isinstance(gt_poses, torch.Tensor) else torch.from_numpy(np.asarray(gt_poses, np.float32))
-            pin = torch.empty(tuple(host.shape), dtype=torch.float32, pin_memory=True)
-            pin.copy_(host)
-            with torch.cuda.device(self.device):
-                gt = pin.to(self.device, non_blocking=True)
+        gt = gt_poses if isinstance(gt_poses, torch.Tensor) and gt_poses.is_cuda else \
+            self._upload(gt_poses if isinstance(gt_poses, torch.Tensor) else np.asarray(gt_poses, np.float32), torch.float32)
         if gt.dtype != torch.float32 or gt.numel() != 16 * B:
             raise RuntimeError("esac.backward_batch_async: gtPoses must hold B float32 4x4 poses")
         gt = gt.contiguous()
@@ -657,14 +652,11 @@ class Engine:
             out = torch.empty((B, 4), dtype=torch.float64, device=self.device)
         elif not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (B, 4)):
             raise RuntimeError("esac.backward_batch_async: out must be a dense float64 device tensor [B,4]")
-        table = None
-        if shapes is not None:
-            table = ragged_cams
-        elif cams is not None:
-            table = _cams_arg(cams, B, "esac.backward_batch_async")
+        if shapes is None:  # (a shared-shape call's cams are judged behind gtPoses and out, as ever)
+            table, ragged = _frame_table("esac.backward_batch_async", params, cams, None, B)
         if pose_records is not None:
-            self._arm_pose_records("esac.backward_batch_async", "poseRecords", pose_records, B, True)
-        rc = (self.lib.esac_hip_backward_batch_dev_shapes if shapes is not None else self.lib.esac_hip_backward_batch_dev)(
+            self._arm_pose_records(pose_records, B)
+        rc = (self.lib.esac_hip_backward_batch_dev_shapes if ragged else self.lib.esac_hip_backward_batch_dev)(
             self.ctx, B, sc.data_ptr(), sc_stride, out_gradients.data_ptr(), int(out_gradients.stride(0)), ha.data_ptr(),
             gt.data_ptr(), table.ctypes.data if table is not None else None, float(w_rot), float(w_trans), float(loss_cut),
             C.byref(params), self._stream(), out.data_ptr())
@@ -723,10 +715,8 @@ class Engine:
         (`out` when given; columns: VERIFY_*)."""
         who = "esac.verify_batch"
         B, K, fmt = _check_verify_args(who, scene_coords, poses, experts, shapes, out)
-        sc = scene_coords if scene_coords.is_cuda else scene_coords.to(self.device, non_blocking=True)
-        sc = sc.contiguous()
-        po = poses if poses.is_cuda else self._upload(poses, poses.dtype)
-        po = po.contiguous()
+        sc = self._on_device(scene_coords)
+        po = (poses if poses.is_cuda else self._upload(poses, poses.dtype)).contiguous()
         ex = experts if isinstance(experts, torch.Tensor) and experts.is_cuda else \
             self._upload(torch.as_tensor(np.asarray(experts, np.int64) if not isinstance(experts, torch.Tensor) else experts).clamp(-1, 2 ** 31 - 1), torch.int32)
         if ex.dtype != torch.int32:
@@ -740,19 +730,8 @@ class Engine:
                 raise RuntimeError("%s: %s lives on %s, this engine on %s" % (who, name, t.device, self.device))
         if out is None:
             out = torch.empty((B, K, VERIFY_DOUBLES), dtype=torch.float64, device=self.device)
-        table, ragged = None, 0
-        if shapes is not None:
-            shapes = _shapes_arg(who, shapes, B)
-            if cams is None:
-                cams = make_cams([params.shift_x] * B, [params.shift_y] * B, [params.focal] * B, [params.ppx] * B, [params.ppy] * B)
-            else:
-                cams = _cams_arg(cams, B, who).copy()  # (the caller's table keeps its padding)
-            cams["reserved"][:, :2] = np.asarray(shapes, np.int32)
-            table, ragged = cams, 1
-        elif cams is not None:
-            table = _cams_arg(cams, B, who)  # (the library copies the table before it returns)
-        stride = int(sc.stride(0)) if sc.dim() in (5, 2) else 0
-        self._call(self.lib.esac_hip_verify_batch, B, K, sc.data_ptr(), stride, po.data_ptr(), fmt, ex.data_ptr(), C.byref(params),
+        table, ragged = _frame_table(who, params, cams, shapes if shapes is None else _shapes_arg(who, shapes, B), B)
+        self._call(self.lib.esac_hip_verify_batch, B, K, sc.data_ptr(), _frame_stride(sc), po.data_ptr(), fmt, ex.data_ptr(), C.byref(params),
                    table.ctypes.data if table is not None else None, ragged, self._stream(), out.data_ptr())
         self._keep_verify = (sc, po, ex, out)  # alive until the kernel has run
         return out
@@ -1098,6 +1077,54 @@ def engine(device=None):
     return eng
 
 
+def _engine_for(*inputs):
+    """The engine of the first device tensor among `inputs` (tensors, or lists of tensors), else the current GPU's."""
+    for x in inputs:
+        for t in x if isinstance(x, (list, tuple)) else (x,):
+            if isinstance(t, torch.Tensor) and t.is_cuda:
+                return engine(t.device.index)
+    return engine(None)
+
+
+def _call_params(eng, E, H, W, N, cam_scalars, score_args, *, training):
+    """One call's parameter block from the module state: seed, call counter (read, not advanced), limits and the strict mode of
+    the path -- training: set_strict_training's, otherwise set_strict_reference's."""
+    strict = {"strict_training": _state["strict_training"]} if training else {"strict_reference": _state["strict_reference"]}
+    return eng.make_params(E, H, W, N, *cam_scalars, *score_args, seed=_state["seed"], call=_state["call"],
+                           max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"], **strict)
+
+
+def _stage_gradients(outGradients, eng):
+    """The gradient tensor the kernels accumulate into: (outGradients, False) when it is dense on eng's device, else (a dense
+    device copy, True) -- the caller then copies it back into its own (CPU or strided) storage after the call."""
+    if outGradients.is_cuda and outGradients.is_contiguous() and outGradients.device == eng.device:
+        return outGradients, False
+    return outGradients.to(eng.device).contiguous(), True
+
+
+def _check_assignment_range(who, hypAssignment, E):
+    """A host hypAssignment must lie in [0,E) (a device one is judged by the kernels: no round trip).  Touches no device."""
+    if not hypAssignment.is_cuda:
+        lo, hi = int(hypAssignment.min()), int(hypAssignment.max())
+        if lo < 0 or hi >= E:
+            raise RuntimeError("%s: hypAssignment values must lie in [0,%d), found [%d,%d]" % (who, E, lo, hi))
+
+
+def _check_async_tensors(who, sceneCoordinates, outGradients, hypAssignment, gtPoses, host_gradients):
+    """What an asynchronous training call asks of its tensors: a contiguous outGradients, the first three on a device, all on
+    one device.  host_gradients: the call's own words for an outGradients on the host.  Touches no device."""
+    if not outGradients.is_contiguous():
+        raise RuntimeError("%s: outGradients must be contiguous (an asynchronous call cannot copy back into strided storage)" % who)
+    for name, t, why in (("outGradients", outGradients, host_gradients),
+                         ("sceneCoordinates", sceneCoordinates, "stages nothing on the host"),
+                         ("hypAssignment", hypAssignment, "stages nothing on the host")):
+        if not t.is_cuda:
+            raise RuntimeError("%s: %s must be a device tensor (an asynchronous call %s)" % (who, name, why))
+    if outGradients.device != sceneCoordinates.device or hypAssignment.device != sceneCoordinates.device or \
+            (gtPoses.is_cuda and gtPoses.device != sceneCoordinates.device):
+        raise RuntimeError("%s: sceneCoordinates, outGradients, hypAssignment and a device gtPoses must live on one device" % who)
+
+
 def last_result():
     """Details of the most recent forward(): scores tensor (device, float64 [N]; a buffer the next call with the same
     signature overwrites -- clone it to keep it) and the result record."""
@@ -1280,24 +1307,34 @@ def _ragged_call(who, sceneCoordinates, hypAssignment, shapes, experts, cam_args
     if B > MAX_BATCH:
         raise RuntimeError("%s: hypAssignment holds %d frames, at most %d per call" % (who, B, MAX_BATCH))
     E, shapes = _ragged_args(who, sceneCoordinates, B, shapes, experts)
-    (shiftX, shiftY, focalLength, ppointX, ppointY), cams = _per_frame_cams(who, B, *cam_args)
-    if isinstance(sceneCoordinates, (list, tuple)):
-        on_dev = [m.device.index for m in sceneCoordinates if m.is_cuda]
-        eng = engine(on_dev[0] if on_dev else None)
-        packed, _ = pack_frames(sceneCoordinates, device=eng.device)
-    else:
-        eng = engine(sceneCoordinates.device.index if sceneCoordinates.is_cuda else None)
-        packed = sceneCoordinates
-    H, W = capacity_shape(shapes)
-    p = eng.make_params(E, H, W, N, shiftX, shiftY, focalLength, ppointX, ppointY, *score_args, seed=_state["seed"],
-                        call=_state["call"], max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"],
-                        strict_reference=_state["strict_reference"])
+    cam_scalars, cams = _per_frame_cams(who, B, *cam_args)
+    eng = _engine_for(sceneCoordinates)
+    packed = pack_frames(sceneCoordinates, device=eng.device)[0] if isinstance(sceneCoordinates, (list, tuple)) else sceneCoordinates
+    p = _call_params(eng, E, *capacity_shape(shapes), N, cam_scalars, score_args, training=False)
     first = _state["call"]
     scores = torch.empty(B, N, dtype=torch.float64, device=eng.device)
     # (zeros: a frame whose kernels never reach the record write reads RES_VALID = 0 -> EVAL_STATUS 1, not stale memory)
     records = None if want_host else torch.zeros(B, RES_DOUBLES, dtype=torch.float64, device=eng.device)
     res = eng.forward_batch(packed, hypAssignment, p, scores_out=scores, result_out=records, want_host=want_host, cams=cams, shapes=shapes)
     _state["call"] += B  # (behind the call: a table the library refuses -- a frame's camera beyond its own pixel range -- draws no RNG stream)
+    return res, records, scores, first
+
+
+def _shared_call(who, sceneCoordinates, hypAssignment, cam_args, score_args, want_host):
+    """forward_batch / forward_batch_async without shapes, from the batch-size check on: returns what _ragged_call returns."""
+    B, N = hypAssignment.shape
+    if sceneCoordinates.dim() == 5 and sceneCoordinates.size(0) != B:
+        raise RuntimeError("%s: batch sizes of sceneCoordinates and hypAssignment differ" % who)
+    cam_scalars, cams = _per_frame_cams(who, B, *cam_args)
+    eng = _engine_for(sceneCoordinates)
+    E, H, W = sceneCoordinates.shape[-4], sceneCoordinates.shape[-2], sceneCoordinates.shape[-1]
+    p = _call_params(eng, E, H, W, N, cam_scalars, score_args, training=False)
+    first = _state["call"]
+    _state["call"] += B  # (ahead of the call: a shared-shape batch draws its B streams even if the library then refuses)
+    scores = torch.empty(B, N, dtype=torch.float64, device=eng.device)
+    # (zeros, as in _ragged_call)
+    records = None if want_host else torch.zeros(B, RES_DOUBLES, dtype=torch.float64, device=eng.device)
+    res = eng.forward_batch(sceneCoordinates, hypAssignment, p, scores_out=scores, result_out=records, want_host=want_host, cams=cams)
     return res, records, scores, first
 
 
@@ -1315,36 +1352,21 @@ def forward_batch(sceneCoordinates, hypAssignment, outPoses, shiftX, shiftY, foc
     S // (3 * the largest h*w)).  Everything else, and every return value, as without shapes."""
     if not isinstance(hypAssignment, torch.Tensor) or hypAssignment.dim() != 2 or hypAssignment.dtype != torch.int64:
         raise RuntimeError("esac.forward_batch: hypAssignment must be int64 [B,N]")
+    B = hypAssignment.shape[0]
+    cam_args = (shiftX, shiftY, focalLength, ppointX, ppointY)
+    score_args = (inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling)
     if shapes is not None:
-        B, N = hypAssignment.shape
         if not isinstance(outPoses, torch.Tensor) or outPoses.dtype != torch.float32 or tuple(outPoses.shape) != (B, 4, 4):
             raise RuntimeError("esac.forward_batch: outPoses must be float32 [B,4,4]")
-        res, _, scores, _ = _ragged_call("esac.forward_batch", sceneCoordinates, hypAssignment, shapes, experts,
-                                         (shiftX, shiftY, focalLength, ppointX, ppointY),
-                                         (inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling), True)
-        outPoses.copy_(torch.from_numpy(res[:, RES_POSE:RES_POSE + 16].astype(np.float32).reshape(B, 4, 4)))
-        _state["last"] = {"scores": scores, "result": res}
-        return [int(v) for v in res[:, RES_EXPERT]]
-    if experts is not None:
-        raise RuntimeError("esac.forward_batch: experts is an argument of a ragged batch (shapes=...)")
-    if sceneCoordinates.dtype != torch.float32 or sceneCoordinates.dim() not in (4, 5) or sceneCoordinates.size(-3) != 3:
-        raise RuntimeError("esac.forward_batch: sceneCoordinates must be float32 [B,E,3,H,W] or [E,3,H,W]")
-    B, N = hypAssignment.shape
-    if outPoses.dtype != torch.float32 or tuple(outPoses.shape) != (B, 4, 4):
-        raise RuntimeError("esac.forward_batch: outPoses must be float32 [B,4,4]")
-    if sceneCoordinates.dim() == 5 and sceneCoordinates.size(0) != B:
-        raise RuntimeError("esac.forward_batch: batch sizes of sceneCoordinates and hypAssignment differ")
-    (shiftX, shiftY, focalLength, ppointX, ppointY), cams = _per_frame_cams("esac.forward_batch", B, shiftX, shiftY, focalLength,
-                                                                            ppointX, ppointY)
-    eng = engine(sceneCoordinates.device.index if sceneCoordinates.is_cuda else None)
-    E, H, W = sceneCoordinates.shape[-4], sceneCoordinates.shape[-2], sceneCoordinates.shape[-1]
-    p = eng.make_params(E, H, W, N, shiftX, shiftY, focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha,
-                        inlierBeta, maxReproj, subSampling, seed=_state["seed"], call=_state["call"],
-                        max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"],
-                        strict_reference=_state["strict_reference"])
-    _state["call"] += B
-    scores = torch.empty(B, N, dtype=torch.float64, device=eng.device)
-    res = eng.forward_batch(sceneCoordinates, hypAssignment, p, scores_out=scores, cams=cams)
+        res, _, scores, _ = _ragged_call("esac.forward_batch", sceneCoordinates, hypAssignment, shapes, experts, cam_args, score_args, True)
+    else:
+        if experts is not None:
+            raise RuntimeError("esac.forward_batch: experts is an argument of a ragged batch (shapes=...)")
+        if sceneCoordinates.dtype != torch.float32 or sceneCoordinates.dim() not in (4, 5) or sceneCoordinates.size(-3) != 3:
+            raise RuntimeError("esac.forward_batch: sceneCoordinates must be float32 [B,E,3,H,W] or [E,3,H,W]")
+        if outPoses.dtype != torch.float32 or tuple(outPoses.shape) != (B, 4, 4):
+            raise RuntimeError("esac.forward_batch: outPoses must be float32 [B,4,4]")
+        res, _, scores, _ = _shared_call("esac.forward_batch", sceneCoordinates, hypAssignment, cam_args, score_args, True)
     outPoses.copy_(torch.from_numpy(res[:, RES_POSE:RES_POSE + 16].astype(np.float32).reshape(B, 4, 4)))
     _state["last"] = {"scores": scores, "result": res}
     return [int(v) for v in res[:, RES_EXPERT]]
@@ -1375,25 +1397,17 @@ def backward(sceneCoordinates, outGradients, hypAssignment, gtPose, wLossRot, wL
     if poseRecord is not None:
         _check_pose_records("esac.backward", "poseRecord", poseRecord, None, False,
                             sceneCoordinates.device if sceneCoordinates.is_cuda else None)
-    dev = sceneCoordinates.device.index if sceneCoordinates.is_cuda else None
-    eng = engine(dev)
+    eng = _engine_for(sceneCoordinates)
     E, _, H, W = sceneCoordinates.shape
-    N = hypAssignment.shape[0]
-    if not hypAssignment.is_cuda:
-        lo, hi = int(hypAssignment.min()), int(hypAssignment.max())
-        if lo < 0 or hi >= E:
-            raise RuntimeError("esac.backward: hypAssignment values must lie in [0,%d), found [%d,%d]" % (E, lo, hi))
-    p = eng.make_params(E, H, W, N, shiftX, shiftY, focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha,
-                        inlierBeta, maxReproj, subSampling, seed=_state["seed"], call=_state["call"],
-                        max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"],
-                        strict_training=_state["strict_training"])
+    _check_assignment_range("esac.backward", hypAssignment, E)
+    p = _call_params(eng, E, H, W, hypAssignment.shape[0], (shiftX, shiftY, focalLength, ppointX, ppointY),
+                     (inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling), training=True)
     _state["call"] += 1
-    in_place = outGradients.is_cuda and outGradients.is_contiguous() and outGradients.device == eng.device
-    grads = outGradients if in_place else outGradients.to(eng.device).contiguous()
+    grads, copy_back = _stage_gradients(outGradients, eng)
     out = eng.backward_device(sceneCoordinates, grads, hypAssignment, gtPose.detach().cpu().numpy(), wLossRot, wLossTrans,
                               lossCut, p, pose_record=poseRecord)
-    if not in_place:
-        outGradients.copy_(grads)  # the accumulated tensor back into the caller's (CPU or strided) storage
+    if copy_back:
+        outGradients.copy_(grads)
     _state["last"] = {"backward": out}
     return float(out[0])
 
@@ -1459,45 +1473,29 @@ def _ragged_backward_args(who, sceneCoordinates, outGradients, hypAssignment, gt
     return int(B), int(N), E, shapes
 
 
-def _ragged_backward_params(eng, E, shapes, N, cam_scalars, score_args):
-    H, W = capacity_shape(shapes)
-    return eng.make_params(E, H, W, N, *cam_scalars, *score_args, seed=_state["seed"], call=_state["call"],
-                           max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"],
-                           strict_training=_state["strict_training"])
-
-
 def _ragged_backward_batch(who, sceneCoordinates, outGradients, hypAssignment, gtPoses, loss_args, cam_args, score_args, shapes,
                            experts, poseRecords):
     B, N, E, shapes = _ragged_backward_args(who, sceneCoordinates, outGradients, hypAssignment, gtPoses, shapes, experts, False)
     some = sceneCoordinates[0] if isinstance(sceneCoordinates, (list, tuple)) else sceneCoordinates
     if poseRecords is not None:
         _check_pose_records(who, "poseRecords", poseRecords, B, False, some.device if some.is_cuda else None)
-    if not hypAssignment.is_cuda:
-        lo, hi = int(hypAssignment.min()), int(hypAssignment.max())
-        if lo < 0 or hi >= E:
-            raise RuntimeError("%s: hypAssignment values must lie in [0,%d), found [%d,%d]" % (who, E, lo, hi))
+    _check_assignment_range(who, hypAssignment, E)
     cam_scalars, cams = _per_frame_cams(who, B, *cam_args)
-    if isinstance(sceneCoordinates, (list, tuple)):
-        on_dev = [m.device.index for m in sceneCoordinates if m.is_cuda]
-        eng = engine(on_dev[0] if on_dev else None)
-        packed, _ = pack_frames(sceneCoordinates, device=eng.device)
-    else:
-        eng = engine(sceneCoordinates.device.index if sceneCoordinates.is_cuda else None)
-        packed = sceneCoordinates
-    p = _ragged_backward_params(eng, E, shapes, N, cam_scalars, score_args)
+    eng = _engine_for(sceneCoordinates)
+    packed = pack_frames(sceneCoordinates, device=eng.device)[0] if isinstance(sceneCoordinates, (list, tuple)) else sceneCoordinates
+    p = _call_params(eng, E, *capacity_shape(shapes), N, cam_scalars, score_args, training=True)
     as_list = isinstance(outGradients, (list, tuple))
     if as_list:
-        grads, _ = pack_frames(list(outGradients), device=eng.device)
+        grads, copy_back = pack_frames(list(outGradients), device=eng.device)[0], False
     else:
-        in_place = outGradients.is_cuda and outGradients.is_contiguous() and outGradients.device == eng.device
-        grads = outGradients if in_place else outGradients.to(eng.device).contiguous()
+        grads, copy_back = _stage_gradients(outGradients, eng)
     out = eng.backward_batch_shapes(packed, grads, hypAssignment, gtPoses.detach().cpu().numpy(), *loss_args, p, shapes, cams=cams,
                                     pose_records=poseRecords)
     _state["call"] += B  # (behind the call: a table the library refuses draws no RNG stream)
     if as_list:
         for g, v in zip(outGradients, unpack_frames(grads, shapes, E)):
             g.copy_(v)  # the accumulated tensors back into the caller's
-    elif grads is not outGradients:
+    elif copy_back:
         outGradients.copy_(grads)
     _state["last"] = {"backward": out}
     return [float(v) for v in out[:, 0]]
@@ -1533,16 +1531,10 @@ def backward_batch_shapes_async(sceneCoordinates, outGradients, hypAssignment, g
     if poseRecords is not None:
         _check_pose_records(who, "poseRecords", poseRecords, B, True, sceneCoordinates.device if sceneCoordinates.is_cuda else None)
     cam_scalars, cams = _per_frame_cams(who, B, shiftX, shiftY, focalLength, ppointX, ppointY)
-    if not outGradients.is_contiguous():
-        raise RuntimeError("%s: outGradients must be contiguous (an asynchronous call cannot copy back into strided storage)" % who)
-    for name, t in (("outGradients", outGradients), ("sceneCoordinates", sceneCoordinates), ("hypAssignment", hypAssignment)):
-        if not t.is_cuda:
-            raise RuntimeError("%s: %s must be a device tensor (an asynchronous call stages nothing on the host)" % (who, name))
-    if outGradients.device != sceneCoordinates.device or hypAssignment.device != sceneCoordinates.device or \
-            (gtPoses.is_cuda and gtPoses.device != sceneCoordinates.device):
-        raise RuntimeError("%s: sceneCoordinates, outGradients, hypAssignment and a device gtPoses must live on one device" % who)
+    _check_async_tensors(who, sceneCoordinates, outGradients, hypAssignment, gtPoses, "stages nothing on the host")
     eng = engine(sceneCoordinates.device.index)
-    p = _ragged_backward_params(eng, E, shapes, N, cam_scalars, (inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling))
+    p = _call_params(eng, E, *capacity_shape(shapes), N, cam_scalars, (inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling),
+                     training=True)
     eng.arm_pose_records(poseRecords)
     rec = eng.backward_batch_shapes_async(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLossRot, wLossTrans, lossCut, p, shapes,
                                           cams=cams)
@@ -1569,24 +1561,16 @@ def backward_batch(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLoss
     if poseRecords is not None:
         _check_pose_records("esac.backward_batch", "poseRecords", poseRecords, B, False,
                             sceneCoordinates.device if sceneCoordinates.is_cuda else None)
-    if not hypAssignment.is_cuda:
-        lo, hi = int(hypAssignment.min()), int(hypAssignment.max())
-        if lo < 0 or hi >= E:
-            raise RuntimeError("esac.backward_batch: hypAssignment values must lie in [0,%d), found [%d,%d]" % (E, lo, hi))
-    (shiftX, shiftY, focalLength, ppointX, ppointY), cams = _per_frame_cams("esac.backward_batch", B, shiftX, shiftY, focalLength,
-                                                                             ppointX, ppointY)
-    eng = engine(sceneCoordinates.device.index if sceneCoordinates.is_cuda else None)
-    p = eng.make_params(E, H, W, N, shiftX, shiftY, focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha,
-                        inlierBeta, maxReproj, subSampling, seed=_state["seed"], call=_state["call"],
-                        max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"],
-                        strict_training=_state["strict_training"])
+    _check_assignment_range("esac.backward_batch", hypAssignment, E)
+    cam_scalars, cams = _per_frame_cams("esac.backward_batch", B, shiftX, shiftY, focalLength, ppointX, ppointY)
+    eng = _engine_for(sceneCoordinates)
+    p = _call_params(eng, E, H, W, N, cam_scalars, (inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling), training=True)
     _state["call"] += B
-    in_place = outGradients.is_cuda and outGradients.is_contiguous() and outGradients.device == eng.device
-    grads = outGradients if in_place else outGradients.to(eng.device).contiguous()
+    grads, copy_back = _stage_gradients(outGradients, eng)
     out = eng.backward_batch(sceneCoordinates, grads, hypAssignment, gtPoses.detach().cpu().numpy(), wLossRot, wLossTrans,
                              lossCut, p, cams=cams, pose_records=poseRecords)
-    if not in_place:
-        outGradients.copy_(grads)  # the accumulated tensors back into the caller's (CPU or strided) storage
+    if copy_back:
+        outGradients.copy_(grads)
     _state["last"] = {"backward": out}
     return [float(v) for v in out[:, 0]]
 
@@ -1612,23 +1596,10 @@ def backward_batch_async(sceneCoordinates, outGradients, hypAssignment, gtPoses,
     B, N, E, H, W = _check_batch_tensors(who, sceneCoordinates, outGradients, hypAssignment, gtPoses, name_each=True)
     if poseRecords is not None:
         _check_pose_records(who, "poseRecords", poseRecords, B, True, sceneCoordinates.device if sceneCoordinates.is_cuda else None)
-    (shiftX, shiftY, focalLength, ppointX, ppointY), cams = _per_frame_cams(who, B, shiftX, shiftY, focalLength, ppointX, ppointY)
-    if not outGradients.is_contiguous():
-        raise RuntimeError("%s: outGradients must be contiguous (an asynchronous call cannot copy back into strided storage)" % who)
-    if not outGradients.is_cuda:
-        raise RuntimeError("%s: outGradients must be a device tensor (an asynchronous call cannot copy back into host storage)" % who)
-    if not sceneCoordinates.is_cuda:
-        raise RuntimeError("%s: sceneCoordinates must be a device tensor (an asynchronous call stages nothing on the host)" % who)
-    if not hypAssignment.is_cuda:
-        raise RuntimeError("%s: hypAssignment must be a device tensor (an asynchronous call stages nothing on the host)" % who)
-    if outGradients.device != sceneCoordinates.device or hypAssignment.device != sceneCoordinates.device or \
-            (gtPoses.is_cuda and gtPoses.device != sceneCoordinates.device):
-        raise RuntimeError("%s: sceneCoordinates, outGradients, hypAssignment and a device gtPoses must live on one device" % who)
+    cam_scalars, cams = _per_frame_cams(who, B, shiftX, shiftY, focalLength, ppointX, ppointY)
+    _check_async_tensors(who, sceneCoordinates, outGradients, hypAssignment, gtPoses, "cannot copy back into host storage")
     eng = engine(sceneCoordinates.device.index)
-    p = eng.make_params(E, H, W, N, shiftX, shiftY, focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha,
-                        inlierBeta, maxReproj, subSampling, seed=_state["seed"], call=_state["call"],
-                        max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"],
-                        strict_training=_state["strict_training"])
+    p = _call_params(eng, E, H, W, N, cam_scalars, (inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling), training=True)
     _state["call"] += B
     eng.arm_pose_records(poseRecords)
     rec = eng.backward_batch_async(sceneCoordinates, outGradients, hypAssignment, gtPoses, wLossRot, wLossTrans, lossCut, p, cams=cams)
@@ -1780,9 +1751,7 @@ def verify_batch(sceneCoordinates, poses, experts, shiftX, shiftY, focalLength, 
         else:
             E = int(sceneCoordinates.shape[-4])
     (shiftX, shiftY, focalLength, ppointX, ppointY), cams = _per_frame_cams(who, B, shiftX, shiftY, focalLength, ppointX, ppointY)
-    on_dev = [t.device.index for t in (list(sceneCoordinates) if isinstance(sceneCoordinates, (list, tuple)) else [sceneCoordinates]) + [poses]
-              if isinstance(t, torch.Tensor) and t.is_cuda]
-    eng = engine(on_dev[0] if on_dev else None)
+    eng = _engine_for(sceneCoordinates, poses)
     if isinstance(sceneCoordinates, (list, tuple)):
         sceneCoordinates, _ = pack_frames(sceneCoordinates, device=eng.device)
     H, W = capacity_shape(shapes) if shapes is not None else (int(sceneCoordinates.shape[-2]), int(sceneCoordinates.shape[-1]))
@@ -1804,34 +1773,18 @@ def forward_batch_async(sceneCoordinates, hypAssignment, shiftX, shiftY, focalLe
     who = "esac.forward_batch_async"
     if not isinstance(hypAssignment, torch.Tensor) or hypAssignment.dim() != 2 or hypAssignment.dtype != torch.int64 or hypAssignment.numel() == 0:
         raise RuntimeError("%s: hypAssignment must be a non-empty int64 [B,N]" % who)
+    cam_args = (shiftX, shiftY, focalLength, ppointX, ppointY)
+    score_args = (inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling)
     if shapes is not None:
-        _, records, scores, first = _ragged_call(who, sceneCoordinates, hypAssignment, shapes, experts,
-                                                 (shiftX, shiftY, focalLength, ppointX, ppointY),
-                                                 (inlierThreshold, inlierAlpha, inlierBeta, maxReproj, subSampling), False)
-        _state["last"] = {"records": records, "scores": scores, "call": first, "seed": _state["seed"]}
-        return _state["last"]
-    if experts is not None:
-        raise RuntimeError("%s: experts is an argument of a ragged batch (shapes=...)" % who)
-    if not isinstance(sceneCoordinates, torch.Tensor) or sceneCoordinates.dtype != torch.float32 or sceneCoordinates.dim() not in (4, 5) \
-            or sceneCoordinates.size(-3) != 3:
-        raise RuntimeError("%s: sceneCoordinates must be float32 [B,E,3,H,W] or [E,3,H,W]" % who)
-    B, N = hypAssignment.shape
-    if B > MAX_BATCH:
-        raise RuntimeError("%s: hypAssignment holds %d frames, at most %d per call" % (who, B, MAX_BATCH))
-    if sceneCoordinates.dim() == 5 and sceneCoordinates.size(0) != B:
-        raise RuntimeError("%s: batch sizes of sceneCoordinates and hypAssignment differ" % who)
-    (shiftX, shiftY, focalLength, ppointX, ppointY), cams = _per_frame_cams(who, B, shiftX, shiftY, focalLength, ppointX, ppointY)
-    eng = engine(sceneCoordinates.device.index if sceneCoordinates.is_cuda else None)
-    E, H, W = sceneCoordinates.shape[-4], sceneCoordinates.shape[-2], sceneCoordinates.shape[-1]
-    p = eng.make_params(E, H, W, N, shiftX, shiftY, focalLength, ppointX, ppointY, inlierThreshold, inlierAlpha,
-                        inlierBeta, maxReproj, subSampling, seed=_state["seed"], call=_state["call"],
-                        max_tries=_state["max_tries"], max_ref_steps=_state["max_ref_steps"],
-                        strict_reference=_state["strict_reference"])
-    first = _state["call"]
-    _state["call"] += B
-    scores = torch.empty(B, N, dtype=torch.float64, device=eng.device)
-    # (zeros: a frame whose kernels never reach the record write reads RES_VALID = 0 -> EVAL_STATUS 1, not stale memory)
-    records = torch.zeros(B, RES_DOUBLES, dtype=torch.float64, device=eng.device)
-    eng.forward_batch(sceneCoordinates, hypAssignment, p, scores_out=scores, result_out=records, want_host=False, cams=cams)
+        _, records, scores, first = _ragged_call(who, sceneCoordinates, hypAssignment, shapes, experts, cam_args, score_args, False)
+    else:
+        if experts is not None:
+            raise RuntimeError("%s: experts is an argument of a ragged batch (shapes=...)" % who)
+        if not isinstance(sceneCoordinates, torch.Tensor) or sceneCoordinates.dtype != torch.float32 or sceneCoordinates.dim() not in (4, 5) \
+                or sceneCoordinates.size(-3) != 3:
+            raise RuntimeError("%s: sceneCoordinates must be float32 [B,E,3,H,W] or [E,3,H,W]" % who)
+        if hypAssignment.shape[0] > MAX_BATCH:
+            raise RuntimeError("%s: hypAssignment holds %d frames, at most %d per call" % (who, hypAssignment.shape[0], MAX_BATCH))
+        _, records, scores, first = _shared_call(who, sceneCoordinates, hypAssignment, cam_args, score_args, False)
     _state["last"] = {"records": records, "scores": scores, "call": first, "seed": _state["seed"]}
     return _state["last"]
